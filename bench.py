@@ -17,7 +17,18 @@ re-initialises at its first frame.  The warm-up steps are the first W frames of 
 timed steps the next K.  The one exchange step of the path -- the all-gather of the chunk-boundary
 poses, 12 doubles per chunk, RCCL for N > 1 -- is inside the timed region.  Weak scaling.
 
-Reported beside ``value`` (all measured in this invocation, nothing carried as a literal):
+A plain run does only what the headline needs: set-up, the W warm-up steps, the K timed steps ONCE
+(``ms_per_step`` = the clock over them / K), the outputs (``--dump-outputs DIR``) and the line.
+``--full`` adds everything below: the timed region repeated until ``--min-timed-s`` is on the clock,
+the instrumented pass behind ``roofline`` and the stage table, the legs beyond the front-end's clock
+and the CPU baseline.
+
+``--dump-outputs DIR`` writes, after the timed steps, what the timed path returned to its caller at
+its last step (rank 0's chunks) and the chunk start poses of the exchange, as float64 ``.npy`` files:
+last_step_{R,t,inliers,tracked,keyframe} and chunk_start_{R,t}.  The inputs are the same on every run
+with the same arguments (seeded generator, no clock in them).
+
+Reported beside ``value`` with ``--full`` (all measured in this invocation, nothing carried as a literal):
   value_including_chunk_inits  the whole share again, every chunk's stereo initialisation included
   single_chunk_frames_per_s    ONE contiguous chunk per GPU (the north-star's partitioning),
                                pipelined, over rank 0's whole share
@@ -76,6 +87,34 @@ def lk_pmc_constants(n_kpts: int):
     if d.get("lk_hip_sha256") != sha or d.get("kpts") != n_kpts:
         return None
     return d
+
+
+def render_stream(scene, poses, device: str, batch: int = 8):
+    """``synth.stereo_torch(scene, poses, device=device, batch=batch)`` with every distinct pose ray-cast once.  The bench
+    loop is closed (a lap of 492 frames): past the first lap each pose repeats an earlier one bit for bit, and the renderer
+    is a per-pixel function of the pose, so a repeat's images are copies of the first render.  The stream is laid out as
+    stereo_torch lays it out (one tensor per batch of frames: its left images, then its right images)."""
+    import torch
+    from ros_stereo_slam_amd import synth
+
+    keys = [np.asarray(R, np.float64).tobytes() + np.asarray(t, np.float64).tobytes() for R, t in poses]
+    slot, uniq = {}, []
+    for p, k in zip(poses, keys):
+        if k not in slot:
+            slot[k] = len(uniq)
+            uniq.append(p)
+    ul, ur = synth.stereo_torch(scene, uniq, device=device, batch=batch)
+    lefts, rights = [], []
+    for s in range(0, len(poses), batch):
+        js = [slot[k] for k in keys[s:s + batch]]
+        if js == list(range(s, s + len(js))):     # first renders: stereo_torch's own batch
+            lefts.extend(ul[j] for j in js)
+            rights.extend(ur[j] for j in js)
+            continue
+        both = torch.stack([ul[j] for j in js] + [ur[j] for j in js])
+        lefts.extend(both[i] for i in range(len(js)))
+        rights.extend(both[len(js) + i] for i in range(len(js)))
+    return lefts, rights
 
 
 def rel_truth(poses):
@@ -203,6 +242,11 @@ def main():
     ap.add_argument("--steps", type=int, default=50,
                     help="timed steps; one step = one frame of every chunk of the GPU (64 frames per GPU with the defaults)")
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: repeats up to --min-timed-s, the instrumented pass (roofline, stage "
+                         "table), the legs beyond the front-end's clock and the CPU baseline; the --no-* options below trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned at its last step as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
                     help="only the contract's timed region (no re-run with inits, no single-chunk run, no pose graph)")
@@ -225,11 +269,22 @@ def main():
     ap.add_argument("--no-kernel-timing", action="store_true",
                     help="diagnostic: no HIP events around the kernels (the roofline object is then empty)")
     ap.add_argument("--min-timed-s", type=float, default=1.0,
-                    help="the K timed steps are repeated (warm-up untimed every time) until this much time is on the clock")
+                    help="--full: the K timed steps are repeated (warm-up untimed every time) until this much time is on the clock")
     ap.add_argument("--max-repeats", type=int, default=16)
     ap.add_argument("--kitti", default=None, help="KITTI odometry root (holds sequences/<seq>/image_2, image_3)")
     ap.add_argument("--seq", default="00")
     args = ap.parse_args()
+    if not args.full:
+        # the headline alone: the K timed steps once, nothing measured beside them.  An option that only shapes what
+        # --full adds is refused rather than silently dropped.
+        full_only = [f"--{d.replace('_', '-')}" for d in ("no_cpu_baseline", "no_extras", "no_kpts8192", "no_host_images",
+                                                          "cpu_frames", "no_detector", "no_kernel_timing", "min_timed_s",
+                                                          "max_repeats")
+                     if getattr(args, d) != ap.get_default(d)]
+        if full_only:
+            ap.error(f"{', '.join(full_only)} only apply with --full")
+        args.no_extras = args.no_kernel_timing = args.no_cpu_baseline = True
+        args.min_timed_s = 0.0
     if args.kitti is not None:
         return kitti_leg(args)
     if args.gpus < 1:
@@ -284,7 +339,7 @@ def main():
     poses_all = synth.loop_trajectory(world * share + 1, **synth.BENCH_LOOP)
     my_poses = poses_all[rank * share:(rank + 1) * share + 1]
     t_r0 = time.perf_counter()
-    lefts, rights = synth.stereo_torch(scene, my_poses, device=f"cuda:{local_rank}", batch=8)
+    lefts, rights = render_stream(scene, my_poses, device=f"cuda:{local_rank}", batch=8)
     torch.cuda.synchronize()
     render_s = time.perf_counter() - t_r0
 
@@ -420,7 +475,7 @@ def main():
         return [(v, lefts[s + lo:s + b + 1], rights[s + lo:s + b + 1]) for v, (s, e) in zip(sh.vos, bounds)]
 
     def run(a: int, b: int, init: bool, out, stats=None):
-        """advance every chunk from its local frame a to b (init: seed on frame a first)"""
+        """advance every chunk from its local frame a to b (init: seed on frame a first); -> capi.run_chunks' results"""
         res = capi.run_chunks(jobs_for(a, b, init), pipeline=pipeline, init=init)
         for m, (rc, done, Rs, ts, inl, trk, kf) in enumerate(res):
             if rc or done != b - a:
@@ -432,6 +487,7 @@ def main():
                 stats["keyframes"] += int(kf.sum())
                 stats["inliers"] += int(inl.sum())
                 stats["tracked"] += int(trk.sum())
+        return res
 
     def lk_launch_alone(sh_, frames_per_chunk: int):
         """Mean duration of a tracking launch that has the chip to ITSELF: the first lock-step group (one context, one
@@ -532,6 +588,7 @@ def main():
     # ---- the timed region: EXACTLY --steps steps + the path's one exchange, REPEATED (each repeat: every chunk's stereo
     # initialisation + its first W frames untimed, then the K timed steps) until at least --min-timed-s seconds are on the
     # clock, so that a box's +-2 % does not decide a round.  value = all frames of all repeats / all time.
+    # A plain run (no --full) does it once.
     reps = []               # (elapsed max over ranks, elapsed local)
     local = None
     target_s = max(0.0, args.min_timed_s)
@@ -549,7 +606,7 @@ def main():
         torch.cuda.synchronize()
         sh.sync()
         t0 = time.perf_counter()
-        run(Wn, L, False, loc_r, st_r)
+        res_timed = run(Wn, L, False, loc_r, st_r)
         boundaries = exchange(loc_r)
         starts = chunked.prefix_transforms(boundaries)  # global pose of every chunk's first frame
         assert len(starts) == world * M
@@ -569,6 +626,15 @@ def main():
     elapsed = sum(e for e, _ in reps) / len(reps)           # mean duration of the K timed steps
     elapsed_local = sum(e for _, e in reps) / len(reps)
     ranks_seen = dist.get_world_size() if dist is not None else 1   # after a real all-gather over the group
+    if args.dump_outputs and rank == 0:
+        # the last timed step as run_chunks handed it to its caller (rank 0's chunks), and the exchange's result
+        dump = {"last_step_R": [r[2][-1] for r in res_timed], "last_step_t": [r[3][-1] for r in res_timed],
+                "last_step_inliers": [r[4][-1] for r in res_timed], "last_step_tracked": [r[5][-1] for r in res_timed],
+                "last_step_keyframe": [r[6][-1] for r in res_timed],
+                "chunk_start_R": [R for R, _ in starts], "chunk_start_t": [t for _, t in starts]}
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in dump.items():
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), np.asarray(a, np.float64))
 
     trace("instrumented pass")
     # ---- the SAME frames once more with HIP events around every launch: per-kernel launch durations for the
@@ -646,17 +712,7 @@ def main():
         t_sh = np.array([t for _, t in traj])
         path_len = float(np.sum(np.linalg.norm(np.diff(t_truth, axis=0), axis=1)))
         fps = world * n_frames / elapsed
-        lk_ms, lk_launches = times.get("lk", (0.0, 0))
-        if not lk_launches and M > 1:
-            # no instrumented pass: a lock-step group step queues two tracking launches per context (the frame's pass of
-            # all its chunks, the stereo pass of those that keyframe)
-            lk_launches = 2 * K * len(sh.ctxs)
-        # passes carried by the LK launches of the timed region: one tracking pass per frame + one stereo pass per keyframe
-        passes = n_frames + stats["keyframes"]
         kf_rate = stats["keyframes"] / n_frames
-        roof = roofline_of(n_kpts, lk_ms, lk_launches, passes, alone_main, elapsed, G if M > 1 else 1)
-        roof["launches_per_step"] = lk_launches / K
-        roof["frame_hbm_frac"] = frame_algorithmic_bytes(n_kpts, kf_rate) / (elapsed / n_frames) / 8e12
         ate_sh = chunked.ate_rmse(t_sh, t_truth)
         result = {
             "metric": f"stereo frames/sec @1241x376, {n_kpts} kpts",
@@ -710,8 +766,19 @@ def main():
             "path_length_m": path_len,
             "ate_rmse_vs_truth": ate_sh,
             "ate_over_path_length": ate_sh / path_len,
-            "roofline": roof,
         }
+        if args.full:
+            lk_ms, lk_launches = times.get("lk", (0.0, 0))
+            if not lk_launches and M > 1:
+                # no instrumented pass: a lock-step group step queues two tracking launches per context (the frame's pass of
+                # all its chunks, the stereo pass of those that keyframe)
+                lk_launches = 2 * K * len(sh.ctxs)
+            # passes carried by the LK launches of the timed region: one tracking pass per frame + one stereo pass per keyframe
+            passes = n_frames + stats["keyframes"]
+            roof = roofline_of(n_kpts, lk_ms, lk_launches, passes, alone_main, elapsed, G if M > 1 else 1)
+            roof["launches_per_step"] = lk_launches / K
+            roof["frame_hbm_frac"] = frame_algorithmic_bytes(n_kpts, kf_rate) / (elapsed / n_frames) / 8e12
+            result["roofline"] = roof
         result.update(extras)
 
     # ---- one contiguous chunk per GPU: measured before the communicator existed (single); its trajectory figures ----

@@ -4,15 +4,16 @@
 set -u
 cd "$GRAFT_REPO_ROOT" || exit 1
 ROUNDS=$1; shift
-mkdir -p gpurun_out/abenv
+OUT=${OUT:-out}/abenv
+mkdir -p $OUT
 for r in $(seq 1 "$ROUNDS"); do
   i=0
   for v in "$@"; do
     i=$((i+1))
-    env $v timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras ${BENCH_FLAGS:-} > gpurun_out/abenv/${i}_$r.json 2> gpurun_out/abenv/${i}_$r.err || { echo "$v round $r failed"; tail -5 gpurun_out/abenv/${i}_$r.err; exit 1; }
+    env $v timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extras ${BENCH_FLAGS:-} > $OUT/${i}_$r.json 2> $OUT/${i}_$r.err || { echo "$v round $r failed"; tail -5 $OUT/${i}_$r.err; exit 1; }
     python3 -c "
 import json
-d=json.loads(open('gpurun_out/abenv/${i}_$r.json').read().strip().splitlines()[-1])
+d=json.loads(open('$OUT/${i}_$r.json').read().strip().splitlines()[-1])
 print('$v', $r, round(d['${BENCH_KEY:-value}']), flush=True)" || exit 1
   done
 done

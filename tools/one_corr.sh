@@ -1,12 +1,13 @@
 #!/bin/bash
 # kernel trace + HIP API trace of ONE chunk per GPU in the same run: for every kernel, when was its launch call made
-# relative to the end of the previous kernel on its queue (host-late or device-late?) -> gpurun_out/one_corr.txt
+# relative to the end of the previous kernel on its queue (host-late or device-late?) -> $OUT/one_corr.txt
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 export GPU_MAX_HW_QUEUES=${GPU_MAX_HW_QUEUES:-8}
+OUT=${OUT:-out}; mkdir -p $OUT
 rm -rf /tmp/onec
-timeout -k 10 300 rocprofv3 --kernel-trace --hip-runtime-trace --output-format csv -d /tmp/onec -o one -- python3 bench.py --chunks-per-gpu 1 --steps 100 --warmup 5 --no-cpu-baseline --no-extras --no-kernel-timing > gpurun_out/onec_bench.json 2> gpurun_out/onec.err || exit 1
-python3 - $(find /tmp/onec -name "one_kernel_trace.csv") $(find /tmp/onec -name "one_hip_api_trace.csv") > gpurun_out/one_corr.txt <<'PY'
+timeout -k 10 300 rocprofv3 --kernel-trace --hip-runtime-trace --output-format csv -d /tmp/onec -o one -- python3 bench.py --full --chunks-per-gpu 1 --steps 100 --warmup 5 --no-cpu-baseline --no-extras --no-kernel-timing > $OUT/onec_bench.json 2> $OUT/onec.err || exit 1
+python3 - $(find /tmp/onec -name "one_kernel_trace.csv") $(find /tmp/onec -name "one_hip_api_trace.csv") > $OUT/one_corr.txt <<'PY'
 import csv,sys
 ks=[r for r in csv.DictReader(open(sys.argv[1])) if not any(x in r['Kernel_Name'] for x in ('at::','elementwise','vectorized','rocprim','hipcub','fillBuffer'))]
 api={}

@@ -15,13 +15,13 @@ OUT=gpurun_out/r03
 mkdir -p $OUT
 echo "{\"GPU_MAX_HW_QUEUES\": \"$GPU_MAX_HW_QUEUES\", \"lk_hip_sha256\": \"$(sha256sum ros_stereo_slam_amd/csrc/lk.hip | cut -d' ' -f1)\"}" > $OUT/environment.json
 keep() { head -1 "$1" > "$2"; grep -v "at::\|elementwise\|vectorized\|Memcpy\|rocprim\|hipcub\|fillBuffer" "$1" | tail -n +2 >> "$2"; }
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-extras --no-kernel-timing"
+ARGS="--full --steps 20 --warmup 5 --no-cpu-baseline --no-extras --no-kernel-timing"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r03_trace -o bench -- python3 bench.py $ARGS > $OUT/trace_bench.json 2> $OUT/trace.err || exit 1
 keep $(find /tmp/r03_trace -name "bench_kernel_stats.csv") $OUT/kernel_stats.csv
 keep $(find /tmp/r03_trace -name "bench_kernel_trace.csv") $OUT/kernel_trace.csv
 [ "$1" = trace ] && exit 0
 for K in 4096 8192; do
-PARGS="--steps 6 --warmup 1 --no-cpu-baseline --no-extras --no-kernel-timing --kpts $K"
+PARGS="--full --steps 6 --warmup 1 --no-cpu-baseline --no-extras --no-kernel-timing --kpts $K"
 timeout -k 10 400 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU --kernel-trace --output-format csv -d /tmp/r03_sq_$K -o sq -- python3 bench.py $PARGS > $OUT/sq_bench_$K.json 2> $OUT/sq_$K.err || exit 2
 keep $(find /tmp/r03_sq_$K -name "sq_counter_collection.csv") $OUT/sq_counter_collection_$K.csv
 keep $(find /tmp/r03_sq_$K -name "sq_kernel_trace.csv") $OUT/sq_kernel_trace_$K.csv
@@ -30,11 +30,11 @@ keep $(find /tmp/r03_fetch_$K -name "fetch_counter_collection.csv") $OUT/fetch_c
 timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d /tmp/r03_write_$K -o write -- python3 bench.py $PARGS > $OUT/write_bench_$K.json 2> $OUT/write_$K.err || exit 4
 keep $(find /tmp/r03_write_$K -name "write_counter_collection.csv") $OUT/write_counter_collection_$K.csv
 done
-timeout -k 10 300 python3 bench.py --chunks-per-gpu 1 --steps 100 --warmup 5 --no-cpu-baseline --no-extras --no-kernel-timing > $OUT/one_plain.json 2> $OUT/one_plain.err || exit 5
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/r03_one -o one -- python3 bench.py --chunks-per-gpu 1 --steps 100 --warmup 5 --no-cpu-baseline --no-extras --no-kernel-timing > $OUT/one_bench.json 2> $OUT/one.err || exit 6
+timeout -k 10 300 python3 bench.py --full --chunks-per-gpu 1 --steps 100 --warmup 5 --no-cpu-baseline --no-extras --no-kernel-timing > $OUT/one_plain.json 2> $OUT/one_plain.err || exit 5
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/r03_one -o one -- python3 bench.py --full --chunks-per-gpu 1 --steps 100 --warmup 5 --no-cpu-baseline --no-extras --no-kernel-timing > $OUT/one_bench.json 2> $OUT/one.err || exit 6
 keep $(find /tmp/r03_one -name "one_kernel_trace.csv") $OUT/one_trace.csv
 # the one-chunk stages from device time stamps (no profiler in the way: its interception makes the host the bottleneck of this run)
-SVO_CHAIN_STAMPS=1 timeout -k 10 300 python3 bench.py --chunks-per-gpu 1 --steps 200 --warmup 10 --no-cpu-baseline --no-extras --no-kernel-timing > $OUT/one_stamps.json 2> $OUT/one_stamps.err || exit 11
+SVO_CHAIN_STAMPS=1 timeout -k 10 300 python3 bench.py --full --chunks-per-gpu 1 --steps 200 --warmup 10 --no-cpu-baseline --no-extras --no-kernel-timing > $OUT/one_stamps.json 2> $OUT/one_stamps.err || exit 11
 grep "svo chain" $OUT/one_stamps.err > $OUT/one_stamps.txt
 timeout -k 10 300 python3 tools/pg_profile.py 4541 40 3 > $OUT/pg_plain.log 2>&1 || exit 7
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r03_pg -o pg -- python3 tools/pg_profile.py 4541 40 1 > $OUT/pg_prof.log 2>&1 || exit 8

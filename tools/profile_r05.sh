@@ -23,12 +23,12 @@ timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CYCL
 cp $(find /tmp/r05_vr -name "vr_counter_collection.csv") $OUT/valu_rate_counter_collection.csv
 cp $(find /tmp/r05_vr -name "vr_kernel_trace.csv") $OUT/valu_rate_kernel_trace.csv
 [ "$1" = valu ] && exit 0
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-extras --no-kernel-timing --min-timed-s 0"
+ARGS="--full --steps 20 --warmup 5 --no-cpu-baseline --no-extras --no-kernel-timing --min-timed-s 0"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/r05_trace -o bench -- python3 bench.py $ARGS > $OUT/trace_bench.json 2> $OUT/trace.err || exit 3
 keep $(find /tmp/r05_trace -name "bench_kernel_stats.csv") $OUT/kernel_stats.csv
 keep $(find /tmp/r05_trace -name "bench_kernel_trace.csv") $OUT/kernel_trace.csv
 for K in ${KPTS:-4096 8192}; do
-PARGS="--steps 6 --warmup 1 --no-cpu-baseline --no-extras --no-kernel-timing --min-timed-s 0 --kpts $K"
+PARGS="--full --steps 6 --warmup 1 --no-cpu-baseline --no-extras --no-kernel-timing --min-timed-s 0 --kpts $K"
 timeout -k 10 400 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU --kernel-trace --output-format csv -d /tmp/r05_sq_$K -o sq -- python3 bench.py $PARGS > $OUT/sq_bench_$K.json 2> $OUT/sq_$K.err || exit 4
 keep $(find /tmp/r05_sq_$K -name "sq_counter_collection.csv") $OUT/sq_counter_collection_$K.csv
 keep $(find /tmp/r05_sq_$K -name "sq_kernel_trace.csv") $OUT/sq_kernel_trace_$K.csv
