@@ -169,6 +169,38 @@ int svo_sor_filter(svo_ctx *ctx, const float *xyz, const float *color, int n, in
                    float z_limit, float *xyz_out, float *color_out, int *n_out, float *mean_dist_out,
                    int *n_pass_out, int mem);
 
+/* ---- dense stereo: StereoProcess::stereoMatch / reprojectDisparity, src/StereoCV.cpp:21-59,227-250 -- */
+/* cv::StereoSGBM::create(1, 96, 7, 24, 96, 0, 60, 0, 3000, 5) + compute(grey1, grey2, disp) of
+ * src/StereoCV.cpp:40-53 (MODE_SGBM: five paths, BT costs, median 3, filterSpeckles).  The recipe
+ * and every recalled point of it: tests/sgbm_numpy.py, DESIGN.md section 10.                    */
+enum { SVO_SGBM_MODE_SGBM = 0 };
+typedef struct svo_sgbm_params {
+    int min_disparity, num_disparities, block_size, p1, p2, disp12_max_diff,
+        pre_filter_cap, uniqueness_ratio, speckle_window_size, speckle_range, mode;
+} svo_sgbm_params;
+/* the reference's values, src/StereoCV.cpp:40-51                                                 */
+void svo_sgbm_default_params(svo_sgbm_params *p);
+/* n_pairs (1..16) pairs of h x w x c images (c = 1 grey, c = 3 BGR converted as cvtColor BGR2GRAY,
+ * src/StereoCV.cpp:37-38), back to back where `mem` says; disp: n_pairs x h x w int16, disparity
+ * x 16, invalid = (min_disparity - 1) * 16.  SVO_ERR_ARG: num_disparities not a positive multiple
+ * of 16 up to 256, an even block_size or one outside 1..11, p2 <= p1, w <= num_disparities +
+ * min_disparity, an unknown mode.  SVO_ERR_CAPACITY: w > 2048 or more than 2^30 cost cells
+ * (n_pairs x h x band columns x num_disparities) per call.                                       */
+int svo_sgbm_compute(svo_ctx *ctx, const svo_sgbm_params *p, const uint8_t *left, const uint8_t *right,
+                     int w, int h, int c, int n_pairs, int16_t *disp, int mem);
+/* Q of cv::stereoRectify(K, 0, K, 0, size, I, (tx, 0, 0)) as src/StereoCV.cpp:229-234 calls it
+ * (CALIB_ZERO_DISPARITY); Q16 row-major.  tx = +baseline is the reference's call (Q[3][2] < 0:
+ * negative depths); tx = -baseline the conventional one.  Host only.       */
+int svo_stereo_rectify_q(double fx, double fy, double cx, double cy, double tx, int w, int h, double *Q16);
+/* disp.convertTo(CV_32F, disp_scale) + reprojectImageTo3D(disp, img3d, Q) + the loop of
+ * src/StereoCV.cpp:240-249: pixels with Z > z_max or Z <= z_min skipped, (X, flip_y ? -Y : Y, Z)
+ * and the image's B, G, R (grey replicated) as floats, row-major.  disp_scale 1 = the reference
+ * (16 x the disparity), 1/16 = metric.  Q16: host.  xyz_out / bgr_out: w*h x 3 capacity (bgr_out
+ * may be NULL, then image may be too).  *n_out is a HOST int in both modes.                     */
+int svo_stereo_reproject(svo_ctx *ctx, const int16_t *disp, const uint8_t *image, int w, int h, int c,
+                         const double *Q16, float disp_scale, float z_min, float z_max, int flip_y,
+                         float *xyz_out, float *bgr_out, int *n_out, int mem);
+
 /* ---- loop-closure detection: features ---------------------------------------------------------- */
 /* cv::ORB::create()->detectAndCompute(img, Mat(), kp, desc) of visualSLAM::checkLoopDetectorStatus,
  * src/optimizationStuff.cpp:49-56.  image: h x w x c (BGR or grey).  Up to n_features (500

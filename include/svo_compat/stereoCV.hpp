@@ -1,8 +1,10 @@
-// svo_compat/stereoCV.hpp -- the one member of the reference's StereoProcess
-// (include/stereoCV.h:59-71) that overlaps the hot path: stereoTriangulate(im1, im2, out3d).
-// The rest of that class is a separate SGBM dense-stereo demo (src/StereoCV.cpp) publishing
-// over ROS/PCL; it is outside the hot-path scope and is not provided.
+// svo_compat/stereoCV.hpp -- the reference's StereoProcess (include/stereoCV.h:32-73): stereoTriangulate(im1, im2,
+// out3d) on the hot path's sparse stereo, and the dense SGBM demo of src/StereoCV.cpp -- stereoMatch(iter) and
+// reprojectDisparity(disp, pts, colours) -- on svo_sgbm_compute / svo_stereo_reproject.  pclPublish (SOR + ROS),
+// visualizeCloud and mainLoop are not provided.
 #pragma once
+
+#include <cstdio>
 
 #include "visualSLAM.hpp"
 
@@ -16,6 +18,65 @@ class StereoProcess {
     std::vector<Point3f> tri3dPoints, color3dMap;
 
     explicit StereoProcess(svo_ctx *ctx = nullptr) : slam_(ctx) {}
+    // include/stereoCV.h:52-57 (the ROS publisher is not created)
+    StereoProcess(const char *lptr, const char *rptr, svo_ctx *ctx = nullptr) : lFptr(lptr), rFptr(rptr), slam_(ctx)
+    {
+        ctx_ = ctx ? ctx : shared_context();
+    }
+
+    // include/stereoCV.h:36-48
+    const char *lFptr = nullptr, *rFptr = nullptr;
+    Mat lImg, rImg;
+    Mat K = k_matrix(focal_x, focal_y, cx, cy);
+    // false (default): reprojectDisparity does what the reference does -- Q of stereoRectify with t = +baseline and the
+    // raw x16 disparities, which puts every valid pixel behind the camera so that its (0.01, 5] window keeps nothing
+    // (DESIGN.md section 10).  true: the conventional Q (t = -baseline) and disparities / 16, metric points.
+    bool metricDisparity = false;
+
+    // src/StereoCV.cpp:21-59: both frames loaded as visualSLAM::loadImageL / R do (B,G,R, svo_io_load_frame), converted
+    // to grey and matched with StereoSGBM(1, 96, 7, 24, 96, 0, 60, 0, 3000, 5).  Returns CV_16SC1, disparity x 16; an
+    // empty Mat when a frame is missing (the reference prints and carries on).
+    Mat stereoMatch(int iter)
+    {
+        lImg = load_bgr(lFptr, iter);
+        rImg = load_bgr(rFptr, iter);
+        if (lImg.empty() || rImg.empty() || lImg.rows != rImg.rows || lImg.cols != rImg.cols)
+            return Mat();
+        svo_sgbm_params prm;
+        svo_sgbm_default_params(&prm);
+        Mat disp(lImg.rows, lImg.cols, kDisp16S);
+        if (disp.elemSize() != 2)
+            throw std::runtime_error("stereoMatch: this Mat type has no 16-bit elements");
+        check(svo_sgbm_compute(ctx(), &prm, lImg.data, rImg.data, lImg.cols, lImg.rows, 3, 1,
+                               reinterpret_cast<int16_t *>(disp.data), SVO_MEM_HOST));
+        return disp;
+    }
+
+    // src/StereoCV.cpp:227-250: Q from stereoRectify, reprojectImageTo3D, points with Z > 5 or Z <= 0.01 skipped,
+    // (X, -Y, Z) and lImg's B, G, R as floats in row-major order
+    void reprojectDisparity(Mat disp, std::vector<Point3f> &reproject3dPoints, std::vector<Point3f> &colorMap)
+    {
+        reproject3dPoints.clear();
+        colorMap.clear();
+        if (disp.empty())
+            return;
+        if (disp.elemSize() != 2 || lImg.empty() || lImg.rows != disp.rows || lImg.cols != disp.cols)
+            throw std::invalid_argument("reprojectDisparity: expected a CV_16S disparity map of lImg's size");
+        double Q[16];
+        check(svo_stereo_rectify_q(focal_x, focal_y, cx, cy, metricDisparity ? -baseline : baseline, disp.cols, disp.rows, Q));
+        const size_t n = (size_t)disp.rows * disp.cols;
+        std::vector<float> xyz(n * 3), bgr(n * 3);
+        int kept = 0;
+        check(svo_stereo_reproject(ctx(), reinterpret_cast<const int16_t *>(disp.data), lImg.data, disp.cols, disp.rows,
+                                   lImg.channels(), Q, metricDisparity ? 1.0f / 16 : 1.0f, 0.01f, 5.0f, 1, xyz.data(),
+                                   bgr.data(), &kept, SVO_MEM_HOST));
+        reproject3dPoints.reserve(kept);
+        colorMap.reserve(kept);
+        for (int i = 0; i < kept; i++) {
+            reproject3dPoints.emplace_back(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
+            colorMap.emplace_back(bgr[3 * i], bgr[3 * i + 1], bgr[3 * i + 2]);
+        }
+    }
 
     // include/stereoCV.h:62.  The reference matches SIFT features here (src/StereoCV.cpp:64-121);
     // this adaptor uses the hot path's dense-grid LK + F-RANSAC + DLT triangulation instead and
@@ -34,6 +95,34 @@ class StereoProcess {
     }
 
   private:
+#if defined(SVO_WITH_OPENCV) && defined(CV_16SC1)
+    static constexpr int kDisp16S = CV_16SC1;
+#else
+    static constexpr int kDisp16S = 3;  // CV_16SC1
+#endif
+    svo_ctx *ctx_ = nullptr;
+    svo_ctx *ctx() { return ctx_ ? ctx_ : (ctx_ = shared_context()); }
+    static Mat k_matrix(double fx, double fy, double cx_, double cy_)
+    {
+        Mat k = Mat::zeros(3, 3, CV_64F);
+        k.at<double>(0, 0) = fx, k.at<double>(0, 2) = cx_, k.at<double>(1, 1) = fy, k.at<double>(1, 2) = cy_;
+        k.at<double>(2, 2) = 1;
+        return k;
+    }
+    static Mat load_bgr(const char *pattern, int iter)
+    {
+        char path[1024];
+        int w = 0, h = 0, c = 0;
+        if (!pattern || svo_io_format_path(path, (int)sizeof(path), pattern, iter) != SVO_OK ||
+            svo_io_image_info(path, &w, &h, &c) != SVO_OK) {
+            std::fprintf(stderr, "\n\nYIKES Dawg, Failed to fetch frame, check the file path\n\n\n");
+            return Mat();
+        }
+        Mat im(h, w, CV_8UC3);
+        if (svo_io_read_image(path, 3, im.data, (size_t)w * h * 3, &w, &h) != SVO_OK)
+            return Mat();
+        return im;
+    }
     visualSLAM slam_;
 };
 

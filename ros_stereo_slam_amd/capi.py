@@ -408,6 +408,91 @@ def orb_extract_batch(self, images, **params):
             for i in range(len(images))]
 
 
+class SgbmParams(C.Structure):
+    """``svo_sgbm_params``: cv::StereoSGBM::create's arguments (defaults: the reference's, src/StereoCV.cpp:40-51)."""
+    _fields_ = [(n, C.c_int) for n in ("min_disparity", "num_disparities", "block_size", "p1", "p2", "disp12_max_diff",
+                                       "pre_filter_cap", "uniqueness_ratio", "speckle_window_size", "speckle_range", "mode")]
+
+
+SGBM_MODE_SGBM = 0
+
+
+def sgbm_params(**overrides) -> SgbmParams:
+    p = SgbmParams()
+    load().svo_sgbm_default_params(C.byref(p))
+    for k, v in overrides.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def stereo_rectify_q(fx, fy, cx, cy, tx, w, h) -> np.ndarray:
+    """``svo_stereo_rectify_q``: Q of stereoRectify(K, 0, K, 0, (w, h), I, (tx, 0, 0)) as a 4 x 4 array."""
+    Q = np.zeros(16, np.float64)
+    _check(load().svo_stereo_rectify_q(C.c_double(fx), C.c_double(fy), C.c_double(cx), C.c_double(cy), C.c_double(tx),
+                                       int(w), int(h), _ptr(Q)))
+    return Q.reshape(4, 4)
+
+
+def _is_device(a) -> bool:
+    return hasattr(a, "is_cuda") and bool(a.is_cuda)
+
+
+@_ctx_method
+def sgbm(self, left, right, **params):
+    """``svo_sgbm_compute`` (StereoProcess::stereoMatch, src/StereoCV.cpp:21-59): one pair (h x w or h x w x c) or a
+    batch (n x h x w x c), numpy arrays or device tensors (both sides alike) -> int16 disparities x 16 of the same
+    leading shape, a numpy array for host inputs and a device tensor for device inputs."""
+    prm = sgbm_params(**params)
+    dev = _is_device(left)
+    assert dev == _is_device(right), "left and right must live in the same memory"
+    shape = tuple(left.shape)
+    assert tuple(right.shape) == shape
+    single = len(shape) in (2, 3)   # a batch is always n x h x w x c
+    if len(shape) == 2:
+        n, h, w, c = 1, shape[0], shape[1], 1
+    elif len(shape) == 3:
+        n, (h, w, c) = 1, shape
+    else:
+        n, h, w, c = shape
+        single = False
+    if dev:
+        import torch
+
+        lt, rt = left.contiguous(), right.contiguous()
+        out = torch.empty((n, h, w), dtype=torch.int16, device=left.device)
+        torch.cuda.synchronize(left.device)
+        _check(self.lib.svo_sgbm_compute(self._h, C.byref(prm), _ptr(lt), _ptr(rt), w, h, c, n, _ptr(out), MEM_DEVICE))
+        _check(self.lib.svo_ctx_sync(self._h))
+        return out[0] if single else out
+    lt = np.ascontiguousarray(left, np.uint8)
+    rt = np.ascontiguousarray(right, np.uint8)
+    out = np.empty((n, h, w), np.int16)
+    _check(self.lib.svo_sgbm_compute(self._h, C.byref(prm), _ptr(lt), _ptr(rt), w, h, c, n, _ptr(out), MEM_HOST))
+    return out[0] if single else out
+
+
+@_ctx_method
+def stereo_reproject(self, disp, image, Q, disp_scale=1.0, z_min=0.01, z_max=5.0, flip_y=True):
+    """``svo_stereo_reproject`` (StereoProcess::reprojectDisparity, src/StereoCV.cpp:227-250) -> (xyz [n,3], bgr [n,3])
+    float32 host arrays, row-major order.  disp: h x w int16; image: h x w (x c) uint8 or None."""
+    disp = np.ascontiguousarray(disp, np.int16)
+    h, w = disp.shape
+    img, c = None, 1
+    if image is not None:
+        img = np.ascontiguousarray(image, np.uint8)
+        c = 1 if img.ndim == 2 else img.shape[2]
+    q = np.ascontiguousarray(Q, np.float64).reshape(16)
+    xyz = np.empty((h * w, 3), np.float32)
+    bgr = np.empty((h * w, 3), np.float32) if img is not None else None
+    n = C.c_int()
+    _check(self.lib.svo_stereo_reproject(self._h, _ptr(disp), _ptr(img), w, h, c, _ptr(q), C.c_float(disp_scale),
+                                         C.c_float(z_min), C.c_float(z_max), int(bool(flip_y)), _ptr(xyz), _ptr(bgr),
+                                         C.byref(n), MEM_HOST))
+    k = n.value
+    return xyz[:k].copy(), (bgr[:k].copy() if bgr is not None else None)
+
+
 MATH_FN = {"sin": 0, "cos": 1, "acos": 2, "cbrt": 3, "log": 4}
 
 

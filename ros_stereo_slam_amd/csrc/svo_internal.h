@@ -128,6 +128,8 @@ struct svo_ctx {
     hipStream_t up_stream = nullptr;
     DevBuf up_ring;
     hipEvent_t up_ev[3] = {nullptr, nullptr, nullptr}, use_ev[3] = {nullptr, nullptr, nullptr};
+    // sgbm.hip: the dense matcher's cost volume and path planes, its per-pixel work arrays, the reprojection's staging
+    DevBuf sgbm_cost, sgbm_misc, sgbm_rp;
 };
 
 // Low-latency host wait for everything queued on the context's stream: records an event and
