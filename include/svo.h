@@ -168,6 +168,19 @@ int svo_get_colors(svo_ctx *ctx, const svo_pyramid *pyr, const float *xy, int n,
 int svo_sor_filter(svo_ctx *ctx, const float *xyz, const float *color, int n, int mean_k, double stddev_mul,
                    float z_limit, float *xyz_out, float *color_out, int *n_out, float *mean_dist_out,
                    int *n_pass_out, int mem);
+/* The same filter for large clouds -- StereoProcess::pclPublish's pcl::StatisticalOutlierRemoval (MeanK 20,
+ * StddevMulThresh 0.8, src/StereoCV.cpp:289-293) of a dense cloud, or SORcloud of an accumulated map.  Same
+ * arguments and outputs as svo_sor_filter, for n up to 4194304 (2^22, else SVO_ERR_CAPACITY) and mean_k 1..256
+ * (else SVO_ERR_ARG).  For every cloud both accept it returns the same bits as svo_sor_filter: mean distances, kept
+ * points and colours.  That holds because the multiset of the kk = min(mean_k, m - 1) smallest float squared
+ * distances is unique (ties cannot change it), and its double sum of square roots does not depend on order whenever
+ * it is exact (any realistic spread: exact while the largest term over the smallest nonzero one stays below
+ * 2^29 / kk).  A point with a NaN or infinite coordinate is dropped with the z pre-filter: it counts neither as
+ * passed nor as kept (PCL would keep it).  In device mode the outputs must not overlap the inputs.  The search is
+ * an exact kNN over the Morton-sorted cloud with a box hierarchy.                        */
+int svo_sor_filter_large(svo_ctx *ctx, const float *xyz, const float *color, int n, int mean_k, double stddev_mul,
+                         float z_limit, float *xyz_out, float *color_out, int *n_out, float *mean_dist_out,
+                         int *n_pass_out, int mem);
 
 /* ---- dense stereo: StereoProcess::stereoMatch / reprojectDisparity, src/StereoCV.cpp:21-59,227-250 -- */
 /* cv::StereoSGBM::create(1, 96, 7, 24, 96, 0, 60, 0, 3000, 5) + compute(grey1, grey2, disp) of

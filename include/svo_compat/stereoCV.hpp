@@ -1,10 +1,13 @@
 // svo_compat/stereoCV.hpp -- the reference's StereoProcess (include/stereoCV.h:32-73): stereoTriangulate(im1, im2,
 // out3d) on the hot path's sparse stereo, and the dense SGBM demo of src/StereoCV.cpp -- stereoMatch(iter) and
-// reprojectDisparity(disp, pts, colours) -- on svo_sgbm_compute / svo_stereo_reproject.  pclPublish (SOR + ROS),
+// reprojectDisparity(disp, pts, colours) -- on svo_sgbm_compute / svo_stereo_reproject -- and pclPublish(pts, colours)
+// on svo_sor_filter_large, the filtered cloud left in publishedCloud / publishedColors instead of a ROS message.
 // visualizeCloud and mainLoop are not provided.
 #pragma once
 
+#include <cstdint>
 #include <cstdio>
+#include <stdexcept>
 
 #include "visualSLAM.hpp"
 
@@ -78,6 +81,42 @@ class StereoProcess {
         }
     }
 
+    // src/StereoCV.cpp:275-296 minus ROS: every point in PCL's frame, (x, z, y) x mulFactor 5 (float products), its
+    // colour as the uint8_t r = colorMap.z, g = .y, b = .x fields (clamped to 0..255, truncated), then
+    // pcl::StatisticalOutlierRemoval with MeanK 20 and StddevMulThresh 0.8 (svo_sor_filter_large, at most 2^22
+    // points).  The kept points (x, y, z) and colours (r, g, b) go to publishedCloud / publishedColors, in input order;
+    // pts3d and colorMap are left as they are.
+    std::vector<Point3f> publishedCloud, publishedColors;
+    void pclPublish(std::vector<Point3f> &pts3d, std::vector<Point3f> &colorMap)
+    {
+        publishedCloud.clear();
+        publishedColors.clear();
+        if (colorMap.size() < pts3d.size())
+            throw std::invalid_argument("pclPublish: a colour for every point is needed");
+        const int mulFactor = 5;
+        const size_t n = pts3d.size();
+        if (n > (size_t)(1 << 22))
+            throw std::length_error("pclPublish: at most 2^22 points");
+        std::vector<float> xyz(n * 3), rgb(n * 3), xyz_out(n * 3), rgb_out(n * 3);
+        for (size_t i = 0; i < n; i++) {
+            xyz[3 * i] = pts3d[i].x * mulFactor;
+            xyz[3 * i + 1] = pts3d[i].z * mulFactor;
+            xyz[3 * i + 2] = pts3d[i].y * mulFactor;
+            rgb[3 * i] = pcl_channel(colorMap[i].z);
+            rgb[3 * i + 1] = pcl_channel(colorMap[i].y);
+            rgb[3 * i + 2] = pcl_channel(colorMap[i].x);
+        }
+        int kept = 0;
+        check(svo_sor_filter_large(ctx(), xyz.data(), rgb.data(), (int)n, 20, 0.8, 0.0f, xyz_out.data(), rgb_out.data(),
+                                   &kept, nullptr, nullptr, SVO_MEM_HOST));
+        publishedCloud.reserve(kept);
+        publishedColors.reserve(kept);
+        for (int i = 0; i < kept; i++) {
+            publishedCloud.emplace_back(xyz_out[3 * i], xyz_out[3 * i + 1], xyz_out[3 * i + 2]);
+            publishedColors.emplace_back(rgb_out[3 * i], rgb_out[3 * i + 1], rgb_out[3 * i + 2]);
+        }
+    }
+
     // include/stereoCV.h:62.  The reference matches SIFT features here (src/StereoCV.cpp:64-121);
     // this adaptor uses the hot path's dense-grid LK + F-RANSAC + DLT triangulation instead and
     // says so: same output contract (camera-frame 3-D points, colours in color3dMap).
@@ -101,6 +140,8 @@ class StereoProcess {
     static constexpr int kDisp16S = 3;  // CV_16SC1
 #endif
     svo_ctx *ctx_ = nullptr;
+    // a float colour as a uint8_t field of pcl::PointXYZRGB holds it: clamped to 0..255 (NaN to 0), then truncated
+    static float pcl_channel(float v) { return v > 0.f ? (float)(uint8_t)(v < 255.f ? v : 255.f) : 0.f; }
     svo_ctx *ctx() { return ctx_ ? ctx_ : (ctx_ = shared_context()); }
     static Mat k_matrix(double fx, double fy, double cx_, double cy_)
     {

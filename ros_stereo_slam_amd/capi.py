@@ -521,6 +521,41 @@ def sor_filter(self, xyz, color=None, mean_k=200, stddev_mul=0.01, z_limit=500.0
 
 
 @_ctx_method
+def sor_filter_large(self, xyz, color=None, mean_k=20, stddev_mul=0.8, z_limit=0.0):
+    """``svo_sor_filter_large``: sor_filter's algorithm and results for up to 2^22 points; the defaults are
+    StereoProcess::pclPublish's (src/StereoCV.cpp:289-293).  numpy arrays, or device tensors (float32, n x 3, on the
+    context's device) which give device tensors back -> (xyz_kept, color_kept or None, mean_dist)."""
+    if _is_device(xyz):
+        import torch
+
+        assert color is None or _is_device(color), "xyz and color must live in the same memory"
+        xt = xyz.reshape(-1, 3).contiguous()
+        ct = None if color is None else color.reshape(-1, 3).contiguous()
+        assert xt.dtype == torch.float32 and (ct is None or (ct.dtype == torch.float32 and ct.shape == xt.shape))
+        n = xt.shape[0]
+        xo = torch.empty((max(n, 1), 3), dtype=torch.float32, device=xt.device)
+        co = torch.empty_like(xo) if ct is not None else None
+        md = torch.empty(max(n, 1), dtype=torch.float32, device=xt.device)
+        torch.cuda.synchronize(xt.device)
+        mem = MEM_DEVICE
+    else:
+        xt = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        ct = None if color is None else np.ascontiguousarray(color, np.float32).reshape(-1, 3)
+        n = xt.shape[0]
+        xo, md = np.zeros((max(n, 1), 3), np.float32), np.zeros(max(n, 1), np.float32)
+        co = np.zeros((max(n, 1), 3), np.float32) if ct is not None else None
+        mem = MEM_HOST
+    kept, passed = C.c_int(), C.c_int()
+    _check(self.lib.svo_sor_filter_large(self._h, _ptr(xt), _ptr(ct), n, int(mean_k), C.c_double(stddev_mul),
+                                         C.c_float(z_limit), _ptr(xo), _ptr(co), C.byref(kept), _ptr(md), C.byref(passed),
+                                         mem))
+    k, p = kept.value, passed.value
+    if mem == MEM_DEVICE:
+        return xo[:k], (co[:k] if co is not None else None), md[:p]
+    return xo[:k].copy(), (co[:k].copy() if co is not None else None), md[:p].copy()
+
+
+@_ctx_method
 def pnp_ransac(self, obj, img, K4, iterations=100, reproj_err=1.0, confidence=0.99, seed=0):
     obj = np.ascontiguousarray(obj, np.float32).reshape(-1, 3)
     img = np.ascontiguousarray(img, np.float32).reshape(-1, 2)

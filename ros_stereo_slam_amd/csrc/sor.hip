@@ -14,6 +14,7 @@
 // PCL's loop does, so the threshold is bit-identical to the sequential algorithm.
 // Brute force: N^2 distance evaluations out of L2 (N <= 9216: 110 kB), no HBM traffic to speak of.
 #include "ransac_common.hip.h"
+#include "sor_common.hip.h"
 #include "svo_internal.h"
 
 namespace {
@@ -24,14 +25,6 @@ __global__ __launch_bounds__(256) void sor_zmask_kernel(const float *__restrict_
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n)
         mask[i] = (z_limit > 0.f && -1.f * xyz[3 * i + 2] > z_limit) ? 0 : 1;
-}
-
-__device__ __forceinline__ double wave_sum_double(double v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-        v += __shfl_xor(v, off, 64);
-    return v;
 }
 
 template <int T>
@@ -84,36 +77,6 @@ __global__ __launch_bounds__(256) void sor_knn_kernel(const float *__restrict__ 
     const double total = wave_sum_double(s_less) + (double)(kk - c_less) * (double)sqrtf(__uint_as_float(kth));
     if (lane == 0)
         dist[a] = (float)(total / kk);
-}
-
-// mean / stddev of the distances in point order by one thread (PCL's own loop), then the keep mask
-__global__ __launch_bounds__(1024) void sor_threshold_kernel(const float *__restrict__ dist,
-                                                             const int *__restrict__ d_m, double stddev_mul, int cap,
-                                                             uint8_t *__restrict__ mask)
-{
-    __shared__ double s_thr;
-    const int m = *d_m;
-    if (threadIdx.x == 0) {
-        double sum = 0, sq_sum = 0;
-        for (int i = 0; i < m; i++) {
-            const float d = dist[i];
-            sum += d;
-            sq_sum += d * d;  // the product in float, as upstream
-        }
-        double thr = 1.7976931348623157e308;
-        if (m > 1) {
-            const double mean = sum / m;
-            double variance = (sq_sum - sum * sum / m) / (m - 1);
-            if (variance < 0)
-                variance = 0;
-            thr = mean + stddev_mul * sqrt(variance);
-        }
-        s_thr = thr;
-    }
-    __syncthreads();
-    const double thr = s_thr;
-    for (int i = threadIdx.x; i < cap; i += 1024)
-        mask[i] = (i < m && (double)dist[i] <= thr) ? 1 : 0;
 }
 
 }  // namespace

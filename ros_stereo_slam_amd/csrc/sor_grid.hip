@@ -1,0 +1,648 @@
+// sor_grid.hip -- statistical outlier removal of large clouds (up to 2^22 points) for gfx950: svo_sor_filter_large.
+//
+// The algorithm and every rounding step are svo_sor_filter's (sor.hip, oracle/sor.c): the z pre-filter, the mean
+// distance to the kk = min(mean_k, m - 1) nearest OTHER points (float squared distances dx*dx + dy*dy + dz*dz, their
+// sqrtf summed in double), the cloud statistics in point order, keep d <= mean + mul * stddev.  Points with a
+// non-finite coordinate are dropped with the z pre-filter (they must never reach the quantisation below).
+//
+// What differs is the neighbour search, which sor.hip does by brute force (one wave per point, every distance in VGPRs,
+// hence its 9216-point cap):
+//   1. bounds of the surviving cloud; every point gets a 63-bit Morton key of its cell on a 2^21 grid per axis;
+//   2. (key, index) pairs sorted by a stable LSD radix sort (8-bit digits, 8 passes; the first device sort of the
+//      project, its own section below), the points gathered into Morton order;
+//   3. a fixed-fan-out box hierarchy over the sorted array: the bounding box of every 64 consecutive points (level 1),
+//      of every 64 level-1 boxes (level 2) and of every 64 level-2 boxes (level 3, at most 16 of them for 2^22 points);
+//   4. ONE WAVE PER QUERY, queries in Morton order: the query's neighbours in the sorted array seed a per-wave LDS
+//      buffer of candidate squared distances (float bits, which order like unsigned ints); the hierarchy is then
+//      walked, and a box is skipped only when a lower bound of the float squared distance of any point inside it
+//      (computed in double from the query's true coordinates, shrunk by 1e-6 relative, far more than the six
+//      roundings of the float expression) is not below the current kk-th smallest candidate.  When the buffer
+//      fills, it is cut to its kk smallest values (entries below the kk-th smallest plus copies of it: the multiset of
+//      the kk smallest values is all the mean needs, ties cannot change it) and later points are appended only
+//      when strictly below that value.  The kk-th smallest is sor.hip's 31-step bitwise search with wave-wide counts.
+//   5. the threshold kernel and the compaction, shared with sor.hip.
+// Every loop is bounded by construction: 8 sort passes, at most 16 x 64 x 64 level-1 boxes per query, 31 bit steps
+// per selection, and a buffer cut frees at least CAP - kk - 64 slots.  Degenerate clouds (all points identical,
+// collinear, one far point) only make the boxes overlap more; the walk then visits more of them, never more than all.
+//
+// Exactness: the multiset of the kk smallest float squared distances of every query is the brute force's, and the
+// mean is sum(sqrtf(d) for d < kth) + (kk - count) * sqrtf(kth) in double, as in sor.hip -- the same bits whenever
+// that double sum is exact (any realistic spread of distances: float square roots carry 24 significant bits, so
+// the sum is exact while the ratio of the largest to the smallest nonzero term stays below 2^29 / kk).
+#include "ransac_common.hip.h"
+#include "sor_common.hip.h"
+#include "svo_internal.h"
+
+#define SVO_SOR_LARGE_MAX_N (1 << 22)
+#define SVO_SOR_LARGE_MAX_K 256
+
+namespace {
+
+// ---- stable LSD radix sort of (uint64 key, int value) pairs ------------------------------------------------------
+// A tile of RS_TILE elements per workgroup.  Per pass: a digit histogram per tile, one exclusive scan over
+// (digit, tile), then a scatter that ranks every element among the equal digits of its tile in element order (lane
+// order inside a wave by ballot matching, wave order inside a round, round order inside the tile).
+constexpr int RS_THREADS = 256, RS_ROUNDS = 16, RS_TILE = RS_THREADS * RS_ROUNDS;
+
+// lanes of this wave that hold the same 8-bit digit (valid lanes only)
+__device__ __forceinline__ unsigned long long match_digit(bool valid, unsigned d)
+{
+    unsigned long long peers = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < 8; b++) {
+        const bool on = (d >> b) & 1u;
+        const unsigned long long bb = __ballot(on);
+        peers &= on ? bb : ~bb;
+    }
+    return peers;
+}
+
+__global__ __launch_bounds__(RS_THREADS) void radix_hist_kernel(const uint64_t *__restrict__ keys, int n, int shift,
+                                                                int nblk, unsigned *__restrict__ hist)
+{
+    __shared__ unsigned h[256];
+    const int tid = threadIdx.x, lane = tid & 63;
+    h[tid] = 0;
+    __syncthreads();
+    const int base = blockIdx.x * RS_TILE;
+    for (int r = 0; r < RS_ROUNDS; r++) {
+        const int i = base + r * RS_THREADS + tid;
+        const bool valid = i < n;
+        const unsigned d = valid ? (unsigned)(keys[i] >> shift) & 255u : 0u;
+        const unsigned long long peers = match_digit(valid, d);
+        if (valid && (peers & ((1ull << lane) - 1ull)) == 0)  // the lowest lane of its digit adds for all of them
+            atomicAdd(&h[d], (unsigned)__popcll(peers));
+    }
+    __syncthreads();
+    hist[tid * nblk + blockIdx.x] = h[tid];
+}
+
+// exclusive scan of total (= 256 x nblk, digit-major) counts in place, one workgroup
+__global__ __launch_bounds__(1024) void radix_scan_kernel(unsigned *__restrict__ h, int total)
+{
+    __shared__ unsigned part[1024];
+    const int tid = threadIdx.x;
+    const int per = (total + 1023) / 1024;
+    const int s = tid * per, e = min(s + per, total);
+    unsigned sum = 0;
+    for (int j = s; j < e; j++)
+        sum += h[j];
+    part[tid] = sum;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+        const unsigned v = tid >= off ? part[tid - off] : 0u;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    unsigned run = part[tid] - sum;
+    for (int j = s; j < e; j++) {
+        const unsigned t = h[j];
+        h[j] = run;
+        run += t;
+    }
+}
+
+__global__ __launch_bounds__(RS_THREADS) void radix_scatter_kernel(const uint64_t *__restrict__ kin,
+                                                                   const int *__restrict__ vin,
+                                                                   uint64_t *__restrict__ kout, int *__restrict__ vout,
+                                                                   int n, int shift, int nblk,
+                                                                   const unsigned *__restrict__ hist)
+{
+    __shared__ unsigned run[256];
+    __shared__ unsigned wcnt[RS_THREADS / 64][256];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    run[tid] = hist[tid * nblk + blockIdx.x];
+#pragma unroll
+    for (int q = 0; q < RS_THREADS / 64; q++)
+        wcnt[q][tid] = 0;
+    __syncthreads();
+    const int base = blockIdx.x * RS_TILE;
+    for (int r = 0; r < RS_ROUNDS && base + r * RS_THREADS < n; r++) {  // the bound is uniform over the workgroup
+        const int i = base + r * RS_THREADS + tid;
+        const bool valid = i < n;
+        const uint64_t key = valid ? kin[i] : 0ull;
+        const unsigned d = (unsigned)(key >> shift) & 255u;
+        const unsigned long long peers = match_digit(valid, d);
+        const int rank = __popcll(peers & ((1ull << lane) - 1ull));
+        if (valid && rank == 0)
+            wcnt[w][d] = (unsigned)__popcll(peers);
+        __syncthreads();
+        if (valid) {
+            unsigned pos = run[d] + (unsigned)rank;
+            for (int q = 0; q < w; q++)
+                pos += wcnt[q][d];
+            kout[pos] = key;
+            vout[pos] = vin[i];
+        }
+        __syncthreads();
+        unsigned add = 0;
+#pragma unroll
+        for (int q = 0; q < RS_THREADS / 64; q++) {
+            add += wcnt[q][tid];
+            wcnt[q][tid] = 0;
+        }
+        run[tid] += add;
+        __syncthreads();
+    }
+}
+
+// sorts k0/v0 in place (8 passes over the 64-bit keys, k1/v1 the ping-pong buffers); hist: 256 x ceil(n / RS_TILE)
+int radix_sort_pairs(hipStream_t st, uint64_t *k0, int *v0, uint64_t *k1, int *v1, int n, unsigned *hist)
+{
+    if (n <= 0)
+        return SVO_OK;
+    const int nblk = (n + RS_TILE - 1) / RS_TILE;
+    for (int pass = 0; pass < 8; pass++) {
+        const int shift = 8 * pass;
+        const uint64_t *ki = pass & 1 ? k1 : k0;
+        const int *vi = pass & 1 ? v1 : v0;
+        uint64_t *ko = pass & 1 ? k0 : k1;
+        int *vo = pass & 1 ? v0 : v1;
+        hipLaunchKernelGGL(radix_hist_kernel, dim3(nblk), dim3(RS_THREADS), 0, st, ki, n, shift, nblk, hist);
+        hipLaunchKernelGGL(radix_scan_kernel, dim3(1), dim3(1024), 0, st, hist, 256 * nblk);
+        hipLaunchKernelGGL(radix_scatter_kernel, dim3(nblk), dim3(RS_THREADS), 0, st, ki, vi, ko, vo, n, shift, nblk,
+                           hist);
+    }
+    SVO_HIP(hipGetLastError());
+    return SVO_OK;
+}
+
+// ---- the cloud: pre-filter, bounds, keys, Morton order, box hierarchy ---------------------------------------------
+__global__ __launch_bounds__(256) void sorg_zmask_kernel(const float *__restrict__ xyz, int n, float z_limit,
+                                                         uint8_t *__restrict__ mask)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
+        const bool finite = isfinite(x) && isfinite(y) && isfinite(z);
+        mask[i] = (!finite || (z_limit > 0.f && -1.f * z > z_limit)) ? 0 : 1;
+    }
+}
+
+// bnd: lo x, y, z, cells per unit (doubles); one workgroup
+__global__ __launch_bounds__(1024) void sorg_bounds_kernel(const float *__restrict__ xyz, const int *__restrict__ d_m,
+                                                           double *__restrict__ bnd)
+{
+    __shared__ float s_lo[3][1024], s_hi[3][1024];
+    const int m = *d_m, tid = threadIdx.x;
+    float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
+    float hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+    for (int i = tid; i < m; i += 1024)
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            const float v = xyz[3 * i + a];
+            lo[a] = fminf(lo[a], v);
+            hi[a] = fmaxf(hi[a], v);
+        }
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        s_lo[a][tid] = lo[a];
+        s_hi[a][tid] = hi[a];
+    }
+    __syncthreads();
+    for (int off = 512; off >= 1; off >>= 1) {
+        if (tid < off)
+#pragma unroll
+            for (int a = 0; a < 3; a++) {
+                s_lo[a][tid] = fminf(s_lo[a][tid], s_lo[a][tid + off]);
+                s_hi[a][tid] = fmaxf(s_hi[a][tid], s_hi[a][tid + off]);
+            }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        double ext = 0;
+        for (int a = 0; a < 3; a++) {
+            const double e = m > 0 ? (double)s_hi[a][0] - (double)s_lo[a][0] : 0.0;
+            ext = e > ext ? e : ext;
+            bnd[a] = m > 0 ? (double)s_lo[a][0] : 0.0;
+        }
+        bnd[3] = ext > 0 ? 2097152.0 / ext : 0.0;
+    }
+}
+
+__device__ __forceinline__ uint64_t spread3_21(uint64_t x)
+{
+    x &= 0x1fffffull;
+    x = (x | x << 32) & 0x1f00000000ffffull;
+    x = (x | x << 16) & 0x1f0000ff0000ffull;
+    x = (x | x << 8) & 0x100f00f00f00f00full;
+    x = (x | x << 4) & 0x10c30c30c30c30c3ull;
+    x = (x | x << 2) & 0x1249249249249249ull;
+    return x;
+}
+
+// keys of the m points; slots m..n-1 get the largest key (they sort last); values: the point's index
+__global__ __launch_bounds__(256) void sorg_key_kernel(const float *__restrict__ xyz, const int *__restrict__ d_m,
+                                                       const double *__restrict__ bnd, int n, uint64_t *__restrict__ keys,
+                                                       int *__restrict__ vals)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    uint64_t key = ~0ull;
+    if (i < *d_m) {
+        const double inv = bnd[3];
+        uint64_t c[3];
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            const double q = floor(((double)xyz[3 * i + a] - bnd[a]) * inv);
+            c[a] = q <= 0.0 ? 0ull : (q >= 2097151.0 ? 2097151ull : (uint64_t)q);
+        }
+        key = spread3_21(c[0]) | spread3_21(c[1]) << 1 | spread3_21(c[2]) << 2;
+    }
+    keys[i] = key;
+    vals[i] = i;
+}
+
+__global__ __launch_bounds__(256) void sorg_gather_kernel(const float *__restrict__ xyz, const int *__restrict__ idx,
+                                                          const int *__restrict__ d_m, int n, float *__restrict__ pts)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || i >= *d_m)
+        return;
+    const int j = idx[i];
+    pts[3 * i] = xyz[3 * j];
+    pts[3 * i + 1] = xyz[3 * j + 1];
+    pts[3 * i + 2] = xyz[3 * j + 2];
+}
+
+__device__ __forceinline__ float wave_min(float v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1)
+        v = fminf(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+__device__ __forceinline__ float wave_max(float v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1)
+        v = fmaxf(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+// number of elements at a level of the hierarchy: 0 = points, 1..3 = boxes
+__device__ __forceinline__ int level_count(int m, int level)
+{
+    for (int l = 0; l < level; l++)
+        m = (m + 63) >> 6;
+    return m;
+}
+
+// one wave per box of `level` (1..3): the bounds of its 64 children (points for level 1, boxes below), as
+// lo x, y, z, hi x, y, z
+__global__ __launch_bounds__(256) void sorg_box_kernel(const float *__restrict__ child, const int *__restrict__ d_m,
+                                                       int level, int cap_boxes, float *__restrict__ box)
+{
+    const int b = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    const int m = *d_m;
+    const int nb = level_count(m, level), nc = level_count(m, level - 1);
+    if (b >= nb || b >= cap_boxes)
+        return;
+    const int c = b * 64 + lane;
+    float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
+    float hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+    if (c < nc) {
+        if (level == 1) {
+#pragma unroll
+            for (int a = 0; a < 3; a++)
+                lo[a] = hi[a] = child[3 * c + a];
+        } else {
+#pragma unroll
+            for (int a = 0; a < 3; a++) {
+                lo[a] = child[6 * c + a];
+                hi[a] = child[6 * c + 3 + a];
+            }
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        lo[a] = wave_min(lo[a]);
+        hi[a] = wave_max(hi[a]);
+    }
+    if (lane == 0)
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            box[6 * b + a] = lo[a];
+            box[6 * b + 3 + a] = hi[a];
+        }
+}
+
+// ---- the per-query search ------------------------------------------------------------------------------------------
+constexpr int KNN_CAP = 1024;         // candidate squared distances per wave (LDS)
+constexpr int KNN_WAVES = 4;          // waves per workgroup
+
+// squared distance lower bound of any point of box b to (px, py, pz), in double
+__device__ __forceinline__ double box_mind2(const float *__restrict__ box, int b, float px, float py, float pz)
+{
+    const float p[3] = {px, py, pz};
+    double s = 0;
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const double lo = box[6 * b + a], hi = box[6 * b + 3 + a], v = p[a];
+        const double g = lo > v ? lo - v : (v > hi ? v - hi : 0.0);
+        s += g * g;
+    }
+    return s;
+}
+
+// true when no point of a box whose double lower bound is mind2 can have a float squared distance below r2
+__device__ __forceinline__ bool box_skippable(double mind2, unsigned r2)
+{
+    return mind2 * (1.0 - 1e-6) - 1e-37 >= (double)__uint_as_float(r2);
+}
+
+__device__ __forceinline__ double shfl_double(double v, int src)
+{
+    return __shfl(v, src, 64);
+}
+
+struct KnnWave {
+    unsigned *buf;  // KNN_CAP entries of this wave's LDS
+    int nb;         // entries held
+    bool full;      // the buffer holds exactly the kk smallest seen so far (after a cut); r2 = the largest of them
+    unsigned r2;
+    int kk, lane;
+};
+
+// the kk-th smallest of the buffer: the largest v with count(entry < v) < kk, built bit by bit (as sor.hip)
+__device__ unsigned knn_kth(const KnnWave &w)
+{
+    unsigned kth = 0;
+    for (int bit = 30; bit >= 0; bit--) {
+        const unsigned test = kth | (1u << bit);
+        int c = 0;
+        for (int t = w.lane; t < w.nb; t += 64)
+            c += w.buf[t] < test ? 1 : 0;
+        if (svo::wave_sum_small(c) < w.kk)
+            kth = test;
+    }
+    return kth;
+}
+
+// cut the buffer (nb >= kk) to its kk smallest values: entries below the kk-th smallest in place, then copies of it
+__device__ void knn_cut(KnnWave &w)
+{
+    const unsigned kth = knn_kth(w);
+    int out = 0;
+    for (int base = 0; base < w.nb; base += 64) {  // in place: every write lands at or below the chunk just read
+        const int t = base + w.lane;
+        const unsigned v = t < w.nb ? w.buf[t] : 0xffffffffu;
+        const bool keep = t < w.nb && v < kth;
+        const unsigned long long bal = __ballot(keep);
+        __builtin_amdgcn_wave_barrier();
+        if (keep)
+            w.buf[out + __popcll(bal & ((1ull << w.lane) - 1ull))] = v;
+        __builtin_amdgcn_wave_barrier();
+        out += __popcll(bal);
+    }
+    for (int t = out + w.lane; t < w.kk; t += 64)
+        w.buf[t] = kth;
+    __builtin_amdgcn_wave_barrier();
+    w.nb = w.kk;
+    w.full = true;
+    w.r2 = kth;
+}
+
+// one batch of up to 64 candidates (one per lane)
+__device__ __forceinline__ void knn_append(KnnWave &w, bool cand, unsigned d)
+{
+    bool keep = cand && (!w.full || d < w.r2);
+    unsigned long long bal = __ballot(keep);
+    if (bal == 0)
+        return;
+    if (w.nb + __popcll(bal) > KNN_CAP) {  // nb > KNN_CAP - 64 >= kk: a cut leaves kk
+        knn_cut(w);
+        keep = cand && d < w.r2;
+        bal = __ballot(keep);
+    }
+    if (keep)
+        w.buf[w.nb + __popcll(bal & ((1ull << w.lane) - 1ull))] = d;
+    __builtin_amdgcn_wave_barrier();
+    w.nb += __popcll(bal);
+}
+
+__device__ __forceinline__ unsigned dist2_bits(const float *__restrict__ pts, int j, float px, float py, float pz)
+{
+    const float dx = px - pts[3 * j], dy = py - pts[3 * j + 1], dz = pz - pts[3 * j + 2];
+    return __float_as_uint(dx * dx + dy * dy + dz * dz);
+}
+
+// queries in Morton order, one wave each; dist[idx[i]] = mean distance of sorted point i
+__global__ __launch_bounds__(256) void sorg_knn_kernel(const float *__restrict__ pts, const int *__restrict__ idx,
+                                                       const int *__restrict__ d_m, int mean_k,
+                                                       const float *__restrict__ box1, const float *__restrict__ box2,
+                                                       const float *__restrict__ box3, float *__restrict__ dist)
+{
+    __shared__ unsigned s_buf[KNN_WAVES][KNN_CAP];
+    const int m = *d_m;
+    const int lane = threadIdx.x & 63;
+    const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * KNN_WAVES + (threadIdx.x >> 6));
+    if (i >= m)
+        return;
+    const int kk = mean_k < m - 1 ? mean_k : m - 1;
+    if (kk <= 0) {
+        if (lane == 0)
+            dist[idx[i]] = 0.f;
+        return;
+    }
+    const float px = pts[3 * i], py = pts[3 * i + 1], pz = pts[3 * i + 2];
+    KnnWave w;
+    w.buf = s_buf[threadIdx.x >> 6];
+    w.nb = 0;
+    w.full = false;
+    w.r2 = 0xffffffffu;
+    w.kk = kk;
+    w.lane = lane;
+
+    // seed: the query's neighbours in Morton order, at least kk other points (m - 1 >= kk)
+    const int h = (kk + 1) / 2 + 32, span = 2 * h + 1;
+    int w1 = min(m, max(i - h, 0) + span);
+    const int w0 = max(0, w1 - span);
+    for (int base = w0; base < w1; base += 64) {
+        const int j = base + lane;
+        const bool cand = j < w1 && j != i;
+        knn_append(w, cand, cand ? dist2_bits(pts, j, px, py, pz) : 0u);
+    }
+    knn_cut(w);
+
+    // the hierarchy, boxes skipped when provably too far (tested when a level's children are listed, and again with the
+    // tighter bound of the moment before a box is entered); the seed window is not visited twice
+    const int n1 = (m + 63) >> 6, n2 = (n1 + 63) >> 6, n3 = (n2 + 63) >> 6;  // n3 <= 16
+    const double md3 = lane < n3 ? box_mind2(box3, lane, px, py, pz) : 0.0;
+    for (unsigned long long m3 = __ballot(lane < n3 && !box_skippable(md3, w.r2)); m3; m3 &= m3 - 1) {
+        const int k3 = __builtin_ctzll(m3);
+        if (box_skippable(shfl_double(md3, k3), w.r2))
+            continue;
+        const int c2 = k3 * 64 + lane;
+        const double md2 = c2 < n2 ? box_mind2(box2, c2, px, py, pz) : 0.0;
+        for (unsigned long long m2 = __ballot(c2 < n2 && !box_skippable(md2, w.r2)); m2; m2 &= m2 - 1) {
+            const int k2 = __builtin_ctzll(m2);
+            if (w.nb >= kk + 64)
+                knn_cut(w);
+            if (box_skippable(shfl_double(md2, k2), w.r2))
+                continue;
+            const int c1 = (k3 * 64 + k2) * 64 + lane;
+            const double md1 = c1 < n1 ? box_mind2(box1, c1, px, py, pz) : 0.0;
+            for (unsigned long long m1 = __ballot(c1 < n1 && !box_skippable(md1, w.r2)); m1; m1 &= m1 - 1) {
+                const int k1 = __builtin_ctzll(m1);
+                if (w.nb >= kk + 64)
+                    knn_cut(w);
+                if (box_skippable(shfl_double(md1, k1), w.r2))
+                    continue;
+                const int j = ((k3 * 64 + k2) * 64 + k1) * 64 + lane;
+                const bool cand = j < m && j != i && (j < w0 || j >= w1);
+                knn_append(w, cand, cand ? dist2_bits(pts, j, px, py, pz) : 0u);
+            }
+        }
+    }
+
+    // the mean over the kk smallest (nb >= kk: every point not in the buffer was skipped only after a cut)
+    const unsigned kth = knn_kth(w);
+    int c_less = 0;
+    double s_less = 0.;
+    for (int t = lane; t < w.nb; t += 64) {
+        const unsigned v = w.buf[t];
+        if (v < kth) {
+            c_less++;
+            s_less += (double)sqrtf(__uint_as_float(v));
+        }
+    }
+    c_less = svo::wave_sum_small(c_less);
+    const double total = wave_sum_double(s_less) + (double)(kk - c_less) * (double)sqrtf(__uint_as_float(kth));
+    if (lane == 0)
+        dist[idx[i]] = (float)(total / kk);
+}
+
+size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+}  // namespace
+
+// Device-pointer form, svo_launch_sor's contract for up to 2^22 points.  The outputs must not overlap the inputs.
+int svo_launch_sor_large(svo_ctx *ctx, const float *xyz, const float *color, int cap, int mean_k, double stddev_mul,
+                         float z_limit, float *xyz_out, float *color_out, int *d_count, float *d_mean_dist, int *d_pass)
+{
+    if (cap <= 0)
+        return SVO_OK;
+    if (cap > SVO_SOR_LARGE_MAX_N) {
+        svo_set_error("svo_sor_filter_large: at most %d points per call", SVO_SOR_LARGE_MAX_N);
+        return SVO_ERR_CAPACITY;
+    }
+    if (mean_k < 1 || mean_k > SVO_SOR_LARGE_MAX_K) {
+        svo_set_error("svo_sor_filter_large: mean_k %d outside 1..%d", mean_k, SVO_SOR_LARGE_MAX_K);
+        return SVO_ERR_ARG;
+    }
+    const size_t n = (size_t)cap;
+    const int nb1 = (cap + 63) / 64, nb2 = (nb1 + 63) / 64, nb3 = (nb2 + 63) / 64;
+    const int nblk = (cap + RS_TILE - 1) / RS_TILE;
+    // layout of the work buffer
+    size_t off = 0;
+    const size_t o_k0 = off; off = align256(off + n * 8);
+    const size_t o_k1 = off; off = align256(off + n * 8);
+    const size_t o_v0 = off; off = align256(off + n * 4);
+    const size_t o_v1 = off; off = align256(off + n * 4);
+    const size_t o_pts = off; off = align256(off + n * 12);
+    const size_t o_b1 = off; off = align256(off + (size_t)nb1 * 24);
+    const size_t o_b2 = off; off = align256(off + (size_t)nb2 * 24);
+    const size_t o_b3 = off; off = align256(off + (size_t)nb3 * 24);
+    const size_t o_hist = off; off = align256(off + (size_t)256 * nblk * 4);
+    const size_t o_bnd = off; off = align256(off + 64);
+    int rc;
+    if ((rc = ctx->sor_grid.ensure(off)) || (rc = ctx->w_a.ensure(n * 12)) || (rc = ctx->w_b.ensure(n * 12)) ||
+        (rc = ctx->w_c.ensure(n * 4)) || (rc = ctx->w_d.ensure(n + 64)) || (rc = ctx->w_e.ensure(64)))
+        return rc;
+    char *g = ctx->sor_grid.as<char>();
+    uint64_t *k0 = reinterpret_cast<uint64_t *>(g + o_k0), *k1 = reinterpret_cast<uint64_t *>(g + o_k1);
+    int *v0 = reinterpret_cast<int *>(g + o_v0), *v1 = reinterpret_cast<int *>(g + o_v1);
+    float *pts = reinterpret_cast<float *>(g + o_pts);
+    float *b1 = reinterpret_cast<float *>(g + o_b1), *b2 = reinterpret_cast<float *>(g + o_b2),
+          *b3 = reinterpret_cast<float *>(g + o_b3);
+    unsigned *hist = reinterpret_cast<unsigned *>(g + o_hist);
+    double *bnd = reinterpret_cast<double *>(g + o_bnd);
+    float *xyz_c = ctx->w_a.as<float>(), *col_c = ctx->w_b.as<float>();
+    float *dist = d_mean_dist ? d_mean_dist : ctx->w_c.as<float>();
+    uint8_t *mask = ctx->w_d.as<uint8_t>();
+    int *d_m = d_pass ? d_pass : ctx->w_e.as<int>();
+    hipStream_t st = ctx->stream;
+    const dim3 b256(256), g256((cap + 255) / 256);
+    hipLaunchKernelGGL(sorg_zmask_kernel, g256, b256, 0, st, xyz, cap, z_limit, mask);
+    if ((rc = svo_launch_compact(ctx, mask, cap, nullptr, xyz, 3, xyz_c, color, color ? 3 : 0, color ? col_c : nullptr,
+                                 nullptr, 0, nullptr, d_m)))
+        return rc;
+    hipLaunchKernelGGL(sorg_bounds_kernel, dim3(1), dim3(1024), 0, st, xyz_c, d_m, bnd);
+    hipLaunchKernelGGL(sorg_key_kernel, g256, b256, 0, st, xyz_c, d_m, bnd, cap, k0, v0);
+    if ((rc = radix_sort_pairs(st, k0, v0, k1, v1, cap, hist)))
+        return rc;
+    hipLaunchKernelGGL(sorg_gather_kernel, g256, b256, 0, st, xyz_c, v0, d_m, cap, pts);
+    hipLaunchKernelGGL(sorg_box_kernel, dim3((nb1 + 3) / 4), b256, 0, st, pts, d_m, 1, nb1, b1);
+    hipLaunchKernelGGL(sorg_box_kernel, dim3((nb2 + 3) / 4), b256, 0, st, b1, d_m, 2, nb2, b2);
+    hipLaunchKernelGGL(sorg_box_kernel, dim3((nb3 + 3) / 4), b256, 0, st, b2, d_m, 3, nb3, b3);
+    hipLaunchKernelGGL(sorg_knn_kernel, dim3((cap + KNN_WAVES - 1) / KNN_WAVES), dim3(64 * KNN_WAVES), 0, st, pts, v0,
+                       d_m, mean_k, b1, b2, b3, dist);
+    hipLaunchKernelGGL(sor_threshold_kernel, dim3(1), dim3(1024), 0, st, dist, d_m, stddev_mul, cap, mask);
+    if ((rc = svo_launch_compact(ctx, mask, cap, d_m, xyz_c, 3, xyz_out, color ? col_c : nullptr, color ? 3 : 0,
+                                 color ? color_out : nullptr, nullptr, 0, nullptr, d_count)))
+        return rc;
+    SVO_HIP(hipGetLastError());
+    return SVO_OK;
+}
+
+extern "C" int svo_sor_filter_large(svo_ctx *ctx, const float *xyz, const float *color, int n, int mean_k,
+                                    double stddev_mul, float z_limit, float *xyz_out, float *color_out, int *n_out,
+                                    float *mean_dist_out, int *n_pass_out, int mem)
+{
+    SVO_CHECK_ARG(ctx && n >= 0 && mean_k > 0 && mean_k <= SVO_SOR_LARGE_MAX_K && n_out);
+    SVO_CHECK_ARG(mem == SVO_MEM_HOST || mem == SVO_MEM_DEVICE);
+    *n_out = 0;
+    if (n_pass_out)
+        *n_pass_out = 0;
+    if (n > SVO_SOR_LARGE_MAX_N) {
+        svo_set_error("svo_sor_filter_large: %d points, at most %d per call", n, SVO_SOR_LARGE_MAX_N);
+        return SVO_ERR_CAPACITY;
+    }
+    if (n == 0)
+        return SVO_OK;
+    SVO_CHECK_ARG(xyz && xyz_out && (!color || color_out));
+    int rc;
+    if ((rc = ctx->s_g.ensure(64)))
+        return rc;
+    int *d_cnt = ctx->s_g.as<int>();  // [0] kept, [1] passed the pre-filter
+    const float *dx = xyz, *dc = color;
+    float *ox = xyz_out, *oc = color_out, *od = mean_dist_out;
+    if (mem == SVO_MEM_HOST) {
+        if ((rc = ctx->s_a.ensure((size_t)n * 12)) || (rc = ctx->s_b.ensure((size_t)n * 12)) ||
+            (rc = ctx->s_c.ensure((size_t)n * 12)) || (rc = ctx->s_d.ensure((size_t)n * 12)) ||
+            (rc = ctx->s_e.ensure((size_t)n * 4)))
+            return rc;
+        SVO_HIP(hipMemcpyAsync(ctx->s_a.p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream));
+        if (color)
+            SVO_HIP(hipMemcpyAsync(ctx->s_b.p, color, (size_t)n * 12, hipMemcpyHostToDevice, ctx->stream));
+        dx = ctx->s_a.as<float>();
+        dc = color ? ctx->s_b.as<float>() : nullptr;
+        ox = ctx->s_c.as<float>();
+        oc = ctx->s_d.as<float>();
+        od = ctx->s_e.as<float>();
+    }
+    if ((rc = svo_launch_sor_large(ctx, dx, dc, n, mean_k, stddev_mul, z_limit, ox, oc, d_cnt, od, d_cnt + 1)))
+        return rc;
+    SVO_HIP(hipMemcpyAsync(ctx->pinned, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream));
+    SVO_HIP(hipStreamSynchronize(ctx->stream));
+    const int kept = reinterpret_cast<int *>(ctx->pinned)[0], passed = reinterpret_cast<int *>(ctx->pinned)[1];
+    *n_out = kept;
+    if (n_pass_out)
+        *n_pass_out = passed;
+    if (mem == SVO_MEM_HOST) {
+        if (kept > 0) {
+            SVO_HIP(hipMemcpyAsync(xyz_out, ox, (size_t)kept * 12, hipMemcpyDeviceToHost, ctx->stream));
+            if (color)
+                SVO_HIP(hipMemcpyAsync(color_out, oc, (size_t)kept * 12, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        if (mean_dist_out && passed > 0)
+            SVO_HIP(hipMemcpyAsync(mean_dist_out, od, (size_t)passed * 4, hipMemcpyDeviceToHost, ctx->stream));
+        SVO_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return SVO_OK;
+}

@@ -130,6 +130,8 @@ struct svo_ctx {
     hipEvent_t up_ev[3] = {nullptr, nullptr, nullptr}, use_ev[3] = {nullptr, nullptr, nullptr};
     // sgbm.hip: the dense matcher's cost volume and path planes, its per-pixel work arrays, the reprojection's staging
     DevBuf sgbm_cost, sgbm_misc, sgbm_rp;
+    // sor_grid.hip: the large-cloud outlier removal's keys, sorted points, boxes and radix histograms
+    DevBuf sor_grid;
 };
 
 // Low-latency host wait for everything queued on the context's stream: records an event and
@@ -302,6 +304,9 @@ void svo_orb_default_pattern(int8_t *pat);
 // sor.hip
 int svo_launch_sor(svo_ctx *ctx, const float *xyz, const float *color, int cap, int mean_k, double stddev_mul,
                    float z_limit, float *xyz_out, float *color_out, int *d_count, float *d_mean_dist, int *d_pass);
+// sor_grid.hip: the same contract for up to 2^22 points (Morton sort + box hierarchy kNN); mean_k 1..256
+int svo_launch_sor_large(svo_ctx *ctx, const float *xyz, const float *color, int cap, int mean_k, double stddev_mul,
+                         float z_limit, float *xyz_out, float *color_out, int *d_count, float *d_mean_dist, int *d_pass);
 // pnp.hip
 struct svo_pnp_job {  // host-side description of one PnP-RANSAC problem (device pointers)
     const float *obj, *img;
