@@ -214,6 +214,42 @@ int svo_stereo_reproject(svo_ctx *ctx, const int16_t *disp, const uint8_t *image
                          const double *Q16, float disp_scale, float z_min, float z_max, int flip_y,
                          float *xyz_out, float *bgr_out, int *n_out, int mem);
 
+/* ---- two-view monocular geometry: StereoProcess::monocularTriangulate, src/StereoCV.cpp:123-188 ---- */
+/* OpenCV 3.2's five-point solver (EMEstimatorCallback::runKernel, Nister's method) on nsamples
+ * independent 5-samples of NORMALISED double coordinates: x1n / x2n nsamples x 5 x 2, x2^T E x1 = 0.
+ * E_out: nsamples x 10 x 9 (row-major 3x3 each, unit Frobenius norm, the entry of largest magnitude
+ * positive, in ascending order of the solver's z root; unused slots zero); nsol: nsamples ints
+ * (0..10).  Arrays follow `mem`.  The solver's choices: DESIGN.md section 10b.                 */
+int svo_essential_5pt(svo_ctx *ctx, const double *x1n, const double *x2n, int nsamples, double *E_out, int *nsol,
+                      int mem);
+/* cv::findEssentialMat(p1, p2, K, RANSAC, confidence, threshold, mask) for nprob (1..16) problems:
+ * problem k is pairs offsets[k] .. offsets[k+1]-1 of p1 / p2 (float x, y pixels) with
+ * K4[4k .. 4k+3] = fx, fy, cx, cy.  offsets (nprob + 1 ints) and K4 are HOST memory always.  Points
+ * are normalised by K in double; the Sampson error (float) is tested against
+ * (threshold / ((fx + fy) / 2))^2; 5-samples are drawn like svo_pnp_ransac's, keyed by (seed,
+ * iteration); first-best-wins with the adaptive bound, max_iters 1..20000 (OpenCV: 1000).  Below five
+ * pairs: no model; exactly five: every solution of the solver, mask all ones, iters_run 0.  mask:
+ * a byte per pair (1 = inlier).  Per problem (optional, following `mem`): E_out 10 x 9 doubles (the
+ * winning model in slot 0; with five pairs, every solution), nmodels, inlier_count, iters_run.  A
+ * batch gives the same bits as its problems one call at a time.                                    */
+int svo_find_essential(svo_ctx *ctx, const float *p1, const float *p2, const int *offsets, int nprob, const double *K4,
+                       double threshold, double confidence, int max_iters, uint64_t seed, uint8_t *mask,
+                       double *E_out, int *nmodels, int *inlier_count, int *iters_run, int mem);
+/* cv::recoverPose(E, p1, p2, K, R, t, distance_thresh, mask) for nprob (1..16) problems laid out as
+ * svo_find_essential's; E9: nprob x 9.  The four decompositions of E are tested by triangulating
+ * every pair (DLT, normalised coordinates, double): a pair counts when Q2 Q3 > 0, its depth in
+ * camera 1 is below distance_thresh (OpenCV: 50) and its depth in camera 2 is in (0, distance_thresh);
+ * a non-null mask_inout is ANDed in and receives the chosen candidate's mask.  The first candidate
+ * with the largest count wins (OpenCV's order).  R9 (nprob x 9), t3 (nprob x 3, unit norm), good
+ * (optional, nprob ints) follow `mem` like the point arrays; offsets / K4 are host memory.         */
+int svo_recover_pose(svo_ctx *ctx, const double *E9, const float *p1, const float *p2, const int *offsets, int nprob,
+                     const double *K4, double distance_thresh, uint8_t *mask_inout, double *R9, double *t3, int *good,
+                     int mem);
+/* cv::decomposeEssentialMat: R1 = U W V^T, R2 = U W^T V^T, t = u3 (W = [[0,1,0],[-1,0,0],[0,0,1]]).
+ * The SVD's signs are fixed so that each of the first two right singular vectors has its entry of
+ * largest magnitude positive, and u3 = u1 x u2, v3 = v1 x v2 (det +1).  Host only.                 */
+int svo_decompose_essential(const double *E9, double *R1, double *R2, double *t);
+
 /* ---- loop-closure detection: features ---------------------------------------------------------- */
 /* cv::ORB::create()->detectAndCompute(img, Mat(), kp, desc) of visualSLAM::checkLoopDetectorStatus,
  * src/optimizationStuff.cpp:49-56.  image: h x w x c (BGR or grey).  Up to n_features (500

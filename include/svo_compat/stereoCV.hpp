@@ -1,8 +1,9 @@
 // svo_compat/stereoCV.hpp -- the reference's StereoProcess (include/stereoCV.h:32-73): stereoTriangulate(im1, im2,
 // out3d) on the hot path's sparse stereo, and the dense SGBM demo of src/StereoCV.cpp -- stereoMatch(iter) and
 // reprojectDisparity(disp, pts, colours) -- on svo_sgbm_compute / svo_stereo_reproject -- and pclPublish(pts, colours)
-// on svo_sor_filter_large, the filtered cloud left in publishedCloud / publishedColors instead of a ROS message.
-// visualizeCloud and mainLoop are not provided.
+// on svo_sor_filter_large, the filtered cloud left in publishedCloud / publishedColors instead of a ROS message --
+// and monocularTriangulate(im1, im2, out3d) on svo_find_essential / svo_recover_pose / svo_triangulate.  getImg is
+// public here, a thin wrapper over the frame loader.  visualizeCloud and mainLoop are not provided.
 #pragma once
 
 #include <cstdint>
@@ -133,7 +134,57 @@ class StereoProcess {
         color3dMap = slam_.colors;
     }
 
+    // include/stereoCV.h:66, src/StereoCV.cpp:123-188: two-view monocular reconstruction.  The reference matches SIFT
+    // features with a ratio test here; this adaptor uses the hot path's dense grid + LK instead, as stereoTriangulate
+    // does: denseKeypointExtractor / denseLKtracking(im1 -> im2) / FmatThresholding (3 px, 0.99), then
+    // svo_find_essential (1 px, 0.99) and svo_recover_pose on the F-inliers, and svo_triangulate of ALL F-inliers (as
+    // upstream: inlier1 / inlier2, not the E inliers) with P1 = K[I|0], P2 = K[R|t] -- float points, t of unit norm.
+    // The pose lands in monoR / monoT, the F-inliers in monoPts1 / monoPts2.
+    double monoR[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, monoT[3] = {0, 0, 0};
+    std::vector<Point2f> monoPts1, monoPts2;
+    void monocularTriangulate(const Mat &im1, const Mat &im2, std::vector<Point3f> &out3d)
+    {
+        std::vector<KeyPoint> dkps = slam_.denseKeypointExtractor(im1, slam_.gridStep);
+        std::vector<Point2f> pt1, pt2;
+        for (const KeyPoint &k : dkps)
+            pt1.emplace_back(k.pt);
+        slam_.denseLKtracking(im1, im2, pt1, pt2);
+        slam_.FmatThresholding(pt1, pt2);
+        monoPts1 = pt1;
+        monoPts2 = pt2;
+        const int n = (int)pt1.size();
+        const int offsets[2] = {0, n};
+        const double K4[4] = {focal_x, focal_y, cx, cy};
+        std::vector<uint8_t> mask(n > 0 ? n : 1);
+        double E[90];
+        int nmodels = 0;
+        check(svo_find_essential(ctx(), fp(pt1), fp(pt2), offsets, 1, K4, 1.0, 0.99, 1000, slam_.ransacSeed + 4, mask.data(),
+                                 E, &nmodels, nullptr, nullptr, SVO_MEM_HOST));
+        if (nmodels < 1)
+            throw std::runtime_error("monocularTriangulate: no essential matrix");
+        int good = 0;
+        check(svo_recover_pose(ctx(), E, fp(pt1), fp(pt2), offsets, 1, K4, 50.0, nullptr, monoR, monoT, &good, SVO_MEM_HOST));
+        const double K[9] = {focal_x, 0, cx, 0, focal_y, cy, 0, 0, 1};
+        double P1[12], P2[12];
+        for (int r = 0; r < 3; r++)
+            for (int c = 0; c < 4; c++) {
+                P1[4 * r + c] = c < 3 ? K[3 * r + c] : 0.;
+                double s = 0;
+                for (int k = 0; k < 3; k++)
+                    s += K[3 * r + k] * (c < 3 ? monoR[3 * k + c] : monoT[k]);
+                P2[4 * r + c] = s;
+            }
+        out3d.assign(n, Point3f());
+        if (n > 0)
+            check(svo_triangulate(ctx(), P1, P2, fp(pt1), fp(pt2), n, reinterpret_cast<float *>(out3d.data()), nullptr,
+                                  SVO_MEM_HOST));
+    }
+
+    // include/stereoCV.h:60 (private upstream): a frame as stereoMatch loads it, B,G,R; empty when it is missing
+    Mat getImg(const char *pattern, int iter) { return load_bgr(pattern, iter); }
+
   private:
+    static const float *fp(const std::vector<Point2f> &v) { return reinterpret_cast<const float *>(v.data()); }
 #if defined(SVO_WITH_OPENCV) && defined(CV_16SC1)
     static constexpr int kDisp16S = CV_16SC1;
 #else

@@ -555,6 +555,107 @@ def sor_filter_large(self, xyz, color=None, mean_k=20, stddev_mul=0.8, z_limit=0
     return xo[:k].copy(), (co[:k].copy() if co is not None else None), md[:p].copy()
 
 
+# ---- two-view geometry: findEssentialMat / recoverPose (StereoProcess::monocularTriangulate) ----------------------
+def _problem_set(p1, p2, K):
+    """one problem (p1, p2: n x 2 arrays or device tensors, K: 4 numbers) or lists of them -> (p1 and p2 back to back,
+    host offsets, host K4, single, device)"""
+    single = not isinstance(p1, (list, tuple))
+    p1s, p2s = ([p1], [p2]) if single else (list(p1), list(p2))
+    assert len(p1s) == len(p2s) and 1 <= len(p1s) <= 16, "1 to 16 problems per call"
+    Ks = [K] * len(p1s) if np.asarray(K, np.float64).size == 4 else list(K)
+    assert len(Ks) == len(p1s)
+    K4 = np.ascontiguousarray(np.concatenate([np.asarray(k, np.float64).reshape(4) for k in Ks]))
+    dev = _is_device(p1s[0])
+    sizes = [int(np.prod(a.shape)) // 2 for a in p1s]
+    assert sizes == [int(np.prod(a.shape)) // 2 for a in p2s], "p1 and p2 must pair up"
+    offsets = np.ascontiguousarray(np.concatenate([[0], np.cumsum(sizes)]), np.int32)
+    if dev:
+        import torch
+
+        assert all(_is_device(a) for a in p1s + p2s), "all point arrays must live in the same memory"
+        a = torch.cat([x.reshape(-1, 2).to(torch.float32) for x in p1s]).contiguous()
+        b = torch.cat([x.reshape(-1, 2).to(torch.float32) for x in p2s]).contiguous()
+    else:
+        a = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 2) for x in p1s]))
+        b = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).reshape(-1, 2) for x in p2s]))
+    return a, b, offsets, K4, single, dev
+
+
+@_ctx_method
+def essential_5pt(self, x1n, x2n):
+    """``svo_essential_5pt``: the five-point solver on s samples of normalised coordinates (s x 5 x 2 each) ->
+    (E: s x 10 x 3 x 3, the first nsol[k] valid; nsol: s ints)."""
+    x1 = np.ascontiguousarray(x1n, np.float64).reshape(-1, 5, 2)
+    x2 = np.ascontiguousarray(x2n, np.float64).reshape(-1, 5, 2)
+    assert x1.shape == x2.shape
+    s = x1.shape[0]
+    E = np.zeros((s, 10, 3, 3))
+    nsol = np.zeros(s, np.int32)
+    _check(self.lib.svo_essential_5pt(self._h, _ptr(x1), _ptr(x2), s, _ptr(E), _ptr(nsol), MEM_HOST))
+    return E, nsol
+
+
+@_ctx_method
+def find_essential(self, p1, p2, K, threshold=1.0, confidence=0.99, max_iters=1000, seed=0):
+    """``svo_find_essential`` (cv::findEssentialMat, RANSAC): one problem -- p1, p2 (n x 2 pixels), K = (fx, fy, cx, cy)
+    -- or lists of up to 16 problems (K one for all or one per problem).  numpy arrays, or device tensors whose masks
+    come back as device tensors.  Per problem -> (E: m x 3 x 3, mask: n uint8, inlier count, iterations run)."""
+    a, b, offsets, K4, single, dev = _problem_set(p1, p2, K)
+    nprob, total = len(offsets) - 1, int(offsets[-1])
+    args = (C.c_double(threshold), C.c_double(confidence), int(max_iters), C.c_uint64(seed))
+    if dev:
+        import torch
+
+        mask = torch.empty(max(total, 1), dtype=torch.uint8, device=a.device)
+        E = torch.zeros((nprob, 10, 9), dtype=torch.float64, device=a.device)
+        ints = torch.zeros((3, nprob), dtype=torch.int32, device=a.device)
+        torch.cuda.synchronize(a.device)
+        _check(self.lib.svo_find_essential(self._h, _ptr(a), _ptr(b), _ptr(offsets), nprob, _ptr(K4), *args, _ptr(mask),
+                                           _ptr(E), _ptr(ints[0]), _ptr(ints[1]), _ptr(ints[2]), MEM_DEVICE))
+        _check(self.lib.svo_ctx_sync(self._h))
+        E, ints = E.cpu().numpy(), ints.cpu().numpy()
+    else:
+        mask = np.zeros(max(total, 1), np.uint8)
+        E = np.zeros((nprob, 10, 9))
+        ints = np.zeros((3, nprob), np.int32)
+        _check(self.lib.svo_find_essential(self._h, _ptr(a), _ptr(b), _ptr(offsets), nprob, _ptr(K4), *args, _ptr(mask),
+                                           _ptr(E), _ptr(ints[0]), _ptr(ints[1]), _ptr(ints[2]), MEM_HOST))
+    out = [(E[k, :ints[0, k]].reshape(-1, 3, 3), mask[offsets[k]:offsets[k + 1]], int(ints[1, k]), int(ints[2, k]))
+           for k in range(nprob)]
+    return out[0] if single else out
+
+
+@_ctx_method
+def recover_pose(self, E, p1, p2, K, distance_thresh=50.0, mask=None):
+    """``svo_recover_pose`` (cv::recoverPose): one problem -- E (3 x 3), p1, p2 (n x 2 pixels), K = (fx, fy, cx, cy),
+    mask (n, optional: ANDed in) -- or lists of up to 16.  Host arrays -> per problem (R, t (3,), good count, the chosen
+    candidate's mask)."""
+    a, b, offsets, K4, single, dev = _problem_set(p1, p2, K)
+    assert not dev, "recover_pose takes host arrays"
+    nprob, total = len(offsets) - 1, int(offsets[-1])
+    Es = [E] if single else list(E)
+    assert len(Es) == nprob
+    E9 = np.ascontiguousarray(np.concatenate([np.asarray(e, np.float64).reshape(9) for e in Es]))
+    masks = [mask] if single else (list(mask) if mask is not None else [None] * nprob)
+    m = np.ones(max(total, 1), np.uint8)
+    for k, mk in enumerate(masks):
+        if mk is not None:
+            m[offsets[k]:offsets[k + 1]] = np.asarray(mk, np.uint8).reshape(-1)
+    R, t, good = np.zeros((nprob, 3, 3)), np.zeros((nprob, 3)), np.zeros(nprob, np.int32)
+    _check(self.lib.svo_recover_pose(self._h, _ptr(E9), _ptr(a), _ptr(b), _ptr(offsets), nprob, _ptr(K4),
+                                     C.c_double(distance_thresh), _ptr(m), _ptr(R), _ptr(t), _ptr(good), MEM_HOST))
+    out = [(R[k], t[k], int(good[k]), m[offsets[k]:offsets[k + 1]].copy()) for k in range(nprob)]
+    return out[0] if single else out
+
+
+def decompose_essential(E):
+    """``svo_decompose_essential`` (cv::decomposeEssentialMat, host) -> (R1, R2, t)."""
+    e = np.ascontiguousarray(E, np.float64).reshape(9)
+    R1, R2, t = np.zeros((3, 3)), np.zeros((3, 3)), np.zeros(3)
+    _check(load().svo_decompose_essential(_ptr(e), _ptr(R1), _ptr(R2), _ptr(t)))
+    return R1, R2, t
+
+
 @_ctx_method
 def pnp_ransac(self, obj, img, K4, iterations=100, reproj_err=1.0, confidence=0.99, seed=0):
     obj = np.ascontiguousarray(obj, np.float32).reshape(-1, 3)

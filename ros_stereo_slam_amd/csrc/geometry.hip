@@ -11,72 +11,16 @@
 // All are one thread per point, bandwidth-trivial (tens of bytes per point).
 #include <cfloat>
 
+#include "dlt.hip.h"
 #include "svo_internal.h"
+
+using svo::smallest_right_singular_vector4;
 
 namespace {
 
 struct Mat34 {
     double m[12];
 };
-
-// right singular vector of the smallest singular value of a 4x4 matrix (Hestenes Jacobi)
-__device__ void smallest_right_singular_vector4(double (&A)[4][4], double (&v)[4])
-{
-    double V[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-            V[i][j] = i == j ? 1. : 0.;
-    for (int sweep = 0; sweep < 30; sweep++) {
-        bool rotated = false;
-#pragma unroll
-        for (int p = 0; p < 3; p++)
-#pragma unroll
-            for (int q = p + 1; q < 4; q++) {
-                double al = 0, be = 0, ga = 0;
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    al += A[i][p] * A[i][p];
-                    be += A[i][q] * A[i][q];
-                    ga += A[i][p] * A[i][q];
-                }
-                if (fabs(ga) <= DBL_EPSILON * sqrt(al * be) || ga == 0)
-                    continue;
-                rotated = true;
-                const double zeta = (be - al) / (2. * ga);
-                const double t = (zeta >= 0 ? 1. : -1.) / (fabs(zeta) + sqrt(1. + zeta * zeta));
-                const double c = 1. / sqrt(1. + t * t), s = c * t;
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const double ap = A[i][p], aq = A[i][q];
-                    A[i][p] = c * ap - s * aq;
-                    A[i][q] = s * ap + c * aq;
-                    const double vp = V[i][p], vq = V[i][q];
-                    V[i][p] = c * vp - s * vq;
-                    V[i][q] = s * vp + c * vq;
-                }
-            }
-        if (!rotated)
-            break;
-    }
-    int best = 0;
-    double bn = DBL_MAX;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        double nn = 0;
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-            nn += A[i][j] * A[i][j];
-        if (nn < bn) {
-            bn = nn;
-            best = j;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-        v[i] = best == 0 ? V[i][0] : best == 1 ? V[i][1] : best == 2 ? V[i][2] : V[i][3];
-}
 
 struct TriJob {
     const float2 *x1, *x2;

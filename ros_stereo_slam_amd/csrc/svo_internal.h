@@ -132,6 +132,8 @@ struct svo_ctx {
     DevBuf sgbm_cost, sgbm_misc, sgbm_rp;
     // sor_grid.hip: the large-cloud outlier removal's keys, sorted points, boxes and radix histograms
     DevBuf sor_grid;
+    // essential.hip: normalised points, the RANSAC's per-iteration models / counts / state, recoverPose's candidate masks
+    DevBuf ess;
 };
 
 // Low-latency host wait for everything queued on the context's stream: records an event and
