@@ -47,6 +47,7 @@ struct LkParams {
     int doff[SVO_MAX_LEVELS];    // derivative levels of the jobs' first pyramids: element (0,0), in ints
     int dpitch[SVO_MAX_LEVELS];  // bytes, multiple of 16
     int interleave;              // 1: keypoint = workgroup index (a lone launch: balance before L2 locality), 0: XCD bands
+    int lattice;                 // 0: every level interpolates its patches, integer positions too (SVO_LK_LATTICE=0, for A/B and tests)
 };
 static_assert(sizeof(LkBatch) + sizeof(LkParams) <= 4096, "kernel arguments are limited to 4 KB");
 
@@ -573,34 +574,54 @@ __global__ __launch_bounds__(64 * WAVES, 4) void lk_track_kernel(LkBatchN<NJ> ba
             }
             continue;
         }
-        int w00, w01, w10, w11;
-        bilinear_weights(px - (float)ipx, py - (float)ipy, w00, w01, w10, w11);
-
         // ---- 1. previous-image tile -> template patch; derivative tile -> derivative patches, normal matrix ----
         // Both tiles' loads are issued at once: T is written to LDS as soon as it has arrived, the eight vectors
         // of D stay in flight (in registers) while the template patch is formed from T, and take T's place after.
-        wave_lds_sync();
-        TileLoad<C, PT> tload;
-        tile_issue<C, PT>(tload, I, pitch, ipx - 1, ipy - 1, lane);
-        DtileLoad<C> dload;
-        dtile_issue<C>(dload, dprev + prm.doff[level], prm.dpitch[level], ipx, ipy, lane);
-        tile_commit<C, PT, DtileLoad<C>::N>(tload, T, lane);
-        const uint8_t *Ts = T + tload.shift;
-        wave_lds_sync();
-
+        //
+        // A window that starts on an integer position (both fractions exactly 0: the lattice points of a keyframe at
+        // the levels whose scale divides the grid step) has the weights (2^14, 0, 0, 0), and the interpolation is the
+        // identity:  (2^14 p + 2^8) >> 9 == 32 p  and  (2^14 4d + 4 2^13) >> 16 == d.  Such a level unpacks what it
+        // staged instead of interpolating it (IDENT): the same patches bit for bit, a quarter of the instructions.
+        // The choice is the kernel's own, from the fractions, valid for any point; it is made BEFORE the loads are
+        // issued, so that no branch falls inside the window in which the loads are in flight.
+        const float fa = px - (float)ipx, fb = py - (float)ipy;
         int Ivp[npairs(C)], Ixp[npairs(C)], Iyp[npairs(C)];  // packed int16 pairs (low = even element)
-        int a11 = 0, a12 = 0, a22 = 0;
-        {
-            // the spare lane (63) interpolates its derivative patch with zero weights: Ix = Iy = 0 there, so
-            // its share of every sum below and in the iterations is 0 without any masking
-            const int wq0 = active ? (w00 & 0xffff) | (w10 << 16) : 0, wq1 = active ? (w01 & 0xffff) | (w11 << 16) : 0;
+        auto patches = [&](auto ident_c) {
+            constexpr bool IDENT = decltype(ident_c)::value;
             constexpr int NE = SEG * C, NV = (SEG + 1) * C;
-            {
+            int wv0 = 0, wv1 = 0;  // (w00 | w10 << 16), (w01 | w11 << 16)
+            if constexpr (!IDENT) {
+                int w00, w01, w10, w11;
+                bilinear_weights(fa, fb, w00, w01, w10, w11);
+                wv0 = (w00 & 0xffff) | (w10 << 16);
+                wv1 = (w01 & 0xffff) | (w11 << 16);
+            }
+            wave_lds_sync();
+            TileLoad<C, PT> tload;
+            tile_issue<C, PT>(tload, I, pitch, ipx - 1, ipy - 1, lane);
+            DtileLoad<C> dload;
+            dtile_issue<C>(dload, dprev + prm.doff[level], prm.dpitch[level], ipx, ipy, lane);
+            tile_commit<C, PT, DtileLoad<C>::N>(tload, T, lane);
+            const uint8_t *Ts = T + tload.shift;
+            wave_lds_sync();
+
+            const int toff = (int)(Ts - lds) + (wy + 1) * TROW + (wx + 1) * C;
+            if constexpr (IDENT) {
+                // element k is byte k of the lane's row run, times 32: one permute spreads two bytes over the
+                // halves of a dword, one shift scales both (32 * 255 stays inside its half)
+                unsigned t0[ndwords(C)];
+                load_row_packed<C>(lds, toff, t0);
+                ForEachElem<C, npairs(C)>::run([&](auto jc) {
+                    constexpr int j = decltype(jc)::value, k0 = 2 * j, k1 = 2 * j + 1;
+                    constexpr unsigned hi = k1 < NE ? 4u + (unsigned)(k1 & 3) : 0x0cu;
+                    constexpr unsigned sel = (unsigned)(k0 & 3) | (0x0cu << 8) | (hi << 16) | (0x0cu << 24);
+                    Ivp[j] = (int)(__builtin_amdgcn_perm(t0[(k1 < NE ? k1 : k0) >> 2], t0[k0 >> 2], sel) << 5);
+                });
+            } else {
                 unsigned t0[ndwords(C)], t1[ndwords(C)];
-                const int toff = (int)(Ts - lds) + (wy + 1) * TROW + (wx + 1) * C;
                 load_row_packed<C>(lds, toff, t0);
                 load_row_packed<C>(lds, toff + TROW, t1);
-                lane_samples<C, W_BITS - 5>(t0, t1, (w00 & 0xffff) | (w10 << 16), (w01 & 0xffff) | (w11 << 16), Ivp);
+                lane_samples<C, W_BITS - 5>(t0, t1, wv0, wv1, Ivp);
             }
             // the Scharr derivatives of the window's 22x22 neighbourhood come from the derivative level
             // (zero outside the image: the level's border is zero); the tile takes the place of T.
@@ -619,52 +640,88 @@ __global__ __launch_bounds__(64 * WAVES, 4) void lk_track_kernel(LkBatchN<NJ> ba
             wave_lds_sync();
             constexpr int DROW = DTile<C>::ROW / 4;
             int dlane = wy * DROW + wx * C;  // this lane's first tile entry
-            // Derivative tile entries are (4 dx | 4 dy << 16) (pyramid.hip; |4 d| <= 16320: int16).  As for the
-            // image samples, the VERTICAL neighbours of column k are paired once (element k uses columns k and
-            // k + C): 2 permutes per column instead of 4 per element.  With the factor 4 the descale by 2^14 is
-            // "take the high half" -- the permute that packs two elements does it, no shift:
-            //   (4 (sum w d) + 4 RD) >> 16  ==  (sum w d + RD) >> 14.
-            constexpr int RD4 = 4 << (W_BITS - 1);
-            // x then y, each from its own read of the tile rows: half the registers in flight
-            {
-                const int *d0 = D + dlane, *d1 = d0 + DROW;
-                int vx[NV], sx[NE + 1];
-                ForEachElem<C, NV>::run([&](auto kc) {
-                    constexpr int k = decltype(kc)::value;
-                    vx[k] = half_pair<false>(d0[k], d1[k]);
-                });
-                sx[NE] = 0;
+            // Derivative tile entries are (4 dx | 4 dy << 16) (pyramid.hip; |4 d| <= 16320: int16).
+            if constexpr (IDENT) {
+                // element k is entry k of the lane's row run: the low (x) / high (y) halves of two entries packed by
+                // one permute, the factor 4 dropped by one packed arithmetic shift.  The spare lane (63) selects
+                // zero bytes: Ix = Iy = 0 there, as its zero weights give in the interpolating path.
+                const int *d0 = D + dlane;
+                int e[NE + 1];
 #pragma unroll
                 for (int k = 0; k < NE; k++)
-                    sx[k] = sdot2(vx[k + C], wq1, sdot2_sconst(vx[k], wq0, RD4));
+                    e[k] = d0[k];
+                e[NE] = 0;
+                // (The selectors do not depend on the level.  Left to itself the compiler forms them once, before
+                // the level loop, and keeps them and their constants in registers across the iteration loop, which
+                // has none to spare: so from an opaque copy of the lane, the constants as literals of the VOP2 forms.)
+                int sl = lane;
+                asm volatile("" : "+v"(sl));
+                const int spare = sl < 3 * WIN ? 0 : -1;
+                unsigned selx, sely;  // 0x05040100 / 0x07060302: the low / high halves of two dwords; 0x0c: a zero byte
+                asm("v_and_b32 %0, 0x09080d0c, %1\n\tv_xor_b32 %0, 0x05040100, %0" : "=v"(selx) : "v"(spare));
+                asm("v_and_b32 %0, 0x0b0a0f0e, %1\n\tv_xor_b32 %0, 0x07060302, %0" : "=v"(sely) : "v"(spare));
+                const short2v two = {2, 2};
 #pragma unroll
-                for (int j = 0; j < npairs(C); j++)
-                    Ixp[j] = half_pair<true>(sx[2 * j], sx[2 * j + 1 < NE ? 2 * j + 1 : NE]);
+                for (int j = 0; j < npairs(C); j++) {
+                    const unsigned lo = (unsigned)e[2 * j], hi = (unsigned)e[2 * j + 1 < NE ? 2 * j + 1 : NE];
+                    Ixp[j] = __builtin_bit_cast(int, (short2v)(__builtin_bit_cast(short2v, __builtin_amdgcn_perm(hi, lo, selx)) >> two));
+                    Iyp[j] = __builtin_bit_cast(int, (short2v)(__builtin_bit_cast(short2v, __builtin_amdgcn_perm(hi, lo, sely)) >> two));
+                }
+            } else {
+                // As for the image samples, the VERTICAL neighbours of column k are paired once (element k uses
+                // columns k and k + C): 2 permutes per column instead of 4 per element.  With the factor 4 the
+                // descale by 2^14 is "take the high half" -- the permute that packs two elements does it, no shift:
+                //   (4 (sum w d) + 4 RD) >> 16  ==  (sum w d + RD) >> 14.
+                constexpr int RD4 = 4 << (W_BITS - 1);
+                // the spare lane (63) interpolates its derivative patch with zero weights: Ix = Iy = 0 there, so
+                // its share of every sum below and in the iterations is 0 without any masking
+                const int wq0 = active ? wv0 : 0, wq1 = active ? wv1 : 0;
+                // x then y, each from its own read of the tile rows: half the registers in flight
+                {
+                    const int *d0 = D + dlane, *d1 = d0 + DROW;
+                    int vx[NV], sx[NE + 1];
+                    ForEachElem<C, NV>::run([&](auto kc) {
+                        constexpr int k = decltype(kc)::value;
+                        vx[k] = half_pair<false>(d0[k], d1[k]);
+                    });
+                    sx[NE] = 0;
+#pragma unroll
+                    for (int k = 0; k < NE; k++)
+                        sx[k] = sdot2(vx[k + C], wq1, sdot2_sconst(vx[k], wq0, RD4));
+#pragma unroll
+                    for (int j = 0; j < npairs(C); j++)
+                        Ixp[j] = half_pair<true>(sx[2 * j], sx[2 * j + 1 < NE ? 2 * j + 1 : NE]);
+                }
+                // the y pass starts when the x pass is done (left alone the compiler merges the two and needs 106
+                // registers; at most 104 keep a fifth wave slot's worth of every SIMD free for the short kernels)
+                asm volatile("" : "+v"(dlane), "+v"(Ixp[npairs(C) - 1]));
+                {
+                    const int *d0 = D + dlane, *d1 = d0 + DROW;
+                    int vy[NV], sy[NE + 1];
+                    ForEachElem<C, NV>::run([&](auto kc) {
+                        constexpr int k = decltype(kc)::value;
+                        vy[k] = half_pair<true>(d0[k], d1[k]);
+                    });
+                    sy[NE] = 0;
+#pragma unroll
+                    for (int k = 0; k < NE; k++)
+                        sy[k] = sdot2(vy[k + C], wq1, sdot2_sconst(vy[k], wq0, RD4));
+#pragma unroll
+                    for (int j = 0; j < npairs(C); j++)
+                        Iyp[j] = half_pair<true>(sy[2 * j], sy[2 * j + 1 < NE ? 2 * j + 1 : NE]);
+                }
             }
-            // the y pass starts when the x pass is done (left alone the compiler merges the two and needs 106
-            // registers; at most 104 keep a fifth wave slot's worth of every SIMD free for the short kernels)
-            asm volatile("" : "+v"(dlane), "+v"(Ixp[npairs(C) - 1]));
-            {
-                const int *d0 = D + dlane, *d1 = d0 + DROW;
-                int vy[NV], sy[NE + 1];
-                ForEachElem<C, NV>::run([&](auto kc) {
-                    constexpr int k = decltype(kc)::value;
-                    vy[k] = half_pair<true>(d0[k], d1[k]);
-                });
-                sy[NE] = 0;
+        };
+        if (prm.lattice && uniform(fa == 0.f && fb == 0.f))
+            patches(std::true_type());
+        else
+            patches(std::false_type());
+        int a11 = 0, a12 = 0, a22 = 0;
 #pragma unroll
-                for (int k = 0; k < NE; k++)
-                    sy[k] = sdot2(vy[k + C], wq1, sdot2_sconst(vy[k], wq0, RD4));
-#pragma unroll
-                for (int j = 0; j < npairs(C); j++)
-                    Iyp[j] = half_pair<true>(sy[2 * j], sy[2 * j + 1 < NE ? 2 * j + 1 : NE]);
-            }
-#pragma unroll
-            for (int j = 0; j < npairs(C); j++) {
-                a11 = sdot2(Ixp[j], Ixp[j], a11);  // sums of squares of int16 pairs, exact
-                a12 = sdot2(Ixp[j], Iyp[j], a12);
-                a22 = sdot2(Iyp[j], Iyp[j], a22);
-            }
+        for (int j = 0; j < npairs(C); j++) {
+            a11 = sdot2(Ixp[j], Ixp[j], a11);  // sums of squares of int16 pairs, exact
+            a12 = sdot2(Ixp[j], Iyp[j], a12);
+            a22 = sdot2(Iyp[j], Iyp[j], a22);
         }
         int neg_c1 = 0, neg_c2 = 0;  // - sum I * Ix, - sum I * Iy of this lane (see lane_mismatch)
 #pragma unroll
@@ -774,6 +831,7 @@ __global__ __launch_bounds__(64 * WAVES, 4) void lk_track_kernel(LkBatchN<NJ> ba
                 wave_lds_sync();
                 have_tile = true;
             }
+            int w00, w01, w10, w11;
             bilinear_weights(qx - (float)iqx, qy - (float)iqy, w00, w01, w10, w11);
             int s1 = lane_abs_residual<C>(lds, lane_off + (tj_off + (iqy - oy) * Tile<C, TS>::ROW + (iqx - ox) * C),
                                           (w00 & 0xffff) | (w10 << 16), (w01 & 0xffff) | (w11 << 16), Ivp);
@@ -852,6 +910,10 @@ int svo_launch_lk_batch(svo_ctx *ctx, int n_jobs, const LkJob *jobs, const svo_p
     // restores the bands for an A/B.
     static const int batch_interleave = getenv("SVO_LK_INTERLEAVE_BATCH") ? atoi(getenv("SVO_LK_INTERLEAVE_BATCH")) : 1;
     prm.interleave = n_jobs <= 2 ? lone_interleave : batch_interleave;  // two jobs: the two candidate passes of a pipelined chunk
+    // the identity path for windows on integer positions (step 1 of the kernel) computes what the interpolating path
+    // computes; SVO_LK_LATTICE=0 switches it off for an A/B and for the tests that compare the two
+    static const int lattice = getenv("SVO_LK_LATTICE") ? atoi(getenv("SVO_LK_LATTICE")) : 1;
+    prm.lattice = lattice;
     dim3 grid(((n_max + 7) / 8 + WAVES - 1) / WAVES * 8, n_jobs), block(64 * WAVES);  // x: a multiple of 8, every XCD band has all its slots
     ScopedKernelTime t(ctx, SVO_K_LK);
     if (c != 1 && c != 3) {
