@@ -14,7 +14,8 @@
 //      outside the image as OpenCV pads its derivative buffer) in LDS with aligned 16-byte row
 //      loads, builds its patch registers and the 2x2 normal matrix;
 //   2. stages a (22+2*JR)^2 tile of the next image around the current guess and iterates
-//      out of LDS; the tile is re-staged only when the guess drifts more than JR pixels.
+//      out of LDS; the tile is re-staged only when the guess drifts more than JR pixels, and the
+//      lane's rows are re-read from it only when the guess enters another pixel cell.
 // All sums of integer products are exact (int32 per lane, int64 across the wave via
 // cross-lane shuffles) and are rounded to float once, so the result does not depend on
 // the reduction order; scalar float math is compiled with -ffp-contract=off.
@@ -48,6 +49,7 @@ struct LkParams {
     int dpitch[SVO_MAX_LEVELS];  // bytes, multiple of 16
     int interleave;              // 1: keypoint = workgroup index (a lone launch: balance before L2 locality), 0: XCD bands
     int lattice;                 // 0: every level interpolates its patches, integer positions too (SVO_LK_LATTICE=0, for A/B and tests)
+    int cell_cache;              // 0: every iteration reloads and pairs its two tile rows, same cell or not (SVO_LK_CELL_CACHE=0, for A/B and tests)
 };
 static_assert(sizeof(LkBatch) + sizeof(LkParams) <= 4096, "kernel arguments are limited to 4 KB");
 
@@ -410,6 +412,18 @@ __device__ __forceinline__ int column_pair(const unsigned (&up)[ndwords(C)], con
     return (int)__builtin_amdgcn_perm(lo[K >> 2], up[K >> 2], sel);
 }
 
+// The (SEG+1)*C column pairs of a lane's two row runs.  They depend on the staged tile and on the integer
+// cell of the sampling position only, not on its fractions.
+template <int C>
+__device__ __forceinline__ void lane_column_pairs(const unsigned (&up)[ndwords(C)], const unsigned (&lo)[ndwords(C)],
+                                                  int (&V)[(SEG + 1) * C])
+{
+    ForEachElem<C, (SEG + 1) * C>::run([&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        V[k] = column_pair<C, k>(up, lo);
+    });
+}
+
 // The bilinear samples of a lane's SEG*C elements, descaled by `SHIFT` bits and packed as int16
 // pairs (low half = even element; an odd count is padded with 0):
 //   S_k = w00 p[k] + w10 q[k] + w01 p[k+C] + w11 q[k+C] + RND          (p, q: upper / lower row)
@@ -418,17 +432,11 @@ __device__ __forceinline__ int column_pair(const unsigned (&up)[ndwords(C)], con
 // packed without per-element shifts: one v_perm_b32 takes bits 8..23 of both sums (|S| < 2^23), one
 // v_pk_ashrrev_i16 drops the remaining SHIFT - 8 bits.
 template <int C, int SHIFT>
-__device__ __forceinline__ void lane_samples(const unsigned (&up)[ndwords(C)], const unsigned (&lo)[ndwords(C)],
-                                             int wv0, int wv1, int (&out)[npairs(C)])
+__device__ __forceinline__ void samples_of_pairs(const int (&V)[(SEG + 1) * C], int wv0, int wv1, int (&out)[npairs(C)])
 {
     static_assert(SHIFT >= 8 && SHIFT < 16, "the packing below takes bits 8..23 of each sum");
-    constexpr int NE = SEG * C, NV = (SEG + 1) * C;
+    constexpr int NE = SEG * C;
     constexpr int RND = 1 << (SHIFT - 1);
-    int V[NV];
-    ForEachElem<C, NV>::run([&](auto kc) {
-        constexpr int k = decltype(kc)::value;
-        V[k] = column_pair<C, k>(up, lo);
-    });
     int S[NE + 1];
     S[NE] = 0;
 #pragma unroll
@@ -441,6 +449,15 @@ __device__ __forceinline__ void lane_samples(const unsigned (&up)[ndwords(C)], c
         const short2v sh = {(short)(SHIFT - 8), (short)(SHIFT - 8)};
         out[j] = __builtin_bit_cast(int, (short2v)(__builtin_bit_cast(short2v, mid) >> sh));
     }
+}
+
+template <int C, int SHIFT>
+__device__ __forceinline__ void lane_samples(const unsigned (&up)[ndwords(C)], const unsigned (&lo)[ndwords(C)],
+                                             int wv0, int wv1, int (&out)[npairs(C)])
+{
+    int V[(SEG + 1) * C];
+    lane_column_pairs<C>(up, lo, V);
+    samples_of_pairs<C, SHIFT>(V, wv0, wv1, out);
 }
 
 // low (HI = false) or high (HI = true) int16 halves of two dwords as a pair: (x.half, y.half)
@@ -473,35 +490,58 @@ __device__ __forceinline__ int lane_abs_residual(const uint8_t *lds, int off, in
     return s;
 }
 
-// The iteration's form of the same sums:  sum (J - I) * Ix = sum J * Ix - sum I * Ix, and the second
-// term does not change during a level -- the caller passes it (negated) as the start of the
-// accumulator chain, which saves the v_pk_sub_i16 per element pair.  Integer arithmetic, no
-// overflow (|sum J * Ix| and |sum I * Ix| < 2^30 per lane): the same value bit for bit.
+// The iteration samples the staged J tile in two halves.  "Load and pair": the lane's two row runs at the
+// guess's integer cell, as column pairs.  They do not depend on the guess's fractions, so the iteration loop
+// keeps them while the guess stays in its cell and the tile is not re-staged.
 template <int C>
-__device__ __forceinline__ void lane_mismatch(const uint8_t *lds, int off, int wv0, int wv1,
-                                              const int (&Ixp)[npairs(C)], const int (&Iyp)[npairs(C)], int neg_c1,
-                                              int neg_c2, int &s1, int &s2)
+__device__ __forceinline__ void lane_load_pairs(const uint8_t *lds, int off, int (&V)[(SEG + 1) * C])
 {
     unsigned r0[ndwords(C)], r1[ndwords(C)];
     load_row_packed<C>(lds, off, r0);
     load_row_packed<C>(lds, off + Tile<C, TS>::ROW, r1);
-    int Jp[npairs(C)];
-    lane_samples<C, W_BITS - 5>(r0, r1, wv0, wv1, Jp);
-    // the chains start from the level's constants: the first link in the three-operand form (the compiler's
-    // accumulate-in-place form costs a copy of each constant per iteration)
-    asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(s1) : "v"(Jp[0]), "v"(Ixp[0]), "v"(neg_c1));
-    asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(s2) : "v"(Jp[0]), "v"(Iyp[0]), "v"(neg_c2));
+    lane_column_pairs<C>(r0, r1, V);
+}
+
+// "Weigh and dot", the iteration's form of the residual sums:  sum (J - I) * Ix = sum J * Ix - sum I * Ix, and
+// the second term does not change during a level -- the caller passes it (negated) as the start of the
+// accumulator chain, which saves the v_pk_sub_i16 per element pair.  Integer arithmetic, no
+// overflow (|sum J * Ix| and |sum I * Ix| < 2^30 per lane): the same value bit for bit.
+template <int C>
+__device__ __forceinline__ void lane_mismatch(const int (&V)[(SEG + 1) * C], int wv0, int wv1,
+                                              const int (&Ixp)[npairs(C)], const int (&Iyp)[npairs(C)], int neg_c1,
+                                              int neg_c2, int &s1, int &s2)
+{
+    // element pair by element pair, GROUP pairs at a time: the sums of a group are finished before the next
+    // group's samples start, so that few of them are alive beside the cached column pairs
+    constexpr int NE = SEG * C, RND = 1 << (W_BITS - 5 - 1), GROUP = 4;
+    const short2v sh = {(short)(W_BITS - 5 - 8), (short)(W_BITS - 5 - 8)};
 #pragma unroll
-    for (int j = 1; j < npairs(C); j++) {
-        s1 = sdot2(Jp[j], Ixp[j], s1);
-        s2 = sdot2(Jp[j], Iyp[j], s2);
+    for (int j = 0; j < npairs(C); j++) {
+        const int k0 = 2 * j, k1 = 2 * j + 1;
+        const int S0 = sdot2(V[k0 + C], wv1, sdot2_sconst(V[k0], wv0, RND));
+        const int S1 = k1 < NE ? sdot2(V[k1 + C], wv1, sdot2_sconst(V[k1], wv0, RND)) : 0;
+        const int mid = (int)__builtin_amdgcn_perm((unsigned)S1, (unsigned)S0, 0x06050201u);  // bytes 1,2 of each
+        const int Jp = __builtin_bit_cast(int, (short2v)(__builtin_bit_cast(short2v, mid) >> sh));
+        if (j == 0) {
+            // the chains start from the level's constants: the first link in the three-operand form (the compiler's
+            // accumulate-in-place form costs a copy of each constant per iteration)
+            asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(s1) : "v"(Jp), "v"(Ixp[0]), "v"(neg_c1));
+            asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(s2) : "v"(Jp), "v"(Iyp[0]), "v"(neg_c2));
+        } else {
+            s1 = sdot2(Jp, Ixp[j], s1);
+            s2 = sdot2(Jp, Iyp[j], s2);
+        }
+        if (j % GROUP == GROUP - 1 && j + 1 < npairs(C))
+            asm volatile("" : "+v"(s1), "+v"(s2), "+v"(wv0), "+v"(wv1));
     }
 }
 
 // One launch may carry the LK passes of several independent chunks of the stream (blockIdx.y picks
 // the job): the launch lasts as long as the slowest keypoint of ANY job, so two jobs cost little
 // more than one (svo_vo_run_chunks, chunks that share a context).
-template <int C, int NJ>
+// WANT_ERR = false: no job of the launch asks for the level-0 residual (the front-end never does).  The template
+// patch then dies with step 1 of a level instead of occupying its registers through the iteration loop.
+template <int C, int NJ, bool WANT_ERR>
 __global__ __launch_bounds__(64 * WAVES, 4) void lk_track_kernel(LkBatchN<NJ> batch, LkParams prm)
 {
     const LkJob &job = batch.j[blockIdx.y];
@@ -514,7 +554,7 @@ __global__ __launch_bounds__(64 * WAVES, 4) void lk_track_kernel(LkBatchN<NJ> ba
     const int *__restrict__ d_n = job.d_n;
     float *__restrict__ next_pts = job.next_pts;
     uint8_t *__restrict__ status = job.status;
-    float *__restrict__ err = job.err;
+    float *__restrict__ err = WANT_ERR ? job.err : nullptr;
     float *__restrict__ min_eig_out = job.min_eig;
     const int n = d_n ? min(*d_n, n_cap) : n_cap;  // live count may sit in HBM (chained stages)
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -731,6 +771,21 @@ __global__ __launch_bounds__(64 * WAVES, 4) void lk_track_kernel(LkBatchN<NJ> ba
         }
         neg_c1 = -neg_c1;
         neg_c2 = -neg_c2;
+        // The template patch has one use left, the level-0 residual after the iterations.  At C = 3 it waits for it in the
+        // LDS the J tile leaves free (the wave's area is sized by the derivative tile, which is consumed by now) instead
+        // of in 11 registers the iteration loop needs: lane l's dwords at PARK + 4 l + 256 k, conflict-free.
+        constexpr bool PARK_IVP = WANT_ERR && C == 3;
+        constexpr int PARK = Tile<C, TS>::BYTES;
+        static_assert(!PARK_IVP || PARK + npairs(C) * 256 <= Lds<C>::WAVE_BYTES, "no room for the parked template patch");
+        if constexpr (PARK_IVP) {
+            if (level == 0) {
+                wave_lds_sync();
+                int *park = reinterpret_cast<int *>(lds + PARK) + lane;
+#pragma unroll
+                for (int k = 0; k < npairs(C); k++)
+                    park[64 * k] = Ivp[k];
+            }
+        }
         float A11, A12, A22;
         wave_sum3_float(a11, a12, a22, A11, A12, A22);
         A11 *= FLT_SCALE;
@@ -763,14 +818,22 @@ __global__ __launch_bounds__(64 * WAVES, 4) void lk_track_kernel(LkBatchN<NJ> ba
         int tj_off = 0;          // LDS byte offset of the staged tile's pixel (0, 0): TJ's offset + the staging shift
         bool stepped = false;    // at least one Newton step taken: the output is nxp + half (else the guess itself)
         bool out_set = false;    // left through the oscillation test: the output (backed off half a step) is written there
-        for (int j = 0; j < prm.max_count; j++) {
-            const float fx = floorf(nxp), fy = floorf(nyp);
-            const int inx = uniform_int_of(fx), iny = uniform_int_of(fy);
-            if (inx < -WIN || inx >= lw || iny < -WIN || iny >= lh) {
-                if (level == 0)
-                    st = 0;
-                break;
-            }
+        // The iterations of a level, as passes over pixel cells: the column pairs of the lane's two row runs depend on
+        // the staged tile and on the guess's integer cell (inx, iny) only, so the inner loop keeps them in registers
+        // and goes on for as long as the guess stays in its cell (after the first step of a level: about every
+        // second iteration).  A guess that leaves the cell returns to the outer loop, which re-stages the tile when
+        // the guess has drifted off it and loads and pairs the rows of the new cell.  Wave-uniform integers: scalar
+        // compares and scalar branches.  With prm.cell_cache == 0 every iteration returns to the outer loop.
+        float fx = floorf(nxp), fy = floorf(nyp);
+        int inx = uniform_int_of(fx), iny = uniform_int_of(fy);
+        bool more = prm.max_count > 0;
+        if (more && (inx < -WIN || inx >= lw || iny < -WIN || iny >= lh)) {
+            if (level == 0)
+                st = 0;
+            more = false;
+        }
+        int j = 0;
+        while (more) {
             if (!have_tile || inx < ox || inx > ox + 2 * JR || iny < oy || iny > oy + 2 * JR) {
                 ox = inx - JR;
                 oy = iny - JR;
@@ -779,32 +842,51 @@ __global__ __launch_bounds__(64 * WAVES, 4) void lk_track_kernel(LkBatchN<NJ> ba
                 wave_lds_sync();
                 have_tile = true;
             }
-            int wv0, wv1;
-            bilinear_weight_pairs(nxp - fx, nyp - fy, wv0, wv1);
-            int s1, s2;
-            lane_mismatch<C>(lds, lane_off + (tj_off + (iny - oy) * Tile<C, TS>::ROW + (inx - ox) * C),
-                             wv0, wv1, Ixp, Iyp, neg_c1, neg_c2, s1, s2);
-            float b1, b2;
-            wave_sum2_float(s1, s2, b1, b2);
-            const float dx = (A12 * b2 - A22 * b1) * Dds;
-            const float dy = (A12 * b1 - A11 * b2) * Dds;
-            nxp += dx;
-            nyp += dy;
-            stepped = true;
-            // |dx|^2 + |dy|^2 <= eps^2 in double, as the reference; only a step that is small in float
-            // can pass, so the double arithmetic is skipped for all the others
-            if (uniform(fmaxf(fabsf(dx), fabsf(dy)) <= prm.eps_pre) &&
-                uniform((double)dx * (double)dx + (double)dy * (double)dy <= prm.eps_sq))
-                break;
-            // fabs((double)x) < 0.01  <=>  |x| <= 0.01f for a float x: 0.01f is the largest float below 0.01
-            if (j > 0 && uniform(fabsf(dx + pdx) <= 0.01f && fabsf(dy + pdy) <= 0.01f)) {
-                outx = (nxp + half) - dx * 0.5f;
-                outy = (nyp + half) - dy * 0.5f;
-                out_set = true;
-                break;
+            int V[(SEG + 1) * C];
+            lane_load_pairs<C>(lds, lane_off + (tj_off + (iny - oy) * Tile<C, TS>::ROW + (inx - ox) * C), V);
+            const int cx = inx, cy = iny;
+            for (;;) {
+                int wv0, wv1;
+                bilinear_weight_pairs(nxp - fx, nyp - fy, wv0, wv1);
+                int s1, s2;
+                lane_mismatch<C>(V, wv0, wv1, Ixp, Iyp, neg_c1, neg_c2, s1, s2);
+                float b1, b2;
+                wave_sum2_float(s1, s2, b1, b2);
+                const float dx = (A12 * b2 - A22 * b1) * Dds;
+                const float dy = (A12 * b1 - A11 * b2) * Dds;
+                nxp += dx;
+                nyp += dy;
+                stepped = true;
+                more = false;
+                // |dx|^2 + |dy|^2 <= eps^2 in double, as the reference; only a step that is small in float
+                // can pass, so the double arithmetic is skipped for all the others
+                if (uniform(fmaxf(fabsf(dx), fabsf(dy)) <= prm.eps_pre) &&
+                    uniform((double)dx * (double)dx + (double)dy * (double)dy <= prm.eps_sq))
+                    break;
+                // fabs((double)x) < 0.01  <=>  |x| <= 0.01f for a float x: 0.01f is the largest float below 0.01
+                if (j > 0 && uniform(fabsf(dx + pdx) <= 0.01f && fabsf(dy + pdy) <= 0.01f)) {
+                    outx = (nxp + half) - dx * 0.5f;
+                    outy = (nyp + half) - dy * 0.5f;
+                    out_set = true;
+                    break;
+                }
+                pdx = dx;
+                pdy = dy;
+                if (++j >= prm.max_count)
+                    break;
+                fx = floorf(nxp);
+                fy = floorf(nyp);
+                inx = uniform_int_of(fx);
+                iny = uniform_int_of(fy);
+                if (inx < -WIN || inx >= lw || iny < -WIN || iny >= lh) {
+                    if (level == 0)
+                        st = 0;
+                    break;
+                }
+                more = true;
+                if (!prm.cell_cache || inx != cx || iny != cy)
+                    break;  // another cell: load and pair its rows
             }
-            pdx = dx;
-            pdy = dy;
         }
         // the reference keeps nextPt = guess + half up to date inside the loop; the same float operations
         // in the same order, once, after it
@@ -821,24 +903,38 @@ __global__ __launch_bounds__(64 * WAVES, 4) void lk_track_kernel(LkBatchN<NJ> ba
                 st = 0;
                 continue;
             }
-            if (uniform(err == nullptr))
-                continue;  // the caller does not read err: only the bounds test above affects its outputs
-            if (!have_tile || iqx < ox || iqx > ox + 2 * JR || iqy < oy || iqy > oy + 2 * JR) {
-                ox = iqx - JR;
-                oy = iqy - JR;
-                wave_lds_sync();
-                tj_off = (int)(TJ - lds) + uniform(stage_tile<C, TS>(TJ, J, pitch, ox, oy, lane));
-                wave_lds_sync();
-                have_tile = true;
+            // without WANT_ERR no caller of this launch reads err: only the bounds test above affects its outputs
+            if constexpr (WANT_ERR) {
+                if (uniform(err == nullptr))
+                    continue;  // this job's caller does not read it
+                if (!have_tile || iqx < ox || iqx > ox + 2 * JR || iqy < oy || iqy > oy + 2 * JR) {
+                    ox = iqx - JR;
+                    oy = iqy - JR;
+                    wave_lds_sync();
+                    tj_off = (int)(TJ - lds) + uniform(stage_tile<C, TS>(TJ, J, pitch, ox, oy, lane));
+                    wave_lds_sync();
+                    have_tile = true;
+                }
+                int w00, w01, w10, w11;
+                bilinear_weights(qx - (float)iqx, qy - (float)iqy, w00, w01, w10, w11);
+                int Iv0[npairs(C)];
+                if constexpr (PARK_IVP) {
+                    const int *park = reinterpret_cast<const int *>(lds + PARK) + lane;
+#pragma unroll
+                    for (int k = 0; k < npairs(C); k++)
+                        Iv0[k] = park[64 * k];
+                } else {
+#pragma unroll
+                    for (int k = 0; k < npairs(C); k++)
+                        Iv0[k] = Ivp[k];
+                }
+                int s1 = lane_abs_residual<C>(lds, lane_off + (tj_off + (iqy - oy) * Tile<C, TS>::ROW + (iqx - ox) * C),
+                                              (w00 & 0xffff) | (w10 << 16), (w01 & 0xffff) | (w11 << 16), Iv0);
+                if (!active)
+                    s1 = 0;
+                const long long sabs = (long long)wave_sum_exact(s1);  // < 2^24
+                errv = (float)sabs / (float)(32 * WIN * C * WIN);
             }
-            int w00, w01, w10, w11;
-            bilinear_weights(qx - (float)iqx, qy - (float)iqy, w00, w01, w10, w11);
-            int s1 = lane_abs_residual<C>(lds, lane_off + (tj_off + (iqy - oy) * Tile<C, TS>::ROW + (iqx - ox) * C),
-                                          (w00 & 0xffff) | (w10 << 16), (w01 & 0xffff) | (w11 << 16), Ivp);
-            if (!active)
-                s1 = 0;
-            const long long sabs = (long long)wave_sum_exact(s1);  // < 2^24
-            errv = (float)sabs / (float)(32 * WIN * C * WIN);
         }
     }
 
@@ -914,25 +1010,35 @@ int svo_launch_lk_batch(svo_ctx *ctx, int n_jobs, const LkJob *jobs, const svo_p
     // computes; SVO_LK_LATTICE=0 switches it off for an A/B and for the tests that compare the two
     static const int lattice = getenv("SVO_LK_LATTICE") ? atoi(getenv("SVO_LK_LATTICE")) : 1;
     prm.lattice = lattice;
+    // the iteration loop keeps a lane's column pairs while the guess stays in its pixel cell; SVO_LK_CELL_CACHE=0 reloads
+    // them in every iteration (the same values), for an A/B and for the tests that compare the two
+    static const int cell_cache = getenv("SVO_LK_CELL_CACHE") ? atoi(getenv("SVO_LK_CELL_CACHE")) : 1;
+    prm.cell_cache = cell_cache;
+    // the level-0 residual is compiled in only where some job of the launch asks for it
+    bool want_err = false;
+    for (int k = 0; k < n_jobs; k++)
+        want_err = want_err || jobs[k].err != nullptr;
     dim3 grid(((n_max + 7) / 8 + WAVES - 1) / WAVES * 8, n_jobs), block(64 * WAVES);  // x: a multiple of 8, every XCD band has all its slots
     ScopedKernelTime t(ctx, SVO_K_LK);
     if (c != 1 && c != 3) {
         svo_set_error("lk: unsupported channel count %d (1 or 3)", c);
         return SVO_ERR_ARG;
     }
-    if (n_jobs == 1) {
-        if (c == 1)
-            hipLaunchKernelGGL((lk_track_kernel<1, 1>), grid, block, WAVES * Lds<1>::WAVE_BYTES, ctx->stream, one, prm);
+    auto launch = [&](auto c_c, auto err_c) {
+        constexpr int CC = decltype(c_c)::value;
+        constexpr bool WE = decltype(err_c)::value;
+        if (n_jobs == 1)
+            hipLaunchKernelGGL((lk_track_kernel<CC, 1, WE>), grid, block, WAVES * Lds<CC>::WAVE_BYTES, ctx->stream, one, prm);
         else
-            hipLaunchKernelGGL((lk_track_kernel<3, 1>), grid, block, WAVES * Lds<3>::WAVE_BYTES, ctx->stream, one, prm);
-    } else {
-        if (c == 1)
-            hipLaunchKernelGGL((lk_track_kernel<1, SVO_LK_MAX_JOBS>), grid, block, WAVES * Lds<1>::WAVE_BYTES, ctx->stream,
-                               batch, prm);
-        else
-            hipLaunchKernelGGL((lk_track_kernel<3, SVO_LK_MAX_JOBS>), grid, block, WAVES * Lds<3>::WAVE_BYTES, ctx->stream,
-                               batch, prm);
-    }
+            hipLaunchKernelGGL((lk_track_kernel<CC, SVO_LK_MAX_JOBS, WE>), grid, block, WAVES * Lds<CC>::WAVE_BYTES,
+                               ctx->stream, batch, prm);
+    };
+    using one_c = std::integral_constant<int, 1>;
+    using three_c = std::integral_constant<int, 3>;
+    if (c == 1)
+        want_err ? launch(one_c(), std::true_type()) : launch(one_c(), std::false_type());
+    else
+        want_err ? launch(three_c(), std::true_type()) : launch(three_c(), std::false_type());
     SVO_HIP(hipGetLastError());
     return SVO_OK;
 }
