@@ -250,6 +250,44 @@ int svo_recover_pose(svo_ctx *ctx, const double *E9, const float *p1, const floa
  * largest magnitude positive, and u3 = u1 x u2, v3 = v1 x v2 (det +1).  Host only.                 */
 int svo_decompose_essential(const double *E9, double *R1, double *R2, double *t);
 
+/* ---- descriptor matching: cv::BFMatcher(normType, false).knnMatch + the ratio test ----------------------------------
+ * The block the reference runs wherever it pairs features outside the dense grid (src/triangulation.cpp:120-133, the
+ * DENSE_FLAG == false branch of stereoTriangulate; src/StereoCV.cpp:77-88,136-147; src/bundleAdjust.cpp:269-271):
+ *   desc.convertTo(CV_32F); BFMatcher().knnMatch(desc1, desc2, matches, 2); keep m if m.distance < 0.8 * n.distance
+ * svo_knn_match runs knnMatch for nprob (1..16) independent problems: problem p matches query rows q_offsets[p] ..
+ * q_offsets[p+1]-1 against train rows t_offsets[p] .. t_offsets[p+1]-1 (offsets: nprob + 1 ints each, HOST memory
+ * always).  Descriptors are row-major, `dim` elements per row, and are read as 32-bit words: both arrays 4-byte aligned.
+ * idx / dist hold k entries per query row (row r of the query array at r * k), best first, and follow `mem`; train
+ * indices are local to the problem.
+ *   norm              elements      dim                  selection key                       dist
+ *   SVO_MATCH_L2_F32  float         1..256               s (below)                           float sqrt(s)
+ *   SVO_MATCH_L2_U8   bytes         4..256, multiple of 4  sum (a_i - b_i)^2 in integers     float sqrt of the exact integer
+ *   SVO_MATCH_HAMMING uint32 words  1..16 (ORB: 8)       popcount of the xor                 the count as a float
+ * The float key: s = 0; for i in 0..dim-1: t = a_i - b_i; s = s + t*t -- every operation a float operation of its own,
+ * in index order, one accumulator, no FMA (direct differences: the |a|^2 + |b|^2 - 2ab expansion rounds differently and
+ * loses the small distances the ratio test reads).  Both square roots are correctly rounded.  SVO_MATCH_L2_U8 is the
+ * reference's live case -- ORB / BRIEF bytes cast to CV_32F: with dim <= 256 the sum stays below 2^24, every partial sum
+ * is an exact float, so it returns the same bits as SVO_MATCH_L2_F32 on the converted floats in ANY summation order.
+ * Order: ascending key, equal keys to the LOWER train index; selection is on the key, not on the rooted value; a NaN
+ * key orders behind every number.  With fewer than k train rows the missing slots are idx -1, dist +inf; a problem
+ * without queries writes nothing.  k: 1..4.  At most 32768 queries and 32768 train rows per problem
+ * (SVO_ERR_CAPACITY).  SVO_ERR_ARG: an unknown norm, a bad dim or k, decreasing offsets, null or misaligned pointers.
+ * A batch returns the same bits as its problems one call at a time.  No nq x nt distance matrix is formed in memory
+ * (csrc/match.hip).                                                                             */
+enum { SVO_MATCH_L2_F32 = 0, SVO_MATCH_L2_U8 = 1, SVO_MATCH_HAMMING = 2 };
+int svo_knn_match(svo_ctx *ctx, int norm, const void *query, const void *train, int dim, const int *q_offsets,
+                  const int *t_offsets, int nprob, int k, int *idx, float *dist, int mem);
+/* The filter loop of src/triangulation.cpp:127-133 for ONE problem: query i (0 .. nq-1; idx / dist: nq x k as
+ * svo_knn_match writes them) is kept when k >= 2, idx[i*k+1] >= 0 and (double)dist[i*k] < ratio * (double)dist[i*k+1]
+ * -- the comparison in double, as the C++ expression performs it.  Kept pairs in query order: p1[j] = xy_query[i],
+ * p2[j] = xy_train[idx[i*k]] (x, y floats; p1 / p2: nq pairs capacity).  mask (optional): a byte per query, 1 = kept.
+ * *count is a HOST int in both modes (the call synchronises for it).  Device outputs must not overlap the inputs.
+ * Every idx[i*k] must be -1 or name a valid xy_train row: the call has no train count to check it against (host mode
+ * stages xy_train up to the largest idx[i*k]).
+ * At most 32768 queries.                                                                                              */
+int svo_ratio_pairs(svo_ctx *ctx, const int *idx, const float *dist, int nq, int k, double ratio, const float *xy_query,
+                    const float *xy_train, float *p1, float *p2, uint8_t *mask, int *count, int mem);
+
 /* ---- loop-closure detection: features ---------------------------------------------------------- */
 /* cv::ORB::create()->detectAndCompute(img, Mat(), kp, desc) of visualSLAM::checkLoopDetectorStatus,
  * src/optimizationStuff.cpp:49-56.  image: h x w x c (BGR or grey).  Up to n_features (500

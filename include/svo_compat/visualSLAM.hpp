@@ -41,7 +41,10 @@ class visualSLAM {
     int cooldownTimer = 0;
     bool LC_FLAG = false;
     bool SHUTDOWN_FLAG = false;
+    // true: the dense grid + LK branch of stereoTriangulate; false: its ORB + BFMatcher branch (src/triangulation.cpp:104-134).
+    // Only the stage method reads it: processFrame's fused svo_vo_* runner is dense-only.
     bool DENSE_FLAG = true;
+    int orbFeatures = 1000;         // ORB::create(1000), src/triangulation.cpp:105
     double focal_x = 7.188560000000e+02, cx = 6.071928000000e+02;
     double focal_y = 7.188560000000e+02, cy = 1.852157000000e+02;
     int gridStep = 30;              // src/triangulation.cpp:89
@@ -116,7 +119,7 @@ class visualSLAM {
         compact2(mask, refPts, trkPts);
     }
 
-    // ---- src/triangulation.cpp:73-166 (dense branch) ----
+    // ---- src/triangulation.cpp:73-166 (both branches of DENSE_FLAG) ----
     void stereoTriangulate(const Mat &im1, const Mat &im2, std::vector<Point3f> &ref3dPts,
                            std::vector<Point2f> &ref2dPts)
     {
@@ -124,12 +127,16 @@ class visualSLAM {
             std::printf("NULL IMG\n");  // src/triangulation.cpp:81-84
             return;
         }
-        std::vector<KeyPoint> dkps = denseKeypointExtractor(im1, gridStep);
         std::vector<Point2f> refPts, trkPts;
-        for (const KeyPoint &k : dkps)
-            refPts.emplace_back(k.pt);
-        denseLKtracking(im1, im2, refPts, trkPts);
-        FmatThresholding(refPts, trkPts);
+        if (DENSE_FLAG) {
+            std::vector<KeyPoint> dkps = denseKeypointExtractor(im1, gridStep);
+            for (const KeyPoint &k : dkps)
+                refPts.emplace_back(k.pt);
+            denseLKtracking(im1, im2, refPts, trkPts);
+            FmatThresholding(refPts, trkPts);
+        } else {
+            orbRatioPairs(im1, im2, refPts, trkPts);  // no FmatThresholding in this branch, as upstream
+        }
         // getColors (include/monoUtils.h:180-193)
         svo_pyramid *p = nullptr;
         check(svo_pyramid_create(ctx_, mat_cols(im1), mat_rows(im1), mat_channels(im1), 1, &p));
@@ -475,6 +482,35 @@ class visualSLAM {
         svo_pyramid_destroy(ctx_, pa);
         svo_pyramid_destroy(ctx_, pb);
         check(rc);
+    }
+    // src/triangulation.cpp:105-133: ORB::create(orbFeatures) on both images (one set of launches), desc.convertTo(CV_32F) +
+    // BFMatcher().knnMatch(desc1, desc2, matches, 2) = the L2 norm of the descriptor bytes, m.distance < 0.8 * n.distance
+    void orbRatioPairs(const Mat &im1, const Mat &im2, std::vector<Point2f> &pt1, std::vector<Point2f> &pt2)
+    {
+        if (mat_cols(im1) != mat_cols(im2) || mat_rows(im1) != mat_rows(im2) || mat_channels(im1) != mat_channels(im2))
+            throw SvoError(SVO_ERR_ARG, "stereoTriangulate: the two images differ in size");
+        svo_orb_params prm;
+        svo_orb_default_params(&prm);
+        prm.n_features = orbFeatures;
+        const size_t nf = (size_t)(orbFeatures > 0 ? orbFeatures : 0);
+        const uint8_t *imgs[2] = {mat_data(im1), mat_data(im2)};
+        std::vector<Point2f> kp(2 * nf);
+        std::vector<uint32_t> desc(2 * nf * 8);
+        int n[2] = {0, 0};
+        check(svo_orb_extract_batch(ctx_, imgs, 2, mat_cols(im1), mat_rows(im1), mat_channels(im1), &prm, f(kp), nullptr, nullptr,
+                                    nullptr, desc.data(), n, SVO_MEM_HOST));
+        const int qo[2] = {0, n[0]}, to[2] = {0, n[1]};
+        std::vector<int> idx((size_t)n[0] * 2);
+        std::vector<float> dist((size_t)n[0] * 2);
+        check(svo_knn_match(ctx_, SVO_MATCH_L2_U8, desc.data(), desc.data() + nf * 8, 32, qo, to, 1, 2, idx.data(), dist.data(),
+                            SVO_MEM_HOST));
+        pt1.assign((size_t)n[0], Point2f());
+        pt2.assign((size_t)n[0], Point2f());
+        int cnt = 0;
+        check(svo_ratio_pairs(ctx_, idx.data(), dist.data(), n[0], 2, 0.8, f(kp), f(kp) + 2 * nf, f(pt1), f(pt2), nullptr, &cnt,
+                              SVO_MEM_HOST));
+        pt1.resize((size_t)cnt);
+        pt2.resize((size_t)cnt);
     }
     void compact2(const std::vector<uint8_t> &mask, std::vector<Point2f> &a, std::vector<Point2f> &b)
     {

@@ -656,6 +656,107 @@ def decompose_essential(E):
     return R1, R2, t
 
 
+# ---- descriptor matching: BFMatcher::knnMatch + the ratio test (src/triangulation.cpp:120-133) ----------------------
+MATCH_L2_F32, MATCH_L2_U8, MATCH_HAMMING = 0, 1, 2
+
+
+def _match_rows(a, norm):
+    """descriptor rows for ``svo_knn_match`` -> (contiguous array or tensor, dim).  L2_F32: float32 rows.  L2_U8 / HAMMING: the
+    bytes of the rows, whatever integer type holds them (ORB's n x 8 uint32 words are 32 bytes, or 8 words, per row)."""
+    if _is_device(a):
+        import torch
+
+        a = a.contiguous()
+        assert a.ndim == 2
+        if norm == MATCH_L2_F32:
+            assert a.dtype == torch.float32, "L2_F32 takes float32 rows"
+            return a, int(a.shape[1])
+        assert not a.dtype.is_floating_point, "L2_U8 / HAMMING take integer rows"
+        row_bytes = int(a.shape[1]) * a.element_size()
+    else:
+        a = np.asarray(a)
+        assert a.ndim == 2
+        if norm == MATCH_L2_F32:
+            a = np.ascontiguousarray(a, np.float32)
+            return a, int(a.shape[1])
+        assert a.dtype.kind in "ui", "L2_U8 / HAMMING take integer rows"
+        a = np.ascontiguousarray(a)
+        row_bytes = int(a.shape[1]) * a.itemsize
+    if norm == MATCH_L2_U8:
+        return a, row_bytes
+    assert row_bytes % 4 == 0, "HAMMING rows are whole 32-bit words"
+    return a, row_bytes // 4
+
+
+@_ctx_method
+def knn_match(self, query, train, k=2, norm=MATCH_L2_U8, q_offsets=None, t_offsets=None):
+    """``svo_knn_match`` (cv::BFMatcher(norm, false).knnMatch): query / train descriptor rows (numpy arrays, or device
+    tensors which give device tensors back) -> (idx [nq, k] int32, dist [nq, k] float32), best first, ties to the lower
+    train index, missing slots -1 / inf.  q_offsets / t_offsets (p + 1 ints each): up to 16 independent problems over row
+    ranges of the two arrays, train indices local to each; without them one problem over all rows."""
+    q, dim = _match_rows(query, norm)
+    t, dim_t = _match_rows(train, norm)
+    assert dim == dim_t, "query and train rows differ in length"
+    dev = _is_device(q)
+    assert dev == _is_device(t), "query and train must live in the same memory"
+    nq, nt = int(q.shape[0]), int(t.shape[0])
+    qo = np.ascontiguousarray([0, nq] if q_offsets is None else q_offsets, np.int32)
+    to = np.ascontiguousarray([0, nt] if t_offsets is None else t_offsets, np.int32)
+    assert len(qo) == len(to) and len(qo) >= 2
+    assert len(qo) < 2 or (int(qo[-1]) <= nq and int(to[-1]) <= nt), "offsets beyond the arrays"
+    nprob = len(qo) - 1
+    if dev:
+        import torch
+
+        idx = torch.full((nq, k), -1, dtype=torch.int32, device=q.device)
+        dist = torch.full((nq, k), float("inf"), dtype=torch.float32, device=q.device)
+        torch.cuda.synchronize(q.device)
+        _check(self.lib.svo_knn_match(self._h, int(norm), _ptr(q), _ptr(t), dim, _ptr(qo), _ptr(to), nprob, int(k), _ptr(idx),
+                                      _ptr(dist), MEM_DEVICE))
+        _check(self.lib.svo_ctx_sync(self._h))
+        return idx, dist
+    idx = np.full((nq, k), -1, np.int32)
+    dist = np.full((nq, k), np.inf, np.float32)
+    _check(self.lib.svo_knn_match(self._h, int(norm), _ptr(q), _ptr(t), dim, _ptr(qo), _ptr(to), nprob, int(k), _ptr(idx),
+                                  _ptr(dist), MEM_HOST))
+    return idx, dist
+
+
+@_ctx_method
+def ratio_pairs(self, idx, dist, xy_query, xy_train, ratio=0.8):
+    """``svo_ratio_pairs`` (the loop of src/triangulation.cpp:127-133): idx / dist as ``knn_match`` returns them for one
+    problem, xy_query / xy_train the key points (n x 2) -> (p1 [m, 2], p2 [m, 2], mask [nq] uint8).  numpy arrays, or
+    device tensors which give device tensors back."""
+    dev = _is_device(idx)
+    assert all(_is_device(a) == dev for a in (dist, xy_query, xy_train)), "all arrays must live in the same memory"
+    nq, k = int(idx.shape[0]), int(idx.shape[1])
+    cnt = C.c_int()
+    if dev:
+        import torch
+
+        i_, d_ = idx.to(torch.int32).contiguous(), dist.to(torch.float32).contiguous()
+        xq = xy_query.to(torch.float32).reshape(-1, 2).contiguous()
+        xt = xy_train.to(torch.float32).reshape(-1, 2).contiguous()
+        assert xq.shape[0] == nq
+        p1 = torch.zeros((max(nq, 1), 2), dtype=torch.float32, device=i_.device)
+        p2 = torch.zeros_like(p1)
+        mask = torch.zeros(max(nq, 1), dtype=torch.uint8, device=i_.device)
+        torch.cuda.synchronize(i_.device)
+        _check(self.lib.svo_ratio_pairs(self._h, _ptr(i_), _ptr(d_), nq, k, C.c_double(ratio), _ptr(xq), _ptr(xt), _ptr(p1),
+                                        _ptr(p2), _ptr(mask), C.byref(cnt), MEM_DEVICE))
+        _check(self.lib.svo_ctx_sync(self._h))
+        return p1[:cnt.value], p2[:cnt.value], mask[:nq]
+    i_, d_ = np.ascontiguousarray(idx, np.int32), np.ascontiguousarray(dist, np.float32)
+    xq = np.ascontiguousarray(xy_query, np.float32).reshape(-1, 2)
+    xt = np.ascontiguousarray(xy_train, np.float32).reshape(-1, 2)
+    assert xq.shape[0] == nq and (nq == 0 or int(i_[:, 0].max()) < xt.shape[0])
+    p1, p2 = np.zeros((max(nq, 1), 2), np.float32), np.zeros((max(nq, 1), 2), np.float32)
+    mask = np.zeros(max(nq, 1), np.uint8)
+    _check(self.lib.svo_ratio_pairs(self._h, _ptr(i_), _ptr(d_), nq, k, C.c_double(ratio), _ptr(xq), _ptr(xt), _ptr(p1), _ptr(p2),
+                                    _ptr(mask), C.byref(cnt), MEM_HOST))
+    return p1[:cnt.value].copy(), p2[:cnt.value].copy(), mask[:nq].copy()
+
+
 @_ctx_method
 def pnp_ransac(self, obj, img, K4, iterations=100, reproj_err=1.0, confidence=0.99, seed=0):
     obj = np.ascontiguousarray(obj, np.float32).reshape(-1, 3)
