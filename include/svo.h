@@ -85,7 +85,7 @@ int svo_ctx_reset_kernel_time(svo_ctx *ctx);
  * src/VisualSLAM.cpp:71, the cubic of findFundamentalMat at src/tracking.cpp:34,75, the adaptive
  * RANSAC bound of solvePnPRansac at src/keyFrameManagement.cpp:84).  This entry evaluates one of them
  * ON THE DEVICE over an array, so that a test can check the device and the host run it bit for bit. */
-enum { SVO_MATH_SIN = 0, SVO_MATH_COS = 1, SVO_MATH_ACOS = 2, SVO_MATH_CBRT = 3, SVO_MATH_LOG = 4 };
+enum { SVO_MATH_SIN = 0, SVO_MATH_COS = 1, SVO_MATH_ACOS = 2, SVO_MATH_CBRT = 3, SVO_MATH_LOG = 4, SVO_MATH_EXP = 5 };
 int svo_math_eval(svo_ctx *ctx, int fn, const double *x, int n, double *y, int mem);
 
 /* ---- diagnostics ---------------------------------------------------------------------------
@@ -213,6 +213,60 @@ int svo_stereo_rectify_q(double fx, double fy, double cx, double cy, double tx, 
 int svo_stereo_reproject(svo_ctx *ctx, const int16_t *disp, const uint8_t *image, int w, int h, int c,
                          const double *Q16, float disp_scale, float z_min, float z_max, int flip_y,
                          float *xyz_out, float *bgr_out, int *n_out, int mem);
+
+/* ---- SIFT: detection and descriptors of OpenCV 3.2's xfeatures2d::SIFT (src/StereoCV.cpp:64-88, 123-147) ----
+ * The reference pairs features by SIFT::create(N) -> detect / compute -> convertTo(CV_32F) -> BFMatcher().knnMatch(2) -> ratio
+ * 0.8 -> findFundamentalMat; svo_sift_extract_batch produces the features, svo_knn_match (SVO_MATCH_L2_F32, dim 128) and
+ * svo_ratio_pairs consume them.  The algorithm is the one tests/sift_numpy.py states operation by operation (DESIGN.md section
+ * 10d): doubled first octave, nOctaves = cvRound(log2(min(2w, 2h)) - 2) + 1, n_octave_layers + 3 Gaussian layers per octave,
+ * 26-neighbour extrema with the 5-step sub-pixel refinement, contrast and edge tests, 36-bin orientation histogram with peaks at
+ * 0.8 of the maximum, the 4 x 4 x 8 descriptor clipped at 0.2 and stored as saturated bytes in floats (what convertTo(CV_32F)
+ * yields).  Transcendentals are svo_exp / svo_cos / svo_sin of svo_math.h and OpenCV's fastAtan2 polynomial; histogram sums are
+ * exact integer sums, so the result does not depend on the order lanes add in.
+ *
+ * Output: key points in ascending (octave, layer, row, column) order of the refined extremum, the orientations of one extremum in
+ * ascending histogram bin; extrema whose refinement ends in the same cell are one key point (upstream's removeDuplicated).
+ * n_features > 0 keeps every key point whose response is at or above the n_features-th largest, ties included (retainBest), so
+ * an image can return more than n_features.  xy, size: full-resolution pixels (KeyPoint::pt, KeyPoint::size); angle: degrees in
+ * [0, 360); response: |contrast|; octave: cv's packed field (octave in the low byte, -1 = 255 for the doubled frame; layer in the
+ * second byte; the sub-layer offset in the third); desc: 128 floats per key point, integers 0 ... 255.
+ *
+ * svo_sift_extract_batch: n_images (1 ... 16) images of one size, w x h x c bytes each (c = 1, or 3 = BGR, converted with
+ * cvtColor's integer weights); every output array holds n_images x cap entries, image i's at i * cap, n[i] of them valid; desc may
+ * be NULL (detect only).  images: a host array of host or device pointers according to mem; n: HOST ints in both modes -- the
+ * call waits once, for the counts.  SVO_ERR_ARG: null or misaligned (4 bytes) pointers, c not 1 or 3, n_octave_layers outside
+ * 1 ... 8, w or h below 2 (the recipe's octave count would be 0) or above 16384, sigma <= 0 or so large that a Gaussian kernel
+ * exceeds 255 taps, cap < 1, n_images outside 1 ... 16.  SVO_ERR_CAPACITY, two cases: (a) an image yields more than cap key points after
+ * the filters -- every n[i] holds the needed count and the first min(n[i], cap) key points of each image are valid; (b) an image has
+ * more than 65536 refined extrema or 131072 oriented key points before the filters (the work arrays) -- the call returns at that
+ * image: the output arrays are left untouched (host memory) or unspecified (device memory), and n[] is written only up to and
+ * including that image.  svo_last_error tells the two apart.  There is no CPU fallback.
+ *
+ * svo_sift_describe: detector->compute(image, keypoints, desc) for key points that came from elsewhere: the pyramid of `image` is
+ * built as above and each key point is described in the layer its octave field names (scale and angle from size and angle).  A
+ * key point whose octave field names no layer of this pyramid gets a zero descriptor.  On the key points svo_sift_extract_batch
+ * returned it gives the same descriptors.  Every call builds the whole scale space again (it keeps nothing from an earlier
+ * svo_sift_extract_batch on the same image): to describe the key points it detects, pass desc to svo_sift_extract_batch.
+ *
+ * svo_sift_pyramid (diagnostics: the parity tests compare every layer with the restatement): the Gaussian and DoG stacks of one
+ * image, octave after octave, (n_octave_layers + 3) / (n_octave_layers + 2) planes of oh[o] x ow[o] floats each;
+ * svo_sift_pyramid_layout gives the octave count and sizes (ow, oh: 16 ints each, or NULL).                              */
+typedef struct svo_sift_params {
+    int n_features;            /* 0 = all (cv: 0); the reference: 10000 / 20000 */
+    int n_octave_layers;       /* 3 */
+    double contrast_threshold; /* 0.04 */
+    double edge_threshold;     /* 10 */
+    double sigma;              /* 1.6 */
+} svo_sift_params;
+void svo_sift_default_params(svo_sift_params *p);
+int svo_sift_extract_batch(svo_ctx *ctx, const uint8_t *const *images, int n_images, int w, int h, int c,
+                           const svo_sift_params *prm, int cap, float *xy, float *size, float *angle, float *response, int *octave,
+                           float *desc, int *n, int mem);
+int svo_sift_describe(svo_ctx *ctx, const uint8_t *image, int w, int h, int c, const svo_sift_params *prm, const float *xy,
+                      const float *size, const float *angle, const int *octave, int n, float *desc, int mem);
+int svo_sift_pyramid_layout(int w, int h, int n_octave_layers, int *n_octaves, int *ow, int *oh);
+int svo_sift_pyramid(svo_ctx *ctx, const uint8_t *image, int w, int h, int c, const svo_sift_params *prm, float *gauss, float *dog,
+                     int mem);
 
 /* ---- two-view monocular geometry: StereoProcess::monocularTriangulate, src/StereoCV.cpp:123-188 ---- */
 /* OpenCV 3.2's five-point solver (EMEstimatorCallback::runKernel, Nister's method) on nsamples

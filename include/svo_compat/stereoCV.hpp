@@ -135,20 +135,42 @@ class StereoProcess {
     }
 
     // include/stereoCV.h:66, src/StereoCV.cpp:123-188: two-view monocular reconstruction.  The reference matches SIFT
-    // features with a ratio test here; this adaptor uses the hot path's dense grid + LK instead, as stereoTriangulate
-    // does: denseKeypointExtractor / denseLKtracking(im1 -> im2) / FmatThresholding (3 px, 0.99), then
+    // features with a ratio test here; by default (SIFT_FLAG = false) this adaptor uses the hot path's dense grid + LK
+    // instead, as stereoTriangulate does: denseKeypointExtractor / denseLKtracking(im1 -> im2) / FmatThresholding (3 px, 0.99), then
     // svo_find_essential (1 px, 0.99) and svo_recover_pose on the F-inliers, and svo_triangulate of ALL F-inliers (as
     // upstream: inlier1 / inlier2, not the E inliers) with P1 = K[I|0], P2 = K[R|t] -- float points, t of unit norm.
     // The pose lands in monoR / monoT, the F-inliers in monoPts1 / monoPts2.
+    //
+    // SIFT_FLAG = true (opt-in): the reference's own sequence instead of the grid + LK -- SIFT::create(10000) on both images
+    // in one svo_sift_extract_batch call, BFMatcher().knnMatch(desc1, desc2, 2) = svo_knn_match(SVO_MATCH_L2_F32, k 2), the
+    // 0.8 ratio test = svo_ratio_pairs, then FmatThresholding and the same tail.  siftCapacity bounds the key points an
+    // image may return (retainBest keeps ties, so it can exceed the budget); beyond it the call throws SVO_ERR_CAPACITY.
     double monoR[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, monoT[3] = {0, 0, 0};
     std::vector<Point2f> monoPts1, monoPts2;
+    bool SIFT_FLAG = false;
+    int siftFeaturesMono = 10000, siftCapacity = 40000;
+    // detector->detect + compute of SIFT::create(nfeatures) on one image: KeyPoint fields as cv fills them, desc: 128
+    // floats per key point (what desc.convertTo(CV_32F) holds)
+    void siftFeatures(const Mat &img, std::vector<KeyPoint> &kps, std::vector<float> &desc, int nfeatures)
+    {
+        const Mat *imgs[1] = {&img};
+        std::vector<KeyPoint> k[1];
+        std::vector<float> d[1];
+        siftFeaturesBatch(imgs, 1, nfeatures, k, d);
+        kps.swap(k[0]);
+        desc.swap(d[0]);
+    }
     void monocularTriangulate(const Mat &im1, const Mat &im2, std::vector<Point3f> &out3d)
     {
-        std::vector<KeyPoint> dkps = slam_.denseKeypointExtractor(im1, slam_.gridStep);
         std::vector<Point2f> pt1, pt2;
-        for (const KeyPoint &k : dkps)
-            pt1.emplace_back(k.pt);
-        slam_.denseLKtracking(im1, im2, pt1, pt2);
+        if (SIFT_FLAG) {
+            siftRatioPairs(im1, im2, pt1, pt2);
+        } else {
+            std::vector<KeyPoint> dkps = slam_.denseKeypointExtractor(im1, slam_.gridStep);
+            for (const KeyPoint &k : dkps)
+                pt1.emplace_back(k.pt);
+            slam_.denseLKtracking(im1, im2, pt1, pt2);
+        }
         slam_.FmatThresholding(pt1, pt2);
         monoPts1 = pt1;
         monoPts2 = pt2;
@@ -185,6 +207,73 @@ class StereoProcess {
 
   private:
     static const float *fp(const std::vector<Point2f> &v) { return reinterpret_cast<const float *>(v.data()); }
+    static float *fpm(std::vector<Point2f> &v) { return reinterpret_cast<float *>(v.data()); }
+    // n images of one size through one svo_sift_extract_batch call
+    void siftFeaturesBatch(const Mat *const *imgs, int n, int nfeatures, std::vector<KeyPoint> *kps, std::vector<float> *desc)
+    {
+        const Mat &first = *imgs[0];
+        const uint8_t *ptrs[16];
+        if (n < 1 || n > 16)
+            throw SvoError(SVO_ERR_ARG, "siftFeatures: 1 ... 16 images per call");
+        for (int i = 0; i < n; i++) {
+            if (mat_cols(*imgs[i]) != mat_cols(first) || mat_rows(*imgs[i]) != mat_rows(first) ||
+                mat_channels(*imgs[i]) != mat_channels(first))
+                throw SvoError(SVO_ERR_ARG, "siftFeatures: the images differ in size");
+            ptrs[i] = mat_data(*imgs[i]);
+        }
+        svo_sift_params prm;
+        svo_sift_default_params(&prm);
+        prm.n_features = nfeatures;
+        const size_t cap = (size_t)(siftCapacity > 0 ? siftCapacity : 1), e = cap * (size_t)n;
+        std::vector<float> xy(2 * e), size(e), angle(e), resp(e), d(128 * e);
+        std::vector<int> oct(e), cnt((size_t)n);
+        check(svo_sift_extract_batch(ctx(), ptrs, n, mat_cols(first), mat_rows(first), mat_channels(first), &prm, (int)cap,
+                                     xy.data(), size.data(), angle.data(), resp.data(), oct.data(), d.data(), cnt.data(),
+                                     SVO_MEM_HOST));
+        for (int i = 0; i < n; i++) {
+            const size_t b = cap * (size_t)i, m = (size_t)cnt[(size_t)i];
+            kps[i].assign(m, KeyPoint());
+            for (size_t j = 0; j < m; j++) {
+                KeyPoint &k = kps[i][j];
+                k.pt = Point2f(xy[2 * (b + j)], xy[2 * (b + j) + 1]);
+                k.size = size[b + j];
+                k.angle = angle[b + j];
+                k.response = resp[b + j];
+                k.octave = oct[b + j];
+            }
+            desc[i].assign(d.begin() + 128 * b, d.begin() + 128 * (b + m));
+        }
+    }
+    // src/StereoCV.cpp:123-147: SIFT(10000) on both images, knnMatch(desc1, desc2, 2), m.distance < 0.8 * n.distance
+    void siftRatioPairs(const Mat &im1, const Mat &im2, std::vector<Point2f> &pt1, std::vector<Point2f> &pt2)
+    {
+        const Mat *imgs[2] = {&im1, &im2};
+        std::vector<KeyPoint> kps[2];
+        std::vector<float> desc[2];
+        siftFeaturesBatch(imgs, 2, siftFeaturesMono, kps, desc);
+        const int n1 = (int)kps[0].size(), n2 = (int)kps[1].size();
+        std::vector<Point2f> xy1, xy2;
+        for (const KeyPoint &k : kps[0])
+            xy1.emplace_back(k.pt);
+        for (const KeyPoint &k : kps[1])
+            xy2.emplace_back(k.pt);
+        pt1.clear();
+        pt2.clear();
+        if (n1 == 0 || n2 == 0)
+            return;
+        const int qo[2] = {0, n1}, to[2] = {0, n2};
+        std::vector<int> idx((size_t)n1 * 2);
+        std::vector<float> dist((size_t)n1 * 2);
+        check(svo_knn_match(ctx(), SVO_MATCH_L2_F32, desc[0].data(), desc[1].data(), 128, qo, to, 1, 2, idx.data(), dist.data(),
+                            SVO_MEM_HOST));
+        pt1.assign((size_t)n1, Point2f());
+        pt2.assign((size_t)n1, Point2f());
+        int cnt = 0;
+        check(svo_ratio_pairs(ctx(), idx.data(), dist.data(), n1, 2, 0.8, fp(xy1), fp(xy2), fpm(pt1), fpm(pt2), nullptr, &cnt,
+                              SVO_MEM_HOST));
+        pt1.resize((size_t)cnt);
+        pt2.resize((size_t)cnt);
+    }
 #if defined(SVO_WITH_OPENCV) && defined(CV_16SC1)
     static constexpr int kDisp16S = CV_16SC1;
 #else

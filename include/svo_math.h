@@ -2,7 +2,8 @@
  * implementation shared by the HIP library and the CPU oracle.
  *
  * Why: sin / cos / acos / cbrt / log decide thresholds on the pose path (the cubic of the 7-point
- * solver, Rodrigues and its inverse in the PnP refinement, the adaptive RANSAC bound).  The device
+ * solver, Rodrigues and its inverse in the PnP refinement, the adaptive RANSAC bound); exp weighs the
+ * Gaussian kernels and windows of the SIFT extractor (sift.hip).  The device
  * math library and the host's libm round these differently in the last place, which is enough to flip
  * an inlier at a threshold some tens of frames into a sequence.  With the functions below both sides
  * execute the same IEEE-754 double operations (+, -, *, /, sqrt: correctly rounded on the host and on
@@ -209,6 +210,29 @@ SVO_MATH_FN double svo_log(double x)
     const double hfsq = 0.5 * f * f;
     const double dk = (double)k;
     return dk * LN2_HI - ((hfsq - (s * (hfsq + R) + dk * LN2_LO)) - f);
+}
+
+/* e^x for a finite double: x = k ln2 + r with |r| <= ln2 / 2 (ln2 in two pieces, k * LN2_HI exact for |k| < 2^11), the
+ * classic r - r^2 P(r^2) kernel, the scaling by 2^k as an integer addition to the exponent field.  Results below the
+ * normal range are returned as 0, above it as +inf (callers here pass arguments in [-100, 0]). */
+SVO_MATH_FN double svo_exp(double x)
+{
+    const double LN2_HI = 6.93147180369123816490e-01, LN2_LO = 1.90821492927058770002e-10,
+                 INV_LN2 = 1.44269504088896338700e+00;
+    const double P1 = 1.66666666666666019037e-01, P2 = -2.77777777770155933842e-03, P3 = 6.61375632143793436117e-05,
+                 P4 = -1.65339022054652515390e-06, P5 = 4.13813679705723846039e-08;
+    if (x > 709.0)
+        return svo_m_from_bits(0x7ff0000000000000ull);
+    if (x < -708.0)
+        return 0.0;
+    const double k = SVO_MATH_RINT(x * INV_LN2);
+    const double hi = x - k * LN2_HI;
+    const double lo = k * LN2_LO;
+    const double r = hi - lo;
+    const double t = r * r;
+    const double c = r - t * (P1 + t * (P2 + t * (P3 + t * (P4 + t * P5))));
+    const double y = 1.0 - ((lo - (r * c) / (2.0 - c)) - hi);
+    return svo_m_from_bits(svo_m_bits(y) + ((uint64_t)(int64_t)k << 52));
 }
 
 /* x^n for a small positive integer n, multiplications in ascending order (x * x * ... * x) */

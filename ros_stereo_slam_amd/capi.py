@@ -493,7 +493,8 @@ def stereo_reproject(self, disp, image, Q, disp_scale=1.0, z_min=0.01, z_max=5.0
     return xyz[:k].copy(), (bgr[:k].copy() if bgr is not None else None)
 
 
-MATH_FN = {"sin": 0, "cos": 1, "acos": 2, "cbrt": 3, "log": 4}
+MATH_FN = {"sin": 0, "cos": 1, "acos": 2, "cbrt": 3, "log": 4, "exp": 5}
+MATH_EXP = MATH_FN["exp"]
 
 
 @_ctx_method
@@ -504,6 +505,108 @@ def math_eval(self, fn: str, x) -> np.ndarray:
     y = np.empty_like(x)
     _check(self.lib.svo_math_eval(self._h, MATH_FN[fn], _ptr(x), x.size, _ptr(y), MEM_HOST))
     return y
+
+
+class SiftParams(C.Structure):
+    """``svo_sift_params``: cv::xfeatures2d::SIFT::create's arguments (n_features 0 = all)."""
+    _fields_ = [("n_features", C.c_int), ("n_octave_layers", C.c_int), ("contrast_threshold", C.c_double),
+                ("edge_threshold", C.c_double), ("sigma", C.c_double)]
+
+
+def sift_params(**overrides) -> SiftParams:
+    p = SiftParams()
+    load().svo_sift_default_params(C.byref(p))
+    for k, v in overrides.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def _sift_prm(params) -> SiftParams:
+    return params if isinstance(params, SiftParams) else sift_params(**(params or {}))
+
+
+def _image_shape(im):
+    h, w = im.shape[:2]
+    return w, h, (1 if im.ndim == 2 else im.shape[2])
+
+
+@_ctx_method
+def sift_extract(self, images, params=None, cap=20000, descriptors=True):
+    """``svo_sift_extract_batch``: 1 ... 16 images of one size (host arrays or device tensors) in one set of launches -> per
+    image (xy [n, 2], size [n], angle [n], response [n] float32, octave [n] int32 -- cv's packed field --, desc [n, 128] float32
+    or None), host arrays in the recipe's order.  More than ``cap`` key points in an image: SvoError(SVO_ERR_CAPACITY) whose
+    ``needed`` lists the counts."""
+    prm = _sift_prm(params)
+    nimg = len(images)
+    w, h, c = _image_shape(images[0])
+    n = (C.c_int * max(nimg, 1))()
+    e = nimg * cap
+    dev = _is_device(images[0])
+    if dev:
+        import torch
+
+        images = [im.contiguous() for im in images]
+        fb = torch.zeros(e * (5 + (128 if descriptors else 0)), dtype=torch.float32, device=images[0].device)
+        ob = torch.zeros(e, dtype=torch.int32, device=images[0].device)
+        torch.cuda.synchronize(images[0].device)
+        base = fb.data_ptr()
+        args = [C.c_void_p(base + 4 * k * e) for k in (0, 2, 3, 4)] + [_ptr(ob), C.c_void_p(base + 20 * e if descriptors else 0)]
+    else:
+        images = [np.ascontiguousarray(im, np.uint8) for im in images]
+        xy, size, angle = np.zeros((nimg, cap, 2), np.float32), np.zeros((nimg, cap), np.float32), np.zeros((nimg, cap), np.float32)
+        resp, octv = np.zeros((nimg, cap), np.float32), np.zeros((nimg, cap), np.int32)
+        desc = np.zeros((nimg, cap, 128), np.float32) if descriptors else None
+        args = [_ptr(xy), _ptr(size), _ptr(angle), _ptr(resp), _ptr(octv), _ptr(desc)]
+    ptrs = (C.c_void_p * max(nimg, 1))(*[_ptr(im).value for im in images])
+    rc = self.lib.svo_sift_extract_batch(self._h, ptrs, nimg, w, h, c, C.byref(prm), cap, *args, n, MEM_DEVICE if dev else MEM_HOST)
+    if rc != SVO_OK:
+        err = SvoError(rc, self.lib.svo_last_error().decode(errors="replace"))
+        err.needed = list(n[:nimg])
+        raise err
+    if dev:
+        _check(self.lib.svo_ctx_sync(self._h))
+        hb, octv = fb.cpu().numpy(), ob.cpu().numpy().reshape(nimg, cap)
+        xy, size = hb[:2 * e].reshape(nimg, cap, 2), hb[2 * e:3 * e].reshape(nimg, cap)
+        angle, resp = hb[3 * e:4 * e].reshape(nimg, cap), hb[4 * e:5 * e].reshape(nimg, cap)
+        desc = hb[5 * e:].reshape(nimg, cap, 128) if descriptors else None
+    return [(xy[i, :n[i]].copy(), size[i, :n[i]].copy(), angle[i, :n[i]].copy(), resp[i, :n[i]].copy(), octv[i, :n[i]].copy(),
+             desc[i, :n[i]].copy() if descriptors else None) for i in range(nimg)]
+
+
+@_ctx_method
+def sift_describe(self, image, xy, size, angle, octave, params=None) -> np.ndarray:
+    """``svo_sift_describe``: detector->compute(image, keypoints) -> desc [n, 128] float32 (host arrays in and out)."""
+    prm = _sift_prm(params)
+    img = np.ascontiguousarray(image, np.uint8)
+    w, h, c = _image_shape(img)
+    xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+    size, angle = np.ascontiguousarray(size, np.float32), np.ascontiguousarray(angle, np.float32)
+    octave = np.ascontiguousarray(octave, np.int32)
+    desc = np.zeros((len(xy), 128), np.float32)
+    _check(self.lib.svo_sift_describe(self._h, _ptr(img), w, h, c, C.byref(prm), _ptr(xy), _ptr(size), _ptr(angle), _ptr(octave),
+                                      len(xy), _ptr(desc), MEM_HOST))
+    return desc
+
+
+@_ctx_method
+def sift_pyramid(self, image, params=None):
+    """``svo_sift_pyramid`` (diagnostics) -> (gauss, dog): per octave float32 arrays [layers + 3, h, w] / [layers + 2, h, w]."""
+    prm = _sift_prm(params)
+    img = np.ascontiguousarray(image, np.uint8)
+    w, h, c = _image_shape(img)
+    no, ow, oh = C.c_int(), (C.c_int * 16)(), (C.c_int * 16)()
+    _check(self.lib.svo_sift_pyramid_layout(w, h, prm.n_octave_layers, C.byref(no), ow, oh))
+    px = [ow[o] * oh[o] for o in range(no.value)]
+    nl = prm.n_octave_layers
+    g, d = np.zeros(sum(px) * (nl + 3), np.float32), np.zeros(sum(px) * (nl + 2), np.float32)
+    _check(self.lib.svo_sift_pyramid(self._h, _ptr(img), w, h, c, C.byref(prm), _ptr(g), _ptr(d), MEM_HOST))
+    gauss, dog, a, b = [], [], 0, 0
+    for o in range(no.value):
+        gauss.append(g[a:a + px[o] * (nl + 3)].reshape(nl + 3, oh[o], ow[o]))
+        dog.append(d[b:b + px[o] * (nl + 2)].reshape(nl + 2, oh[o], ow[o]))
+        a, b = a + px[o] * (nl + 3), b + px[o] * (nl + 2)
+    return gauss, dog
 
 
 @_ctx_method

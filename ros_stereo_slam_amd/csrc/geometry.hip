@@ -656,6 +656,9 @@ __global__ void math_eval_kernel(int fn, const double *__restrict__ x, int n, do
     case SVO_MATH_CBRT:
         r = svo_cbrt(v);
         break;
+    case SVO_MATH_EXP:
+        r = svo_exp(v);
+        break;
     default:
         r = svo_log(v);
         break;
@@ -665,7 +668,7 @@ __global__ void math_eval_kernel(int fn, const double *__restrict__ x, int n, do
 
 int svo_math_eval(svo_ctx *ctx, int fn, const double *x, int n, double *y, int mem)
 {
-    SVO_CHECK_ARG(ctx && n >= 0 && (n == 0 || (x && y)) && fn >= SVO_MATH_SIN && fn <= SVO_MATH_LOG);
+    SVO_CHECK_ARG(ctx && n >= 0 && (n == 0 || (x && y)) && fn >= SVO_MATH_SIN && fn <= SVO_MATH_EXP);
     SVO_CHECK_ARG(mem == SVO_MEM_HOST || mem == SVO_MEM_DEVICE);
     if (n == 0)
         return SVO_OK;

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "svo_internal.h"
+#include "fast_atan2.hip.h"
 
 namespace {
 
@@ -682,29 +683,6 @@ __device__ __forceinline__ int wave_sum(int v)
     for (int off = 32; off >= 1; off >>= 1)
         v += __shfl_xor(v, off, 64);
     return v;
-}
-
-__device__ __forceinline__ float fast_atan2_deg(float y, float x)
-{
-    const float k = (float)(180 / 3.14159265358979323846);
-    const float p1 = 0.9997878412794807f * k, p3 = -0.3258083974640975f * k, p5 = 0.1555786518463281f * k,
-                p7 = -0.04432655554792128f * k;
-    const float ax = fabsf(x), ay = fabsf(y);
-    float a, c, c2;
-    if (ax >= ay) {
-        c = ay / (ax + (float)2.2204460492503131e-16);
-        c2 = c * c;
-        a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
-    } else {
-        c = ax / (ay + (float)2.2204460492503131e-16);
-        c2 = c * c;
-        a = 90.f - (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
-    }
-    if (x < 0)
-        a = 180.f - a;
-    if (y < 0)
-        a = 360.f - a;
-    return a;
 }
 
 // one wavefront per selected key point; grid (ceil(max want / 4), n_lev, batch)

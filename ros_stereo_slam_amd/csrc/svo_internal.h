@@ -134,6 +134,9 @@ struct svo_ctx {
     DevBuf sor_grid;
     // essential.hip: normalised points, the RANSAC's per-iteration models / counts / state, recoverPose's candidate masks
     DevBuf ess;
+    // sift.hip: the scale space (Gaussian and DoG layers of every image of a batch), the detector's work arrays, staged
+    // images and key points, the output block of host calls
+    DevBuf sift_pyr, sift_work, sift_img, sift_out;
 };
 
 // Low-latency host wait for everything queued on the context's stream: records an event and
