@@ -57,7 +57,9 @@ enum {
     SVO_K_PNP = 4,
     SVO_K_POSEGRAPH = 5,
     SVO_K_ANMS = 6,
-    SVO_K_COUNT = 7
+    SVO_K_BRIEF_INTEGRAL = 7, /* svo_brief_*: the row and column passes of the integral images */
+    SVO_K_BRIEF_DESCRIBE = 8, /* svo_brief_describe_batch: the key-point filter and the descriptor kernel */
+    SVO_K_COUNT = 9
 };
 
 typedef struct svo_ctx svo_ctx;
@@ -267,6 +269,41 @@ int svo_sift_describe(svo_ctx *ctx, const uint8_t *image, int w, int h, int c, c
 int svo_sift_pyramid_layout(int w, int h, int n_octave_layers, int *n_octaves, int *ow, int *oh);
 int svo_sift_pyramid(svo_ctx *ctx, const uint8_t *image, int w, int h, int c, const svo_sift_params *prm, float *gauss, float *dog,
                      int mem);
+
+/* ---- BRIEF: OpenCV 3.2's xfeatures2d::BriefDescriptorExtractor (src/StereoCV.cpp:66-75) -------------------------------
+ * StereoProcess::stereoTriangulate describes its SIFT key points with BriefDescriptorExtractor::create() -> compute, converts the
+ * bytes to floats and matches them with BFMatcher (L2): svo_sift_extract_batch (desc = NULL) finds the key points,
+ * svo_brief_describe_batch describes them, svo_knn_match (SVO_MATCH_L2_U8, dim = bytes) and svo_ratio_pairs pair them.  The
+ * algorithm is the one tests/brief_numpy.py states: grey by cvtColor's integer weights, the int32
+ * integral image ((h + 1) x (w + 1), zero first row and column), KeyPointsFilter::runByImageBorder(28) -- a key point stays when
+ * 28 <= cvRound(x) < w - 28 and the same for y, round half to even; an image with w <= 56 or h <= 56 keeps none --, and for test
+ * t with the table row (y1, x1, y2, x2) the bit S(y1, x1) < S(y2, x2) at bit 7 - t % 8 of byte t / 8, S the 9 x 9 box sum
+ * around ((int)(pt.y + 0.5) + y, (int)(pt.x + 0.5) + x).  One departure: a key point with (int)(x + 0.5) > w - 29 or
+ * (int)(y + 0.5) > h - 29 -- only a half-integer coordinate on the far border -- is removed as well; upstream reads one column
+ * or row past its integral image there.  use_orientation is not provided.
+ *
+ * The test table: upstream's generated_16/32/64.i are not part of this library.  The default tables are the library's own (both
+ * end points Gaussian with sigma 48 / 5, clamped to +-24, tools/gen_brief_pattern.py): descriptors are format-compatible with
+ * OpenCV's, not equal to them.  svo_brief_default_pattern copies the default of a descriptor length out (host only, no context):
+ * 8 * bytes rows of (y1, x1, y2, x2).  svo_brief_set_pattern replaces the table of one length for this context (a host that has
+ * OpenCV's tables sets them here); NULL brings the default back.  SVO_ERR_ARG: an entry outside +-24, a test with equal end points.
+ *
+ * svo_brief_describe_batch: n_images (1 ... 16) images of one size, w x h x c bytes each (c = 1, or 3 = BGR); images: a host array
+ * of host or device pointers according to mem.  Image i's key points are the n_in[i] <= cap (x, y) pairs at xy + 2 * i * cap
+ * (xy follows mem; n_in: HOST ints in both modes).  Outputs at row i * cap (they follow mem): desc, `bytes` (16, 32 or 64) per kept
+ * key point, and kept_index, the index of each kept key point among the image's n_in[i], ascending -- the order is preserved.
+ * n_out[i], HOST ints in both modes, is the number kept: the call waits once, for the counts.  In device mode the outputs must not
+ * overlap xy.  SVO_ERR_ARG: null or misaligned (4 bytes: xy, n_in, kept_index, n_out) pointers, c not 1 or 3, bytes not 16 / 32 /
+ * 64, n_images outside 1 ... 16, cap < 1, an n_in[i] outside 0 ... cap, w or h below 1 or above 16384.  SVO_ERR_CAPACITY:
+ * 255 w h > 2^31 - 1 (the int32 integral image could overflow), decided before anything is allocated.  Nothing is written when a
+ * call is refused.  A batch returns the same bits as one call per image, host memory the same as device memory.
+ *
+ * svo_brief_integral (diagnostics: the parity tests read the table): the (h + 1) x (w + 1) int32 integral image of one image.   */
+int svo_brief_default_pattern(int bytes, int8_t *pattern);
+int svo_brief_set_pattern(svo_ctx *ctx, int bytes, const int8_t *pattern);
+int svo_brief_describe_batch(svo_ctx *ctx, const uint8_t *const *images, int n_images, int w, int h, int c, int bytes,
+                             const float *xy, const int *n_in, int cap, int *kept_index, uint8_t *desc, int *n_out, int mem);
+int svo_brief_integral(svo_ctx *ctx, const uint8_t *image, int w, int h, int c, int32_t *sum, int mem);
 
 /* ---- two-view monocular geometry: StereoProcess::monocularTriangulate, src/StereoCV.cpp:123-188 ---- */
 /* OpenCV 3.2's five-point solver (EMEstimatorCallback::runKernel, Nister's method) on nsamples

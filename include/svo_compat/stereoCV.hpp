@@ -2,7 +2,8 @@
 // out3d) on the hot path's sparse stereo, and the dense SGBM demo of src/StereoCV.cpp -- stereoMatch(iter) and
 // reprojectDisparity(disp, pts, colours) -- on svo_sgbm_compute / svo_stereo_reproject -- and pclPublish(pts, colours)
 // on svo_sor_filter_large, the filtered cloud left in publishedCloud / publishedColors instead of a ROS message --
-// and monocularTriangulate(im1, im2, out3d) on svo_find_essential / svo_recover_pose / svo_triangulate.  getImg is
+// and monocularTriangulate(im1, im2, out3d) on svo_find_essential / svo_recover_pose / svo_triangulate; with BRIEF_FLAG
+// stereoTriangulate runs the reference's own SIFT + BRIEF sequence (svo_sift_extract_batch / svo_brief_describe_batch).  getImg is
 // public here, a thin wrapper over the frame loader.  visualizeCloud and mainLoop are not provided.
 #pragma once
 
@@ -118,9 +119,22 @@ class StereoProcess {
         }
     }
 
-    // include/stereoCV.h:62.  The reference matches SIFT features here (src/StereoCV.cpp:64-121);
-    // this adaptor uses the hot path's dense-grid LK + F-RANSAC + DLT triangulation instead and
+    // include/stereoCV.h:62.  The reference pairs SIFT key points by their BRIEF descriptors here (src/StereoCV.cpp:64-121); by
+    // default (BRIEF_FLAG = false) this adaptor uses the hot path's dense-grid LK + F-RANSAC + DLT triangulation instead and
     // says so: same output contract (camera-frame 3-D points, colours in color3dMap).
+    //
+    // BRIEF_FLAG = true (opt-in): the reference's own sequence -- SIFT::create(20000)->detect on both images in one
+    // svo_sift_extract_batch call (no SIFT descriptors), BriefDescriptorExtractor::create()->compute on both in one
+    // svo_brief_describe_batch call (key points runByImageBorder(28) removes are dropped, as cv erases them),
+    // desc.convertTo(CV_32F) + BFMatcher().knnMatch(2) = svo_knn_match(SVO_MATCH_L2_U8, dim briefBytes, k 2), the 0.8 ratio test =
+    // svo_ratio_pairs, FmatThresholding (3 px, 0.99) and svo_triangulate with P1 = K[I|0], P2 = K[I|(-baseline, 0, 0)].  The pairs
+    // after the ratio test stay in stereoPairs1 / 2, the F-inliers in stereoInliers1 / 2.  Fewer than 8 pairs after the ratio test
+    // give an empty out3d.  color3dMap is gathered at the left inliers so that it stays parallel to tri3dPoints, this adaptor's
+    // contract; upstream leaves color3dMap alone in this method.  The test table is the library's own unless
+    // svo_brief_set_pattern has set OpenCV's.
+    bool BRIEF_FLAG = false;
+    int siftFeaturesStereo = 20000, briefBytes = 32;
+    std::vector<Point2f> stereoPairs1, stereoPairs2, stereoInliers1, stereoInliers2;
     void stereoTriangulate(const Mat &im1, const Mat &im2, std::vector<Point3f> &out3d)
     {
         slam_.baseline = baseline;
@@ -128,10 +142,23 @@ class StereoProcess {
         slam_.focal_y = focal_y;
         slam_.cx = cx;
         slam_.cy = cy;
+        if (BRIEF_FLAG) {
+            briefStereoTriangulate(im1, im2, out3d);
+            return;
+        }
         std::vector<Point2f> pts2d;
         slam_.stereoTriangulate(im1, im2, out3d, pts2d);
         tri3dPoints = out3d;
         color3dMap = slam_.colors;
+    }
+    // brief->compute(img, keypoints, desc) on one image: the key points runByImageBorder(28) removes are erased from
+    // `keypoints`, desc holds briefBytes bytes per remaining key point
+    void briefFeatures(const Mat &img, std::vector<KeyPoint> &keypoints, std::vector<uint8_t> &desc)
+    {
+        const Mat *imgs[1] = {&img};
+        std::vector<uint8_t> d[1];
+        briefFeaturesBatch(imgs, 1, &keypoints, d);
+        desc.swap(d[0]);
     }
 
     // include/stereoCV.h:66, src/StereoCV.cpp:123-188: two-view monocular reconstruction.  The reference matches SIFT
@@ -209,6 +236,7 @@ class StereoProcess {
     static const float *fp(const std::vector<Point2f> &v) { return reinterpret_cast<const float *>(v.data()); }
     static float *fpm(std::vector<Point2f> &v) { return reinterpret_cast<float *>(v.data()); }
     // n images of one size through one svo_sift_extract_batch call
+    // (desc == nullptr: detect only)
     void siftFeaturesBatch(const Mat *const *imgs, int n, int nfeatures, std::vector<KeyPoint> *kps, std::vector<float> *desc)
     {
         const Mat &first = *imgs[0];
@@ -225,10 +253,10 @@ class StereoProcess {
         svo_sift_default_params(&prm);
         prm.n_features = nfeatures;
         const size_t cap = (size_t)(siftCapacity > 0 ? siftCapacity : 1), e = cap * (size_t)n;
-        std::vector<float> xy(2 * e), size(e), angle(e), resp(e), d(128 * e);
+        std::vector<float> xy(2 * e), size(e), angle(e), resp(e), d(desc ? 128 * e : 0);
         std::vector<int> oct(e), cnt((size_t)n);
         check(svo_sift_extract_batch(ctx(), ptrs, n, mat_cols(first), mat_rows(first), mat_channels(first), &prm, (int)cap,
-                                     xy.data(), size.data(), angle.data(), resp.data(), oct.data(), d.data(), cnt.data(),
+                                     xy.data(), size.data(), angle.data(), resp.data(), oct.data(), desc ? d.data() : nullptr, cnt.data(),
                                      SVO_MEM_HOST));
         for (int i = 0; i < n; i++) {
             const size_t b = cap * (size_t)i, m = (size_t)cnt[(size_t)i];
@@ -241,8 +269,105 @@ class StereoProcess {
                 k.response = resp[b + j];
                 k.octave = oct[b + j];
             }
-            desc[i].assign(d.begin() + 128 * b, d.begin() + 128 * (b + m));
+            if (desc)
+                desc[i].assign(d.begin() + 128 * b, d.begin() + 128 * (b + m));
         }
+    }
+    // n images of one size through one svo_brief_describe_batch call; kps[i] loses the key points the border filter removes
+    void briefFeaturesBatch(const Mat *const *imgs, int n, std::vector<KeyPoint> *kps, std::vector<uint8_t> *desc)
+    {
+        const Mat &first = *imgs[0];
+        const uint8_t *ptrs[16];
+        if (n < 1 || n > 16)
+            throw SvoError(SVO_ERR_ARG, "briefFeatures: 1 ... 16 images per call");
+        size_t cap = 1;
+        for (int i = 0; i < n; i++) {
+            if (mat_cols(*imgs[i]) != mat_cols(first) || mat_rows(*imgs[i]) != mat_rows(first) ||
+                mat_channels(*imgs[i]) != mat_channels(first))
+                throw SvoError(SVO_ERR_ARG, "briefFeatures: the images differ in size");
+            ptrs[i] = mat_data(*imgs[i]);
+            cap = kps[i].size() > cap ? kps[i].size() : cap;
+        }
+        const size_t nb = (size_t)briefBytes, e = cap * (size_t)n;
+        std::vector<float> xy(2 * e);
+        std::vector<int> n_in((size_t)n), n_out((size_t)n), kept(e);
+        std::vector<uint8_t> d(e * (nb > 0 ? nb : 1));
+        for (int i = 0; i < n; i++) {
+            n_in[(size_t)i] = (int)kps[i].size();
+            for (size_t j = 0; j < kps[i].size(); j++) {
+                xy[2 * (cap * i + j)] = kps[i][j].pt.x;
+                xy[2 * (cap * i + j) + 1] = kps[i][j].pt.y;
+            }
+        }
+        check(svo_brief_describe_batch(ctx(), ptrs, n, mat_cols(first), mat_rows(first), mat_channels(first), briefBytes, xy.data(),
+                                       n_in.data(), (int)cap, kept.data(), d.data(), n_out.data(), SVO_MEM_HOST));
+        for (int i = 0; i < n; i++) {
+            const size_t b = cap * (size_t)i, m = (size_t)n_out[(size_t)i];
+            std::vector<KeyPoint> stay(m);
+            for (size_t j = 0; j < m; j++)
+                stay[j] = kps[i][(size_t)kept[b + j]];
+            kps[i].swap(stay);
+            desc[i].assign(d.begin() + nb * b, d.begin() + nb * (b + m));
+        }
+    }
+    // src/StereoCV.cpp:64-121
+    void briefStereoTriangulate(const Mat &im1, const Mat &im2, std::vector<Point3f> &out3d)
+    {
+        out3d.clear();
+        tri3dPoints.clear();
+        color3dMap.clear();
+        stereoPairs1.clear();
+        stereoPairs2.clear();
+        stereoInliers1.clear();
+        stereoInliers2.clear();
+        const Mat *imgs[2] = {&im1, &im2};
+        std::vector<KeyPoint> kps[2];
+        siftFeaturesBatch(imgs, 2, siftFeaturesStereo, kps, nullptr);
+        std::vector<uint8_t> desc[2];
+        briefFeaturesBatch(imgs, 2, kps, desc);
+        const int n1 = (int)kps[0].size(), n2 = (int)kps[1].size();
+        if (n1 == 0 || n2 == 0)
+            return;
+        std::vector<Point2f> xy1, xy2;
+        for (const KeyPoint &k : kps[0])
+            xy1.emplace_back(k.pt);
+        for (const KeyPoint &k : kps[1])
+            xy2.emplace_back(k.pt);
+        const int qo[2] = {0, n1}, to[2] = {0, n2};
+        std::vector<int> idx((size_t)n1 * 2);
+        std::vector<float> dist((size_t)n1 * 2);
+        check(svo_knn_match(ctx(), SVO_MATCH_L2_U8, desc[0].data(), desc[1].data(), briefBytes, qo, to, 1, 2, idx.data(), dist.data(),
+                            SVO_MEM_HOST));
+        std::vector<Point2f> pt1((size_t)n1), pt2((size_t)n1);
+        int cnt = 0;
+        check(svo_ratio_pairs(ctx(), idx.data(), dist.data(), n1, 2, 0.8, fp(xy1), fp(xy2), fpm(pt1), fpm(pt2), nullptr, &cnt,
+                              SVO_MEM_HOST));
+        pt1.resize((size_t)cnt);
+        pt2.resize((size_t)cnt);
+        stereoPairs1 = pt1;
+        stereoPairs2 = pt2;
+        if (cnt < 8)
+            return;
+        slam_.FmatThresholding(pt1, pt2);
+        stereoInliers1 = pt1;
+        stereoInliers2 = pt2;
+        const int n = (int)pt1.size();
+        if (n == 0)
+            return;
+        double P1[12], P2[12];
+        check(svo_stereo_projections(focal_x, focal_y, cx, cy, baseline, P1, P2));
+        out3d.assign((size_t)n, Point3f());
+        check(svo_triangulate(ctx(), P1, P2, fp(pt1), fp(pt2), n, reinterpret_cast<float *>(out3d.data()), nullptr, SVO_MEM_HOST));
+        // getColors(im1, inlier1), include/monoUtils.h:180-193
+        color3dMap.assign((size_t)n, Point3f());
+        svo_pyramid *p = nullptr;
+        check(svo_pyramid_create(ctx(), mat_cols(im1), mat_rows(im1), mat_channels(im1), 1, &p));
+        int rc = svo_pyramid_build(ctx(), p, mat_data(im1), SVO_MEM_HOST);
+        if (rc == SVO_OK)
+            rc = svo_get_colors(ctx(), p, fp(pt1), n, reinterpret_cast<float *>(color3dMap.data()), SVO_MEM_HOST);
+        svo_pyramid_destroy(ctx(), p);
+        check(rc);
+        tri3dPoints = out3d;
     }
     // src/StereoCV.cpp:123-147: SIFT(10000) on both images, knnMatch(desc1, desc2, 2), m.distance < 0.8 * n.distance
     void siftRatioPairs(const Mat &im1, const Mat &im2, std::vector<Point2f> &pt1, std::vector<Point2f> &pt2)

@@ -26,7 +26,7 @@ SVO_ERR_NO_DEVICE = -4
 SVO_ERR_TRACKING_LOST = -5
 SVO_ERR_STATE = -6
 MEM_HOST, MEM_DEVICE = 0, 1
-K_PYRAMID, K_LK, K_FRANSAC, K_TRIANGULATE, K_PNP, K_POSEGRAPH, K_ANMS = range(7)
+K_PYRAMID, K_LK, K_FRANSAC, K_TRIANGULATE, K_PNP, K_POSEGRAPH, K_ANMS, K_BRIEF_INTEGRAL, K_BRIEF_DESCRIBE = range(9)
 
 
 class SvoError(RuntimeError):
@@ -607,6 +607,76 @@ def sift_pyramid(self, image, params=None):
         dog.append(d[b:b + px[o] * (nl + 2)].reshape(nl + 2, oh[o], ow[o]))
         a, b = a + px[o] * (nl + 3), b + px[o] * (nl + 2)
     return gauss, dog
+
+
+def brief_default_pattern(bytes=32) -> np.ndarray:
+    """``svo_brief_default_pattern``: the library's own test table of a descriptor length, [8 * bytes, 4] int8 rows of
+    (y1, x1, y2, x2).  Host only."""
+    pat = np.zeros((8 * max(int(bytes), 0), 4), np.int8)
+    _check(load().svo_brief_default_pattern(int(bytes), _ptr(pat) if pat.size else None))
+    return pat
+
+
+@_ctx_method
+def brief_set_pattern(self, pattern=None, bytes=32):
+    """``svo_brief_set_pattern``: the test table of one descriptor length (cv's generated_NN.i where a host has it); None = the
+    default."""
+    if pattern is None:
+        _check(self.lib.svo_brief_set_pattern(self._h, int(bytes), None))
+        return
+    pat = np.ascontiguousarray(pattern, np.int8).reshape(8 * int(bytes), 4)
+    _check(self.lib.svo_brief_set_pattern(self._h, int(bytes), _ptr(pat)))
+
+
+@_ctx_method
+def brief_describe(self, images, xy_list, bytes=32):
+    """``svo_brief_describe_batch``: 1 ... 16 images of one size and the key points of each ([n, 2] float32; host arrays, or device
+    tensors when the images are) in one set of launches -> per image (desc [m, bytes] uint8, kept_index [m] int32), host arrays:
+    the descriptors of the key points runByImageBorder keeps and their indices into the image's list, in order."""
+    nimg = len(images)
+    assert nimg == len(xy_list)
+    w, h, c = _image_shape(images[0])
+    n_in = (C.c_int * max(nimg, 1))(*[int(len(xy)) for xy in xy_list])
+    n_out = (C.c_int * max(nimg, 1))()
+    cap = max([1] + [int(len(xy)) for xy in xy_list])
+    nb = int(bytes)
+    dev = _is_device(images[0])
+    if dev:
+        import torch
+
+        device = images[0].device
+        images = [im.contiguous() for im in images]
+        xy = torch.zeros((nimg, cap, 2), dtype=torch.float32, device=device)
+        for i, p in enumerate(xy_list):
+            if len(p):
+                xy[i, :len(p)] = torch.as_tensor(p, dtype=torch.float32, device=device).reshape(-1, 2)
+        kept = torch.zeros((nimg, cap), dtype=torch.int32, device=device)
+        desc = torch.zeros((nimg, cap, max(nb, 1)), dtype=torch.uint8, device=device)
+        torch.cuda.synchronize(device)
+    else:
+        images = [np.ascontiguousarray(im, np.uint8) for im in images]
+        xy = np.zeros((nimg, cap, 2), np.float32)
+        for i, p in enumerate(xy_list):
+            if len(p):
+                xy[i, :len(p)] = np.asarray(p, np.float32).reshape(-1, 2)
+        kept, desc = np.zeros((nimg, cap), np.int32), np.zeros((nimg, cap, max(nb, 1)), np.uint8)
+    ptrs = (C.c_void_p * max(nimg, 1))(*[_ptr(im).value for im in images])
+    _check(self.lib.svo_brief_describe_batch(self._h, ptrs, nimg, w, h, c, nb, _ptr(xy), n_in, cap, _ptr(kept), _ptr(desc), n_out,
+                                             MEM_DEVICE if dev else MEM_HOST))
+    if dev:
+        _check(self.lib.svo_ctx_sync(self._h))
+        kept, desc = kept.cpu().numpy(), desc.cpu().numpy()
+    return [(desc[i, :n_out[i]].copy(), kept[i, :n_out[i]].copy()) for i in range(nimg)]
+
+
+@_ctx_method
+def brief_integral(self, image) -> np.ndarray:
+    """``svo_brief_integral`` (diagnostics) -> the [h + 1, w + 1] int32 integral image of the grey image (host arrays)."""
+    img = np.ascontiguousarray(image, np.uint8)
+    w, h, c = _image_shape(img)
+    out = np.zeros((h + 1, w + 1), np.int32)
+    _check(self.lib.svo_brief_integral(self._h, _ptr(img), w, h, c, _ptr(out), MEM_HOST))
+    return out
 
 
 @_ctx_method

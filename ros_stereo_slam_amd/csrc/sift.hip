@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void sift_init_kernel(SiftImages im, int w, in
         const size_t i = (size_t)y * w + x;
         if (c == 1)
             return (float)img[i];
-        return (float)((1868 * img[3 * i] + 9617 * img[3 * i + 1] + 4899 * img[3 * i + 2] + 8192) >> 14);
+        return (float)svo_bgr2gray(img[3 * i], img[3 * i + 1], img[3 * i + 2]);
     };
     const float t0 = grey(y0, x0) * a0 + grey(y0, x1) * a1;
     const float t1 = grey(y1, x0) * a0 + grey(y1, x1) * a1;

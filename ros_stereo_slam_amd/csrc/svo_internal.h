@@ -29,6 +29,9 @@ void svo_set_error(const char *fmt, ...);
 // priority instead (s_setprio: the arbiter picks the highest-priority ready wave); the tracker stays at 0.
 __device__ __forceinline__ void svo_chain_priority() { __builtin_amdgcn_s_setprio(3); }
 
+// cvtColor(BGR2GRAY) of one 8-bit pixel: OpenCV's fixed-point weights, one rounding
+__host__ __device__ __forceinline__ int svo_bgr2gray(int b, int g, int r) { return (1868 * b + 9617 * g + 4899 * r + 8192) >> 14; }
+
 #define SVO_HIP(call)                                                                         \
     do {                                                                                      \
         hipError_t e_ = (call);                                                               \
@@ -137,6 +140,13 @@ struct svo_ctx {
     // sift.hip: the scale space (Gaussian and DoG layers of every image of a batch), the detector's work arrays, staged
     // images and key points, the output block of host calls
     DevBuf sift_pyr, sift_work, sift_img, sift_out;
+    // brief.hip: the integral images of a batch, staged images, the filter's and the descriptor kernel's work arrays, the test
+    // tables on the device (three slots of 2048 bytes: 16 / 32 / 64-byte descriptors); brief_pattern: the tables set through
+    // svo_brief_set_pattern (brief_has_pattern[k] == 0: the default), brief_pat_live[k]: slot k of brief_pat holds the current table
+    DevBuf brief_sum, brief_img, brief_work, brief_pat;
+    int8_t brief_pattern[3][2048];
+    int brief_has_pattern[3] = {0, 0, 0};
+    int brief_pat_live[3] = {0, 0, 0};
 };
 
 // Low-latency host wait for everything queued on the context's stream: records an event and
