@@ -305,6 +305,60 @@ int svo_brief_describe_batch(svo_ctx *ctx, const uint8_t *const *images, int n_i
                              const float *xy, const int *n_in, int cap, int *kept_index, uint8_t *desc, int *n_out, int mem);
 int svo_brief_integral(svo_ctx *ctx, const uint8_t *image, int w, int h, int c, int32_t *sum, int mem);
 
+/* ---- SURF: detection and descriptors of OpenCV 3.2's xfeatures2d::SURF (src/bundleAdjust.cpp:236-317, include/trangulation.h:32-61) ----
+ * The older pipeline pairs features by SURF::create(500) -> detect / compute -> BFMatcher().knnMatch(2) -> ratio 0.8 ->
+ * triangulatePoints; svo_surf_extract_batch produces the features, svo_knn_match (SVO_MATCH_L2_F32, dim 64) and svo_ratio_pairs
+ * consume them.  The algorithm is the one tests/surf_numpy.py states operation by operation: the int32
+ * integral image of the grey image, for octave o and layer l (0 ... n_octave_layers + 1) the box-filter Hessian of size
+ * (9 + 6 l) << o sampled every 1 << o pixels (det = dxx dyy - 0.81 dxy^2, trace = dxx + dyy), maxima of the middle layers above the
+ * threshold and their 26 neighbours, the 3 x 3 x 3 interpolation, the dominant orientation from 113 Haar samples in a 60 degree
+ * window moved in steps of 5 degrees, the 64-float descriptor from the rotated window of (int)(21 s) pixels a side (s = size * 1.2
+ * / 9) reduced to 21 x 21 by area averaging.  Transcendentals are svo_exp / svo_cos / svo_sin of svo_math.h and OpenCV's fastAtan2
+ * polynomial; every float sum has a stated order, so the result does not depend on how lanes are scheduled.
+ *
+ * Output: key points in KeypointGreater's order (response descending, then size, octave, y descending, x ascending), remaining ties
+ * by ascending (octave, layer, row, column) of the sample: a total order.  xy, size: pixels (KeyPoint::pt, KeyPoint::size); angle:
+ * degrees in [0, 360) (270 with upright); response: the determinant; octave: 0 ... n_octaves - 1; laplacian: KeyPoint::class_id, the
+ * sign of the trace (-1, 0, 1); desc: 64 floats per key point, unit norm.  A key point whose orientation wavelet does not fit the
+ * image, or that has no orientation sample inside it, is dropped, as upstream drops it.
+ *
+ * svo_surf_extract_batch: n_images (1 ... 16) images of one size, w x h x c bytes each (c = 1, or 3 = BGR, converted with
+ * cvtColor's integer weights); every output array holds n_images x cap entries, image i's at i * cap, n[i] of them valid; desc may
+ * be NULL (detect only).  images: a host array of host or device pointers according to mem; n: HOST ints in both modes -- the
+ * call waits once, for the counts.  SVO_ERR_ARG: null or misaligned (4 bytes) pointers, c not 1 or 3, n_octaves or n_octave_layers
+ * outside 1 ... 8, a negative or non-finite hessian_threshold, extended != 0 (the 128-float descriptor is not provided), w or h
+ * below 1 or above 16384, 255 w h > 2^31 - 1 (the int32 integral image could overflow), cap < 1, n_images outside 1 ... 16; nothing
+ * is written then.  SVO_ERR_CAPACITY, two cases: (a) an image yields more than cap key points -- every n[i] holds the needed count
+ * and the first min(n[i], cap) key points of each image are valid; (b) an image has more than 65536 key points (the work arrays)
+ * -- the call returns at that image: the output arrays are left untouched (host memory) or unspecified (device memory), and n[] is
+ * written only up to and including that image.  A batch returns the same bits as one call per image, host memory the same as
+ * device memory.  There is no CPU fallback.
+ *
+ * svo_surf_describe: detector->compute(image, keypoints, desc) for n key points that came from elsewhere (xy, size): angle_out,
+ * desc (64 floats each) and kept (1 / 0) per key point, in the input order.  A key point that upstream would drop (see above), one
+ * whose position is not finite or beyond +-65536, or whose window (int)(21 s) is not in 21 ... 65536, has kept 0, angle -1 and a zero
+ * descriptor.  On the key points svo_surf_extract_batch returned it gives the same angles and descriptors.
+ *
+ * svo_surf_layers (diagnostics: the parity tests compare every plane with the restatement): the det and trace planes of one image,
+ * octave after octave, n_octave_layers + 2 planes of (h >> o) x (w >> o) floats each; svo_surf_layers_layout gives, per plane, the
+ * filter size, the sample step and the plane's width and height (n_octaves * (n_octave_layers + 2) ints each, any may be NULL). */
+typedef struct svo_surf_params {
+    double hessian_threshold;  /* 100; the reference: 500 / 1200 */
+    int n_octaves;             /* 4 */
+    int n_octave_layers;       /* 3 */
+    int extended;              /* 0; anything else is refused */
+    int upright;               /* 0 */
+} svo_surf_params;
+void svo_surf_default_params(svo_surf_params *p);
+int svo_surf_extract_batch(svo_ctx *ctx, const uint8_t *const *images, int n_images, int w, int h, int c,
+                           const svo_surf_params *prm, int cap, float *xy, float *size, float *angle, float *response, int *octave,
+                           int *laplacian, float *desc, int *n, int mem);
+int svo_surf_describe(svo_ctx *ctx, const uint8_t *image, int w, int h, int c, const svo_surf_params *prm, const float *xy,
+                      const float *size, int n, float *angle_out, float *desc, uint8_t *kept, int mem);
+int svo_surf_layers(svo_ctx *ctx, const uint8_t *image, int w, int h, int c, const svo_surf_params *prm, float *det, float *trace,
+                    int mem);
+int svo_surf_layers_layout(int w, int h, int n_octaves, int n_octave_layers, int *sizes, int *steps, int *lw, int *lh);
+
 /* ---- two-view monocular geometry: StereoProcess::monocularTriangulate, src/StereoCV.cpp:123-188 ---- */
 /* OpenCV 3.2's five-point solver (EMEstimatorCallback::runKernel, Nister's method) on nsamples
  * independent 5-samples of NORMALISED double coordinates: x1n / x2n nsamples x 5 x 2, x2^T E x1 = 0.

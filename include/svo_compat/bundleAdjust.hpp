@@ -3,6 +3,9 @@
 // lists it only in a comment) on top of the C ABI, with the reference's names and argument meaning.
 #pragma once
 
+#include <cstdio>
+
+#include "surf.hpp"
 #include "types.hpp"
 
 namespace svo_compat {
@@ -12,6 +15,10 @@ class visualOdometry {
     int baIterations = 10;  // optimizer.optimize(10), src/bundleAdjust.cpp:606
     // what the last BundleAdjust3d2d did: chi2 before / after, final lambda, iterations, trials
     double lastInfo[5] = {0, 0, 0, 0, 0};
+    // ---- the stereo side of the class (src/bundleAdjust.cpp:30-60, 236-317, 384-404) ----
+    double baseline = 0.54;
+    Mat K;                  // 3x3 CV_64F; stereoTriangulate reads K(0,0), K(1,1), K(0,2), K(1,2), as BundleAdjust3d2d does
+    int surfHessian = 500;  // xfeatures2d::SURF::create(500), src/bundleAdjust.cpp:240
 
     explicit visualOdometry(svo_ctx *ctx = nullptr) : ctx_(ctx ? ctx : shared_context()) {}
 
@@ -31,6 +38,55 @@ class visualOdometry {
                           baIterations, nullptr, nullptr, lastInfo, SVO_MEM_HOST));
         for (int i = 0; i < 3; i++)  // eigen2cv(trans, t): t keeps its 3x1 shape
             (t.rows == 3 ? t.at<double>(i, 0) : t.at<double>(0, i)) = tv(i);
+    }
+
+    // detector->detect(img, kps) + detector->compute(img, kps, desc) with SURF::create(surfHessian): 64 floats per key point
+    void surfFeatures(const Mat &img, std::vector<KeyPoint> &kps, std::vector<float> &desc)
+    {
+        const Mat *imgs[1] = {&img};
+        surf_features_batch(ctx_, imgs, 1, (double)surfHessian, &kps, &desc);
+    }
+
+    // src/bundleAdjust.cpp:236-317: SURF on both images, knnMatch(2), ratio 0.8, triangulatePoints with K[I|0] and
+    // K[I|(-baseline, 0, 0)], dehomogenised in float.  No F-matrix filter: upstream has none here.  The drawing
+    // (drawDeltas, :306-313) is display code and is left out.
+    void stereoTriangulate(Mat im1, Mat im2, std::vector<Point3f> &ref3dPts, std::vector<Point2f> &ref2dPts)
+    {
+        if (mat_data(im1) == nullptr || mat_data(im2) == nullptr) {
+            std::printf("NULL IMG\n");  // :242-245
+            return;
+        }
+        const Mat33d Km = mat33_of(K);
+        std::vector<Point2f> pt1, pt2;
+        surf_ratio_pairs(ctx_, im1, im2, (double)surfHessian, pt1, pt2);
+        std::vector<Point3f> pts3d(pt1.size());
+        if (!pt1.empty()) {
+            double P1[12], P2[12];
+            check(svo_stereo_projections(Km(0, 0), Km(1, 1), Km(0, 2), Km(1, 2), baseline, P1, P2));
+            check(svo_triangulate(ctx_, P1, P2, reinterpret_cast<const float *>(pt1.data()), reinterpret_cast<const float *>(pt2.data()),
+                                  (int)pt1.size(), reinterpret_cast<float *>(pts3d.data()), nullptr, SVO_MEM_HOST));
+        }
+        ref3dPts = pts3d;
+        ref2dPts = pt1;
+    }
+
+    // src/bundleAdjust.cpp:384-404: the new pair's points through the 3x4 CV_64F inv_transform.  Upstream writes the three rows
+    // out in double and stores floats; svo_transform_points is that arithmetic (the kernel of update3dtransformation), used here.
+    // `start` is not read upstream either.
+    void relocalizeFrames(int start, Mat imL, Mat imR, Mat &inv_transform, std::vector<Point2f> &ftrPts, std::vector<Point3f> &pts3d)
+    {
+        (void)start;
+        std::vector<Point2f> new2d;
+        std::vector<Point3f> new3d;
+        ftrPts.clear();
+        pts3d.clear();
+        stereoTriangulate(imL, imR, new3d, new2d);
+        const Mat34d T = mat34_of(inv_transform);
+        pts3d.assign(new3d.size(), Point3f());
+        if (!new3d.empty())
+            check(svo_transform_points(ctx_, T.m, reinterpret_cast<const float *>(new3d.data()), (int)new3d.size(),
+                                       reinterpret_cast<float *>(pts3d.data()), SVO_MEM_HOST));
+        ftrPts = new2d;
     }
 
   private:

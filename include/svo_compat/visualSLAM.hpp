@@ -21,6 +21,7 @@
 #include <cstdio>
 
 #include "poseGraph.hpp"
+#include "surf.hpp"
 #include "types.hpp"
 
 namespace svo_compat {
@@ -45,6 +46,10 @@ class visualSLAM {
     // Only the stage method reads it: processFrame's fused svo_vo_* runner is dense-only.
     bool DENSE_FLAG = true;
     int orbFeatures = 1000;         // ORB::create(1000), src/triangulation.cpp:105
+    // with DENSE_FLAG == false: true = the sparse branch as include/trangulation.h:32-61 writes it, SURF::create(surfHessian)
+    // in ORB's place
+    bool SURF_FLAG = false;
+    int surfHessian = 1200;
     double focal_x = 7.188560000000e+02, cx = 6.071928000000e+02;
     double focal_y = 7.188560000000e+02, cy = 1.852157000000e+02;
     int gridStep = 30;              // src/triangulation.cpp:89
@@ -134,6 +139,10 @@ class visualSLAM {
                 refPts.emplace_back(k.pt);
             denseLKtracking(im1, im2, refPts, trkPts);
             FmatThresholding(refPts, trkPts);
+        } else if (SURF_FLAG) {
+            if (mat_cols(im1) != mat_cols(im2) || mat_rows(im1) != mat_rows(im2) || mat_channels(im1) != mat_channels(im2))
+                throw SvoError(SVO_ERR_ARG, "stereoTriangulate: the two images differ in size");
+            surf_ratio_pairs(ctx_, im1, im2, (double)surfHessian, refPts, trkPts);
         } else {
             orbRatioPairs(im1, im2, refPts, trkPts);  // no FmatThresholding in this branch, as upstream
         }

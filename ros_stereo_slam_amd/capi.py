@@ -679,6 +679,118 @@ def brief_integral(self, image) -> np.ndarray:
     return out
 
 
+class SurfParams(C.Structure):
+    """``svo_surf_params``: cv::xfeatures2d::SURF::create's arguments (extended must stay 0)."""
+    _fields_ = [("hessian_threshold", C.c_double), ("n_octaves", C.c_int), ("n_octave_layers", C.c_int), ("extended", C.c_int),
+                ("upright", C.c_int)]
+
+
+def surf_params(**overrides) -> SurfParams:
+    p = SurfParams()
+    load().svo_surf_default_params(C.byref(p))
+    for k, v in overrides.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def _surf_prm(params) -> SurfParams:
+    return params if isinstance(params, SurfParams) else surf_params(**(params or {}))
+
+
+@_ctx_method
+def surf_extract(self, images, params=None, cap=20000, descriptors=True):
+    """``svo_surf_extract_batch``: 1 ... 16 images of one size (host arrays or device tensors) in one set of launches -> per
+    image (xy [n, 2], size [n], angle [n], response [n] float32, octave [n], laplacian [n] int32, desc [n, 64] float32 or
+    None), host arrays in the recipe's order.  More than ``cap`` key points in an image: SvoError(SVO_ERR_CAPACITY) whose
+    ``needed`` lists the counts and whose ``prefix`` holds the first ``cap`` key points of every image."""
+    prm = _surf_prm(params)
+    nimg = len(images)
+    w, h, c = _image_shape(images[0])
+    n = (C.c_int * max(nimg, 1))()
+    e = nimg * cap
+    dev = _is_device(images[0])
+    if dev:
+        import torch
+
+        images = [im.contiguous() for im in images]
+        fb = torch.zeros(e * (5 + (64 if descriptors else 0)), dtype=torch.float32, device=images[0].device)
+        ob = torch.zeros(2 * e, dtype=torch.int32, device=images[0].device)
+        torch.cuda.synchronize(images[0].device)
+        base, ibase = fb.data_ptr(), ob.data_ptr()
+        args = [C.c_void_p(base + 4 * k * e) for k in (0, 2, 3, 4)] + [C.c_void_p(ibase), C.c_void_p(ibase + 4 * e),
+                                                                    C.c_void_p(base + 20 * e if descriptors else 0)]
+    else:
+        images = [np.ascontiguousarray(im, np.uint8) for im in images]
+        xy, size, angle = np.zeros((nimg, cap, 2), np.float32), np.zeros((nimg, cap), np.float32), np.zeros((nimg, cap), np.float32)
+        resp, octv, lap = np.zeros((nimg, cap), np.float32), np.zeros((nimg, cap), np.int32), np.zeros((nimg, cap), np.int32)
+        desc = np.zeros((nimg, cap, 64), np.float32) if descriptors else None
+        args = [_ptr(xy), _ptr(size), _ptr(angle), _ptr(resp), _ptr(octv), _ptr(lap), _ptr(desc)]
+    ptrs = (C.c_void_p * max(nimg, 1))(*[_ptr(im).value for im in images])
+    rc = self.lib.svo_surf_extract_batch(self._h, ptrs, nimg, w, h, c, C.byref(prm), cap, *args, n, MEM_DEVICE if dev else MEM_HOST)
+    if rc not in (SVO_OK, SVO_ERR_CAPACITY):
+        raise SvoError(rc, self.lib.svo_last_error().decode(errors="replace"))
+    msg = self.lib.svo_last_error().decode(errors="replace") if rc else ""
+    if dev:
+        _check(self.lib.svo_ctx_sync(self._h))
+        hb, ib = fb.cpu().numpy(), ob.cpu().numpy()
+        octv, lap = ib[:e].reshape(nimg, cap), ib[e:].reshape(nimg, cap)
+        xy, size = hb[:2 * e].reshape(nimg, cap, 2), hb[2 * e:3 * e].reshape(nimg, cap)
+        angle, resp = hb[3 * e:4 * e].reshape(nimg, cap), hb[4 * e:5 * e].reshape(nimg, cap)
+        desc = hb[5 * e:].reshape(nimg, cap, 64) if descriptors else None
+    m = [min(n[i], cap) for i in range(nimg)]
+    out = [(xy[i, :m[i]].copy(), size[i, :m[i]].copy(), angle[i, :m[i]].copy(), resp[i, :m[i]].copy(), octv[i, :m[i]].copy(),
+            lap[i, :m[i]].copy(), desc[i, :m[i]].copy() if descriptors else None) for i in range(nimg)]
+    if rc != SVO_OK:
+        err = SvoError(rc, msg)
+        err.needed = list(n[:nimg])
+        err.prefix = out
+        raise err
+    return out
+
+
+@_ctx_method
+def surf_describe(self, image, xy, size, params=None):
+    """``svo_surf_describe``: detector->compute(image, keypoints) -> (angle [n] float32, desc [n, 64] float32, kept [n] uint8);
+    host arrays in and out."""
+    prm = _surf_prm(params)
+    img = np.ascontiguousarray(image, np.uint8)
+    w, h, c = _image_shape(img)
+    xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+    size = np.ascontiguousarray(size, np.float32).reshape(-1)
+    assert len(size) == len(xy)
+    angle, desc, kept = np.zeros(len(xy), np.float32), np.zeros((len(xy), 64), np.float32), np.zeros(len(xy), np.uint8)
+    _check(self.lib.svo_surf_describe(self._h, _ptr(img), w, h, c, C.byref(prm), _ptr(xy), _ptr(size), len(xy), _ptr(angle),
+                                      _ptr(desc), _ptr(kept), MEM_HOST))
+    return angle, desc, kept
+
+
+def surf_layers_layout(w, h, n_octaves=4, n_octave_layers=3):
+    """``svo_surf_layers_layout`` -> (sizes, steps, lw, lh), one int per layer, octave after octave.  Host only."""
+    m = max(n_octaves * (n_octave_layers + 2), 1)
+    arr = [(C.c_int * m)() for _ in range(4)]
+    _check(load().svo_surf_layers_layout(w, h, n_octaves, n_octave_layers, *arr))
+    return tuple(list(a) for a in arr)
+
+
+@_ctx_method
+def surf_layers(self, image, params=None):
+    """``svo_surf_layers`` (diagnostics) -> (det, trace): one float32 plane per layer, octave after octave."""
+    prm = _surf_prm(params)
+    img = np.ascontiguousarray(image, np.uint8)
+    w, h, c = _image_shape(img)
+    _, _, lw, lh = surf_layers_layout(w, h, prm.n_octaves, prm.n_octave_layers)
+    total = sum(a * b for a, b in zip(lw, lh))
+    d, t = np.zeros(max(total, 1), np.float32), np.zeros(max(total, 1), np.float32)
+    _check(self.lib.svo_surf_layers(self._h, _ptr(img), w, h, c, C.byref(prm), _ptr(d), _ptr(t), MEM_HOST))
+    det, trace, a = [], [], 0
+    for pw, ph in zip(lw, lh):
+        det.append(d[a:a + pw * ph].reshape(ph, pw))
+        trace.append(t[a:a + pw * ph].reshape(ph, pw))
+        a += pw * ph
+    return det, trace
+
+
 @_ctx_method
 def sor_filter(self, xyz, color=None, mean_k=200, stddev_mul=0.01, z_limit=500.0):
     """visualSLAM::SORcloud (src/rosFuncs.cpp:9-39) -> (xyz_kept, color_kept or None, mean_dist)."""

@@ -20,84 +20,18 @@
 
 namespace {
 
-constexpr int BRIEF_MAXBATCH = 16, BRIEF_BORDER = 28, BRIEF_HALF_PATCH = 24;
+#include "integral_scan.hip.h"
+
+constexpr int BRIEF_MAXBATCH = INTEGRAL_MAXBATCH, BRIEF_BORDER = 28, BRIEF_HALF_PATCH = 24;
 constexpr int BRIEF_WAVES = 4;       // key points a workgroup of the descriptor kernel works on at a time
 constexpr int BRIEF_MAXGRID = 2048;  // its workgroups per image: 8 per CU, each wave walks on with that stride
 
-struct BriefImages {
-    const uint8_t *img[BRIEF_MAXBATCH];
-};
+using BriefImages = IntegralImages;
 struct BriefCounts {
     int n[BRIEF_MAXBATCH];
 };
 
-// ---- 1. integral image (B2, B3) ----
-// row y of the image -> row y + 1 of the table, as running sums along the row; column 0 and row 0 are zero
-__global__ __launch_bounds__(256) void brief_row_scan_kernel(BriefImages im, int w, int h, int c, int *__restrict__ sum_all,
-                                                             long long img_stride)
-{
-    __shared__ int wave_total[4];
-    const int y = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint8_t *__restrict__ row = im.img[blockIdx.y] + (size_t)y * w * c;
-    int *__restrict__ out = sum_all + blockIdx.y * img_stride + (size_t)(y + 1) * (w + 1);
-    if (threadIdx.x == 0)
-        out[0] = 0;
-    if (y == 0)
-        for (int x = threadIdx.x; x <= w; x += 256)
-            out[x - (w + 1)] = 0;
-    int carry = 0;
-    for (int x0 = 0; x0 < w; x0 += 256) {
-        const int x = x0 + threadIdx.x;
-        int v = 0;
-        if (x < w)
-            v = c == 1 ? (int)row[x] : svo_bgr2gray(row[3 * x], row[3 * x + 1], row[3 * x + 2]);
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(v, o);
-            if (lane >= o)
-                v += t;
-        }
-        if (lane == 63)
-            wave_total[wave] = v;
-        __syncthreads();
-        int before = carry, all = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            before += k < wave ? wave_total[k] : 0;
-            all += wave_total[k];
-        }
-        if (x < w)
-            out[x + 1] = v + before;
-        carry += all;
-        __syncthreads();
-    }
-}
-
-// a thread per column 1 ... w: rows added up from the top; eight rows' loads are in flight before the first add
-__global__ __launch_bounds__(64) void brief_col_scan_kernel(int w, int h, int *__restrict__ sum_all, long long img_stride)
-{
-    const int x = blockIdx.x * 64 + threadIdx.x + 1;
-    if (x > w)
-        return;
-    const size_t pitch = (size_t)w + 1;
-    int *__restrict__ p = sum_all + blockIdx.y * img_stride + pitch + x;
-    int acc = 0, y = 0;
-    for (; y + 8 <= h; y += 8) {
-        int v[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++)
-            v[k] = p[(size_t)(y + k) * pitch];
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            acc += v[k];
-            p[(size_t)(y + k) * pitch] = acc;
-        }
-    }
-    for (; y < h; y++) {
-        acc += p[(size_t)y * pitch];
-        p[(size_t)y * pitch] = acc;
-    }
-}
+// ---- 1. integral image (B2, B3): integral_scan.hip.h ----
 
 // ---- 2. key-point filter (B4, OURS-1) ----
 // mask[i] = 1 for a key point that stays, iota[i] = i (the compaction carries it along as kept_index)
@@ -194,7 +128,7 @@ int brief_check_image(int w, int h, int c)
     return SVO_OK;
 }
 
-long long brief_img_stride(int w, int h) { return (((long long)(w + 1) * (h + 1)) + 63) & ~63ll; }
+long long brief_img_stride(int w, int h) { return integral_img_stride(w, h); }
 
 // the current table of `slot` on the device
 int brief_table(svo_ctx *ctx, int slot, const int8_t **d_table)
@@ -224,8 +158,8 @@ int brief_integrals(svo_ctx *ctx, const uint8_t *const *d_images, int nb, int w,
     for (int k = 0; k < BRIEF_MAXBATCH; k++)
         im.img[k] = k < nb ? d_images[k] : nullptr;
     ScopedKernelTime tm(ctx, SVO_K_BRIEF_INTEGRAL);
-    hipLaunchKernelGGL(brief_row_scan_kernel, dim3(h, nb), dim3(256), 0, ctx->stream, im, w, h, c, ctx->brief_sum.as<int>(), stride);
-    hipLaunchKernelGGL(brief_col_scan_kernel, dim3((w + 63) / 64, nb), dim3(64), 0, ctx->stream, w, h, ctx->brief_sum.as<int>(),
+    hipLaunchKernelGGL(integral_row_scan_kernel, dim3(h, nb), dim3(256), 0, ctx->stream, im, w, h, c, ctx->brief_sum.as<int>(), stride);
+    hipLaunchKernelGGL(integral_col_scan_kernel, dim3((w + 63) / 64, nb), dim3(64), 0, ctx->stream, w, h, ctx->brief_sum.as<int>(),
                        stride);
     SVO_HIP(hipGetLastError());
     return SVO_OK;

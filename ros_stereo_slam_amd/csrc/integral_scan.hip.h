@@ -1,0 +1,80 @@
+// integral_scan.hip.h -- the batched int32 integral image of 8-bit images (grey, or BGR through svo_bgr2gray): (h + 1) x (w + 1),
+// zero first row and column; blockIdx.y = image of the batch.  Shared by brief.hip and surf.hip; each includes it inside its own
+// unnamed namespace.  Integer sums: exact, no order dependence.
+#pragma once
+
+constexpr int INTEGRAL_MAXBATCH = 16;
+
+struct IntegralImages {
+    const uint8_t *img[INTEGRAL_MAXBATCH];
+};
+
+// ints between the tables of two images of a batch
+inline long long integral_img_stride(int w, int h) { return (((long long)(w + 1) * (h + 1)) + 63) & ~63ll; }
+
+// row y of the image -> row y + 1 of the table, as running sums along the row; column 0 and row 0 are zero
+__global__ __launch_bounds__(256) void integral_row_scan_kernel(IntegralImages im, int w, int h, int c, int *__restrict__ sum_all,
+                                                             long long img_stride)
+{
+    __shared__ int wave_total[4];
+    const int y = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint8_t *__restrict__ row = im.img[blockIdx.y] + (size_t)y * w * c;
+    int *__restrict__ out = sum_all + blockIdx.y * img_stride + (size_t)(y + 1) * (w + 1);
+    if (threadIdx.x == 0)
+        out[0] = 0;
+    if (y == 0)
+        for (int x = threadIdx.x; x <= w; x += 256)
+            out[x - (w + 1)] = 0;
+    int carry = 0;
+    for (int x0 = 0; x0 < w; x0 += 256) {
+        const int x = x0 + threadIdx.x;
+        int v = 0;
+        if (x < w)
+            v = c == 1 ? (int)row[x] : svo_bgr2gray(row[3 * x], row[3 * x + 1], row[3 * x + 2]);
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int t = __shfl_up(v, o);
+            if (lane >= o)
+                v += t;
+        }
+        if (lane == 63)
+            wave_total[wave] = v;
+        __syncthreads();
+        int before = carry, all = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            before += k < wave ? wave_total[k] : 0;
+            all += wave_total[k];
+        }
+        if (x < w)
+            out[x + 1] = v + before;
+        carry += all;
+        __syncthreads();
+    }
+}
+
+// a thread per column 1 ... w: rows added up from the top; eight rows' loads are in flight before the first add
+__global__ __launch_bounds__(64) void integral_col_scan_kernel(int w, int h, int *__restrict__ sum_all, long long img_stride)
+{
+    const int x = blockIdx.x * 64 + threadIdx.x + 1;
+    if (x > w)
+        return;
+    const size_t pitch = (size_t)w + 1;
+    int *__restrict__ p = sum_all + blockIdx.y * img_stride + pitch + x;
+    int acc = 0, y = 0;
+    for (; y + 8 <= h; y += 8) {
+        int v[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+            v[k] = p[(size_t)(y + k) * pitch];
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            acc += v[k];
+            p[(size_t)(y + k) * pitch] = acc;
+        }
+    }
+    for (; y < h; y++) {
+        acc += p[(size_t)y * pitch];
+        p[(size_t)y * pitch] = acc;
+    }
+}

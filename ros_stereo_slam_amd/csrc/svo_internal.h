@@ -147,6 +147,9 @@ struct svo_ctx {
     int8_t brief_pattern[3][2048];
     int brief_has_pattern[3] = {0, 0, 0};
     int brief_pat_live[3] = {0, 0, 0};
+    // surf.hip: the integral images of a batch, staged and grey images, the det / trace planes of every layer, the detector's
+    // candidate lists with the staged outputs of host calls
+    DevBuf surf_sum, surf_img, surf_planes, surf_work;
 };
 
 // Low-latency host wait for everything queued on the context's stream: records an event and
