@@ -234,21 +234,13 @@ class StereoProcess {
 
   private:
     static const float *fp(const std::vector<Point2f> &v) { return reinterpret_cast<const float *>(v.data()); }
-    static float *fpm(std::vector<Point2f> &v) { return reinterpret_cast<float *>(v.data()); }
     // n images of one size through one svo_sift_extract_batch call
     // (desc == nullptr: detect only)
     void siftFeaturesBatch(const Mat *const *imgs, int n, int nfeatures, std::vector<KeyPoint> *kps, std::vector<float> *desc)
     {
-        const Mat &first = *imgs[0];
         const uint8_t *ptrs[16];
-        if (n < 1 || n > 16)
-            throw SvoError(SVO_ERR_ARG, "siftFeatures: 1 ... 16 images per call");
-        for (int i = 0; i < n; i++) {
-            if (mat_cols(*imgs[i]) != mat_cols(first) || mat_rows(*imgs[i]) != mat_rows(first) ||
-                mat_channels(*imgs[i]) != mat_channels(first))
-                throw SvoError(SVO_ERR_ARG, "siftFeatures: the images differ in size");
-            ptrs[i] = mat_data(*imgs[i]);
-        }
+        same_size_ptrs(imgs, n, "siftFeatures", ptrs);
+        const Mat &first = *imgs[0];
         svo_sift_params prm;
         svo_sift_default_params(&prm);
         prm.n_features = nfeatures;
@@ -276,18 +268,12 @@ class StereoProcess {
     // n images of one size through one svo_brief_describe_batch call; kps[i] loses the key points the border filter removes
     void briefFeaturesBatch(const Mat *const *imgs, int n, std::vector<KeyPoint> *kps, std::vector<uint8_t> *desc)
     {
-        const Mat &first = *imgs[0];
         const uint8_t *ptrs[16];
-        if (n < 1 || n > 16)
-            throw SvoError(SVO_ERR_ARG, "briefFeatures: 1 ... 16 images per call");
+        same_size_ptrs(imgs, n, "briefFeatures", ptrs);
+        const Mat &first = *imgs[0];
         size_t cap = 1;
-        for (int i = 0; i < n; i++) {
-            if (mat_cols(*imgs[i]) != mat_cols(first) || mat_rows(*imgs[i]) != mat_rows(first) ||
-                mat_channels(*imgs[i]) != mat_channels(first))
-                throw SvoError(SVO_ERR_ARG, "briefFeatures: the images differ in size");
-            ptrs[i] = mat_data(*imgs[i]);
+        for (int i = 0; i < n; i++)
             cap = kps[i].size() > cap ? kps[i].size() : cap;
-        }
         const size_t nb = (size_t)briefBytes, e = cap * (size_t)n;
         std::vector<float> xy(2 * e);
         std::vector<int> n_in((size_t)n), n_out((size_t)n), kept(e);
@@ -325,28 +311,13 @@ class StereoProcess {
         siftFeaturesBatch(imgs, 2, siftFeaturesStereo, kps, nullptr);
         std::vector<uint8_t> desc[2];
         briefFeaturesBatch(imgs, 2, kps, desc);
-        const int n1 = (int)kps[0].size(), n2 = (int)kps[1].size();
-        if (n1 == 0 || n2 == 0)
-            return;
-        std::vector<Point2f> xy1, xy2;
-        for (const KeyPoint &k : kps[0])
-            xy1.emplace_back(k.pt);
-        for (const KeyPoint &k : kps[1])
-            xy2.emplace_back(k.pt);
-        const int qo[2] = {0, n1}, to[2] = {0, n2};
-        std::vector<int> idx((size_t)n1 * 2);
-        std::vector<float> dist((size_t)n1 * 2);
-        check(svo_knn_match(ctx(), SVO_MATCH_L2_U8, desc[0].data(), desc[1].data(), briefBytes, qo, to, 1, 2, idx.data(), dist.data(),
-                            SVO_MEM_HOST));
-        std::vector<Point2f> pt1((size_t)n1), pt2((size_t)n1);
-        int cnt = 0;
-        check(svo_ratio_pairs(ctx(), idx.data(), dist.data(), n1, 2, 0.8, fp(xy1), fp(xy2), fpm(pt1), fpm(pt2), nullptr, &cnt,
-                              SVO_MEM_HOST));
-        pt1.resize((size_t)cnt);
-        pt2.resize((size_t)cnt);
+        const std::vector<Point2f> xy1 = keypoint_points(kps[0]), xy2 = keypoint_points(kps[1]);
+        std::vector<Point2f> pt1, pt2;
+        ratio_match_points(ctx(), SVO_MATCH_L2_U8, desc[0].data(), desc[1].data(), briefBytes, (int)xy1.size(), (int)xy2.size(), fp(xy1),
+                           fp(xy2), pt1, pt2);
         stereoPairs1 = pt1;
         stereoPairs2 = pt2;
-        if (cnt < 8)
+        if (pt1.size() < 8)
             return;
         slam_.FmatThresholding(pt1, pt2);
         stereoInliers1 = pt1;
@@ -376,28 +347,9 @@ class StereoProcess {
         std::vector<KeyPoint> kps[2];
         std::vector<float> desc[2];
         siftFeaturesBatch(imgs, 2, siftFeaturesMono, kps, desc);
-        const int n1 = (int)kps[0].size(), n2 = (int)kps[1].size();
-        std::vector<Point2f> xy1, xy2;
-        for (const KeyPoint &k : kps[0])
-            xy1.emplace_back(k.pt);
-        for (const KeyPoint &k : kps[1])
-            xy2.emplace_back(k.pt);
-        pt1.clear();
-        pt2.clear();
-        if (n1 == 0 || n2 == 0)
-            return;
-        const int qo[2] = {0, n1}, to[2] = {0, n2};
-        std::vector<int> idx((size_t)n1 * 2);
-        std::vector<float> dist((size_t)n1 * 2);
-        check(svo_knn_match(ctx(), SVO_MATCH_L2_F32, desc[0].data(), desc[1].data(), 128, qo, to, 1, 2, idx.data(), dist.data(),
-                            SVO_MEM_HOST));
-        pt1.assign((size_t)n1, Point2f());
-        pt2.assign((size_t)n1, Point2f());
-        int cnt = 0;
-        check(svo_ratio_pairs(ctx(), idx.data(), dist.data(), n1, 2, 0.8, fp(xy1), fp(xy2), fpm(pt1), fpm(pt2), nullptr, &cnt,
-                              SVO_MEM_HOST));
-        pt1.resize((size_t)cnt);
-        pt2.resize((size_t)cnt);
+        const std::vector<Point2f> xy1 = keypoint_points(kps[0]), xy2 = keypoint_points(kps[1]);
+        ratio_match_points(ctx(), SVO_MATCH_L2_F32, desc[0].data(), desc[1].data(), 128, (int)xy1.size(), (int)xy2.size(), fp(xy1),
+                           fp(xy2), pt1, pt2);
     }
 #if defined(SVO_WITH_OPENCV) && defined(CV_16SC1)
     static constexpr int kDisp16S = CV_16SC1;

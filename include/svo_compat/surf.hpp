@@ -12,16 +12,9 @@ namespace svo_compat {
 inline void surf_features_batch(svo_ctx *ctx, const Mat *const *imgs, int n, double hessian, std::vector<KeyPoint> *kps,
                                 std::vector<float> *desc)
 {
-    const Mat &first = *imgs[0];
     const uint8_t *ptrs[16];
-    if (n < 1 || n > 16)
-        throw SvoError(SVO_ERR_ARG, "surfFeatures: 1 ... 16 images per call");
-    for (int i = 0; i < n; i++) {
-        if (mat_cols(*imgs[i]) != mat_cols(first) || mat_rows(*imgs[i]) != mat_rows(first) ||
-            mat_channels(*imgs[i]) != mat_channels(first))
-            throw SvoError(SVO_ERR_ARG, "surfFeatures: the images differ in size");
-        ptrs[i] = mat_data(*imgs[i]);
-    }
+    same_size_ptrs(imgs, n, "surfFeatures", ptrs);
+    const Mat &first = *imgs[0];
     svo_surf_params prm;
     svo_surf_default_params(&prm);
     prm.hessian_threshold = hessian;
@@ -68,8 +61,7 @@ inline void surf_features_batch(svo_ctx *ctx, const Mat *const *imgs, int n, dou
 }
 
 // SURF on both images (one set of launches), BFMatcher().knnMatch(desc1, desc2, matches, 2), m.distance < 0.8 * n.distance:
-// the points of the surviving pairs, in the order of the left image's key points.  Fewer than two key points on the right give no
-// pair (upstream would read matches[i][1] of a one-element list).
+// the points of the surviving pairs, in the order of the left image's key points (ratio_match_points).
 inline void surf_ratio_pairs(svo_ctx *ctx, const Mat &im1, const Mat &im2, double hessian, std::vector<Point2f> &pt1,
                              std::vector<Point2f> &pt2)
 {
@@ -77,32 +69,9 @@ inline void surf_ratio_pairs(svo_ctx *ctx, const Mat &im1, const Mat &im2, doubl
     std::vector<KeyPoint> kps[2];
     std::vector<float> desc[2];
     surf_features_batch(ctx, imgs, 2, hessian, kps, desc);
-    pt1.clear();
-    pt2.clear();
-    const int n1 = (int)kps[0].size(), n2 = (int)kps[1].size();
-    if (n1 < 1 || n2 < 2)
-        return;
-    std::vector<float> a(2 * (size_t)n1), b(2 * (size_t)n2);
-    for (int i = 0; i < n1; i++) {
-        a[2 * (size_t)i] = kps[0][(size_t)i].pt.x;
-        a[2 * (size_t)i + 1] = kps[0][(size_t)i].pt.y;
-    }
-    for (int i = 0; i < n2; i++) {
-        b[2 * (size_t)i] = kps[1][(size_t)i].pt.x;
-        b[2 * (size_t)i + 1] = kps[1][(size_t)i].pt.y;
-    }
-    const int qo[2] = {0, n1}, to[2] = {0, n2};
-    std::vector<int> idx((size_t)n1 * 2);
-    std::vector<float> dist((size_t)n1 * 2);
-    check(svo_knn_match(ctx, SVO_MATCH_L2_F32, desc[0].data(), desc[1].data(), 64, qo, to, 1, 2, idx.data(), dist.data(),
-                        SVO_MEM_HOST));
-    pt1.assign((size_t)n1, Point2f());
-    pt2.assign((size_t)n1, Point2f());
-    int cnt = 0;
-    check(svo_ratio_pairs(ctx, idx.data(), dist.data(), n1, 2, 0.8, a.data(), b.data(), reinterpret_cast<float *>(pt1.data()),
-                          reinterpret_cast<float *>(pt2.data()), nullptr, &cnt, SVO_MEM_HOST));
-    pt1.resize((size_t)cnt);
-    pt2.resize((size_t)cnt);
+    const std::vector<Point2f> xy1 = keypoint_points(kps[0]), xy2 = keypoint_points(kps[1]);
+    ratio_match_points(ctx, SVO_MATCH_L2_F32, desc[0].data(), desc[1].data(), 64, (int)xy1.size(), (int)xy2.size(),
+                       reinterpret_cast<const float *>(xy1.data()), reinterpret_cast<const float *>(xy2.data()), pt1, pt2);
 }
 
 }  // namespace svo_compat

@@ -263,6 +263,55 @@ inline void check(int rc)
         throw SvoError(rc, svo_last_error());
 }
 
+// The "1 ... 16 images of one size" rule of the batched feature calls: the images' data pointers into ptrs (16 entries), or an
+// SvoError that names the caller
+inline void same_size_ptrs(const Mat *const *imgs, int n, const char *what, const uint8_t **ptrs)
+{
+    if (n < 1 || n > 16)
+        throw SvoError(SVO_ERR_ARG, (std::string(what) + ": 1 ... 16 images per call").c_str());
+    const Mat &first = *imgs[0];
+    for (int i = 0; i < n; i++) {
+        if (mat_cols(*imgs[i]) != mat_cols(first) || mat_rows(*imgs[i]) != mat_rows(first) ||
+            mat_channels(*imgs[i]) != mat_channels(first))
+            throw SvoError(SVO_ERR_ARG, (std::string(what) + ": the images differ in size").c_str());
+        ptrs[i] = mat_data(*imgs[i]);
+    }
+}
+
+inline std::vector<Point2f> keypoint_points(const std::vector<KeyPoint> &kps)
+{
+    std::vector<Point2f> xy;
+    xy.reserve(kps.size());
+    for (const KeyPoint &k : kps)
+        xy.emplace_back(k.pt);
+    return xy;
+}
+
+// The pairing every sparse branch of the reference runs after its extractor: desc.convertTo(CV_32F),
+// BFMatcher().knnMatch(desc1, desc2, matches, 2) = svo_knn_match(norm, dim, k 2), m.distance < 0.8 * n.distance = svo_ratio_pairs.
+// desc1 / desc2: n1 / n2 rows of `dim` elements of `norm`'s kind, xy1 / xy2: their (x, y) pairs; pt1 / pt2 receive the points of
+// the surviving pairs in the order of the first image's key points.  Fewer than two key points in the second image give no pair
+// (upstream would read matches[i][1] of a one-element list).
+inline void ratio_match_points(svo_ctx *ctx, int norm, const void *desc1, const void *desc2, int dim, int n1, int n2, const float *xy1,
+                               const float *xy2, std::vector<Point2f> &pt1, std::vector<Point2f> &pt2)
+{
+    pt1.clear();
+    pt2.clear();
+    if (n1 < 1 || n2 < 2)
+        return;
+    const int qo[2] = {0, n1}, to[2] = {0, n2};
+    std::vector<int> idx((size_t)n1 * 2);
+    std::vector<float> dist((size_t)n1 * 2);
+    check(svo_knn_match(ctx, norm, desc1, desc2, dim, qo, to, 1, 2, idx.data(), dist.data(), SVO_MEM_HOST));
+    pt1.assign((size_t)n1, Point2f());
+    pt2.assign((size_t)n1, Point2f());
+    int cnt = 0;
+    check(svo_ratio_pairs(ctx, idx.data(), dist.data(), n1, 2, 0.8, xy1, xy2, reinterpret_cast<float *>(pt1.data()),
+                          reinterpret_cast<float *>(pt2.data()), nullptr, &cnt, SVO_MEM_HOST));
+    pt1.resize((size_t)cnt);
+    pt2.resize((size_t)cnt);
+}
+
 // one context per device, shared by the adaptors of a process
 inline svo_ctx *shared_context(int device = 0)
 {

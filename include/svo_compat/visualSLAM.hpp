@@ -508,18 +508,7 @@ class visualSLAM {
         int n[2] = {0, 0};
         check(svo_orb_extract_batch(ctx_, imgs, 2, mat_cols(im1), mat_rows(im1), mat_channels(im1), &prm, f(kp), nullptr, nullptr,
                                     nullptr, desc.data(), n, SVO_MEM_HOST));
-        const int qo[2] = {0, n[0]}, to[2] = {0, n[1]};
-        std::vector<int> idx((size_t)n[0] * 2);
-        std::vector<float> dist((size_t)n[0] * 2);
-        check(svo_knn_match(ctx_, SVO_MATCH_L2_U8, desc.data(), desc.data() + nf * 8, 32, qo, to, 1, 2, idx.data(), dist.data(),
-                            SVO_MEM_HOST));
-        pt1.assign((size_t)n[0], Point2f());
-        pt2.assign((size_t)n[0], Point2f());
-        int cnt = 0;
-        check(svo_ratio_pairs(ctx_, idx.data(), dist.data(), n[0], 2, 0.8, f(kp), f(kp) + 2 * nf, f(pt1), f(pt2), nullptr, &cnt,
-                              SVO_MEM_HOST));
-        pt1.resize((size_t)cnt);
-        pt2.resize((size_t)cnt);
+        ratio_match_points(ctx_, SVO_MATCH_L2_U8, desc.data(), desc.data() + nf * 8, 32, n[0], n[1], f(kp), f(kp) + 2 * nf, pt1, pt2);
     }
     void compact2(const std::vector<uint8_t> &mask, std::vector<Point2f> &a, std::vector<Point2f> &b)
     {

@@ -20,13 +20,13 @@
 
 namespace {
 
+#include "feature_batch.hip.h"
 #include "integral_scan.hip.h"
 
-constexpr int BRIEF_MAXBATCH = INTEGRAL_MAXBATCH, BRIEF_BORDER = 28, BRIEF_HALF_PATCH = 24;
+constexpr int BRIEF_MAXBATCH = IMAGE_MAXBATCH, BRIEF_BORDER = 28, BRIEF_HALF_PATCH = 24;
 constexpr int BRIEF_WAVES = 4;       // key points a workgroup of the descriptor kernel works on at a time
 constexpr int BRIEF_MAXGRID = 2048;  // its workgroups per image: 8 per CU, each wave walks on with that stride
 
-using BriefImages = IntegralImages;
 struct BriefCounts {
     int n[BRIEF_MAXBATCH];
 };
@@ -108,27 +108,16 @@ int brief_slot(int bytes) { return bytes == 16 ? 0 : bytes == 32 ? 1 : bytes == 
 
 const int8_t *brief_default(int slot) { return slot == 0 ? BRIEF_DEFAULT_16 : slot == 1 ? BRIEF_DEFAULT_32 : BRIEF_DEFAULT_64; }
 
-bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
-template <class T> T *bump(uint8_t *&p, size_t count)
-{
-    T *r = reinterpret_cast<T *>(p);
-    p += (count * sizeof(T) + 255) & ~(size_t)255;
-    return r;
-}
-
 int brief_check_image(int w, int h, int c)
 {
     SVO_CHECK_ARG(c == 1 || c == 3);
     SVO_CHECK_ARG(w >= 1 && h >= 1 && w <= 16384 && h <= 16384);
-    if (255ll * w * h > 2147483647ll) {
+    if (!integral_fits_int32(w, h)) {
         svo_set_error("svo_brief: the int32 integral image of %d x %d pixels could overflow (255 w h > 2^31 - 1)", w, h);
         return SVO_ERR_CAPACITY;
     }
     return SVO_OK;
 }
-
-long long brief_img_stride(int w, int h) { return integral_img_stride(w, h); }
 
 // the current table of `slot` on the device
 int brief_table(svo_ctx *ctx, int slot, const int8_t **d_table)
@@ -147,22 +136,11 @@ int brief_table(svo_ctx *ctx, int slot, const int8_t **d_table)
     return SVO_OK;
 }
 
-// the integral images of nb device images into ctx->brief_sum
+// the integral images of nb device images into ctx->feat_sum
 int brief_integrals(svo_ctx *ctx, const uint8_t *const *d_images, int nb, int w, int h, int c)
 {
-    const long long stride = brief_img_stride(w, h);
-    int rc;
-    if ((rc = ctx->brief_sum.ensure((size_t)stride * nb * 4)))
-        return rc;
-    BriefImages im;
-    for (int k = 0; k < BRIEF_MAXBATCH; k++)
-        im.img[k] = k < nb ? d_images[k] : nullptr;
     ScopedKernelTime tm(ctx, SVO_K_BRIEF_INTEGRAL);
-    hipLaunchKernelGGL(integral_row_scan_kernel, dim3(h, nb), dim3(256), 0, ctx->stream, im, w, h, c, ctx->brief_sum.as<int>(), stride);
-    hipLaunchKernelGGL(integral_col_scan_kernel, dim3((w + 63) / 64, nb), dim3(64), 0, ctx->stream, w, h, ctx->brief_sum.as<int>(),
-                       stride);
-    SVO_HIP(hipGetLastError());
-    return SVO_OK;
+    return integral_images(ctx, d_images, nb, w, h, c, 0);
 }
 
 }  // namespace
@@ -213,17 +191,10 @@ int svo_brief_integral(svo_ctx *ctx, const uint8_t *image, int w, int h, int c, 
         return rc;
     SVO_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const uint8_t *d_img = image;
-    if (mem == SVO_MEM_HOST) {
-        const size_t img_bytes = (size_t)w * h * c;
-        if ((rc = ctx->brief_img.ensure(img_bytes + 256)))
-            return rc;
-        SVO_HIP(hipMemcpyAsync(ctx->brief_img.p, image, img_bytes, hipMemcpyHostToDevice, st));
-        d_img = ctx->brief_img.as<uint8_t>();
-    }
-    if ((rc = brief_integrals(ctx, &d_img, 1, w, h, c)))
+    const uint8_t *d_img = nullptr;
+    if ((rc = stage_images(ctx, &image, 1, (size_t)w * h * c, mem, &d_img)) || (rc = brief_integrals(ctx, &d_img, 1, w, h, c)))
         return rc;
-    SVO_HIP(hipMemcpyAsync(sum, ctx->brief_sum.p, (size_t)(w + 1) * (h + 1) * 4,
+    SVO_HIP(hipMemcpyAsync(sum, ctx->feat_sum.p, (size_t)(w + 1) * (h + 1) * 4,
                            mem == SVO_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
     if (mem == SVO_MEM_HOST)
         SVO_HIP(hipStreamSynchronize(st));
@@ -258,7 +229,7 @@ int svo_brief_describe_batch(svo_ctx *ctx, const uint8_t *const *images, int n_i
     const int8_t *d_table = nullptr;
     if ((rc = brief_table(ctx, slot, &d_table)))
         return rc;
-    const size_t img_bytes = (size_t)w * h * c, e = (size_t)n_images * cap;
+    const size_t e = (size_t)n_images * cap;
     const int mask_stride = (cap + 15) & ~15;
     const bool host = mem == SVO_MEM_HOST;
     if ((rc = ctx->brief_work.ensure(e * (8 + 4 + 8 + (host ? 4 + (size_t)bytes : 0)) + (size_t)n_images * mask_stride + 8 * 256 + 256)))
@@ -276,21 +247,12 @@ int svo_brief_describe_batch(svo_ctx *ctx, const uint8_t *const *images, int n_i
         float *sxy = bump<float>(q, 2 * e);
         d_kept = bump<int>(q, e);
         d_desc = bump<uint8_t>(q, e * bytes);
-        if ((rc = ctx->brief_img.ensure(img_bytes * n_images + 256)))
-            return rc;
-        for (int k = 0; k < n_images; k++) {
-            uint8_t *img_slot = ctx->brief_img.as<uint8_t>() + (size_t)k * img_bytes;
-            SVO_HIP(hipMemcpyAsync(img_slot, images[k], img_bytes, hipMemcpyHostToDevice, st));
-            ptrs[k] = img_slot;
+        for (int k = 0; k < n_images; k++)
             if (n_in[k])
                 SVO_HIP(hipMemcpyAsync(sxy + 2 * (size_t)k * cap, xy + 2 * (size_t)k * cap, (size_t)n_in[k] * 8, hipMemcpyHostToDevice, st));
-        }
         d_xy = sxy;
-    } else {
-        for (int k = 0; k < n_images; k++)
-            ptrs[k] = images[k];
     }
-    if ((rc = brief_integrals(ctx, ptrs, n_images, w, h, c)))
+    if ((rc = stage_images(ctx, images, n_images, (size_t)w * h * c, mem, ptrs)) || (rc = brief_integrals(ctx, ptrs, n_images, w, h, c)))
         return rc;
     {
         ScopedKernelTime tm(ctx, SVO_K_BRIEF_DESCRIBE);
@@ -321,8 +283,8 @@ int svo_brief_describe_batch(svo_ctx *ctx, const uint8_t *const *images, int n_i
         int gx = (n_max + BRIEF_WAVES - 1) / BRIEF_WAVES;
         gx = gx > BRIEF_MAXGRID ? BRIEF_MAXGRID : gx;
         const dim3 grid(gx, n_images), block(64 * BRIEF_WAVES);
-        const int *sums = ctx->brief_sum.as<int>();
-        const long long stride = brief_img_stride(w, h);
+        const int *sums = ctx->feat_sum.as<int>();
+        const long long stride = integral_img_stride(w, h);
         if (slot == 0)
             hipLaunchKernelGGL(brief_describe_kernel<2>, grid, block, 0, st, sums, stride, w, d_kxy, d_counts, cap, d_table, d_desc);
         else if (slot == 1)
@@ -332,20 +294,11 @@ int svo_brief_describe_batch(svo_ctx *ctx, const uint8_t *const *images, int n_i
         SVO_HIP(hipGetLastError());
     }
     // the one wait: the counts
-    int counts[BRIEF_MAXBATCH];
-    SVO_HIP(hipMemcpyAsync(counts, d_counts, sizeof(int) * n_images, hipMemcpyDeviceToHost, st));
-    SVO_HIP(hipStreamSynchronize(st));
-    for (int k = 0; k < n_images; k++)
-        n_out[k] = counts[k];
+    if ((rc = read_counts(ctx, d_counts, n_images, n_out)))
+        return rc;
     if (host) {
-        for (int k = 0; k < n_images; k++) {
-            const size_t m = (size_t)counts[k], b = (size_t)k * cap;
-            if (!m)
-                continue;
-            SVO_HIP(hipMemcpyAsync(kept_index + b, d_kept + b, m * 4, hipMemcpyDeviceToHost, st));
-            SVO_HIP(hipMemcpyAsync(desc + b * bytes, d_desc + b * bytes, m * bytes, hipMemcpyDeviceToHost, st));
-        }
-        SVO_HIP(hipStreamSynchronize(st));
+        const HostColumn cols[2] = {{kept_index, d_kept, 4}, {desc, d_desc, (size_t)bytes}};
+        return copy_rows_to_host(st, cols, 2, n_images, cap, n_out);
     }
     return SVO_OK;
 }

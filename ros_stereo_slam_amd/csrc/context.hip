@@ -212,9 +212,8 @@ int svo_ctx_destroy(svo_ctx *ctx)
                       &ctx->s_f,   &ctx->s_g, &ctx->w_a, &ctx->w_b, &ctx->w_c, &ctx->w_d,
                       &ctx->w_e,   &ctx->orb_out, &ctx->orb_cv_out, &ctx->orb_cv_img, &ctx->orb_cv_ptrs,
                       &ctx->sgbm_cost, &ctx->sgbm_misc, &ctx->sgbm_rp, &ctx->sor_grid, &ctx->ess,
-                      &ctx->sift_pyr, &ctx->sift_work, &ctx->sift_img, &ctx->sift_out,
-                      &ctx->brief_sum, &ctx->brief_img, &ctx->brief_work, &ctx->brief_pat,
-                      &ctx->surf_sum, &ctx->surf_img, &ctx->surf_planes, &ctx->surf_work};
+                      &ctx->feat_img, &ctx->feat_sum, &ctx->sift_pyr, &ctx->sift_work, &ctx->sift_out,
+                      &ctx->brief_work, &ctx->brief_pat, &ctx->surf_planes, &ctx->surf_work};
     for (DevBuf *b : bufs)
         b->release();
     ctx->up_ring.release();

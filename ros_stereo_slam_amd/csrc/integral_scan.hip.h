@@ -1,19 +1,16 @@
 // integral_scan.hip.h -- the batched int32 integral image of 8-bit images (grey, or BGR through svo_bgr2gray): (h + 1) x (w + 1),
 // zero first row and column; blockIdx.y = image of the batch.  Shared by brief.hip and surf.hip; each includes it inside its own
-// unnamed namespace.  Integer sums: exact, no order dependence.
+// unnamed namespace, after feature_batch.hip.h.  Integer sums: exact, no order dependence.
 #pragma once
 
-constexpr int INTEGRAL_MAXBATCH = 16;
-
-struct IntegralImages {
-    const uint8_t *img[INTEGRAL_MAXBATCH];
-};
+// the largest entry is at most 255 w h
+inline bool integral_fits_int32(int w, int h) { return 255ll * w * h <= 2147483647ll; }
 
 // ints between the tables of two images of a batch
 inline long long integral_img_stride(int w, int h) { return (((long long)(w + 1) * (h + 1)) + 63) & ~63ll; }
 
 // row y of the image -> row y + 1 of the table, as running sums along the row; column 0 and row 0 are zero
-__global__ __launch_bounds__(256) void integral_row_scan_kernel(IntegralImages im, int w, int h, int c, int *__restrict__ sum_all,
+__global__ __launch_bounds__(256) void integral_row_scan_kernel(ImageBatch im, int w, int h, int c, int *__restrict__ sum_all,
                                                              long long img_stride)
 {
     __shared__ int wave_total[4];
@@ -77,4 +74,19 @@ __global__ __launch_bounds__(64) void integral_col_scan_kernel(int w, int h, int
         acc += p[(size_t)y * pitch];
         p[(size_t)y * pitch] = acc;
     }
+}
+
+// the integral images of nb device images into ctx->feat_sum, which also gets room for extra_bytes behind them
+inline int integral_images(svo_ctx *ctx, const uint8_t *const *d_images, int nb, int w, int h, int c, size_t extra_bytes)
+{
+    const long long stride = integral_img_stride(w, h);
+    int rc;
+    if ((rc = ctx->feat_sum.ensure((size_t)stride * nb * 4 + extra_bytes)))
+        return rc;
+    hipLaunchKernelGGL(integral_row_scan_kernel, dim3(h, nb), dim3(256), 0, ctx->stream, make_image_batch(d_images, nb), w, h, c,
+                       ctx->feat_sum.as<int>(), stride);
+    hipLaunchKernelGGL(integral_col_scan_kernel, dim3((w + 63) / 64, nb), dim3(64), 0, ctx->stream, w, h, ctx->feat_sum.as<int>(),
+                       stride);
+    SVO_HIP(hipGetLastError());
+    return SVO_OK;
 }

@@ -27,7 +27,9 @@
 
 namespace {
 
-constexpr int SIFT_MAXOCT = 16, SIFT_MAXBATCH = 16, SIFT_BORDER = 5, SIFT_STEPS = 5, SIFT_ORI_BINS = 36, SIFT_MAXPEAK = 18;
+#include "feature_batch.hip.h"
+
+constexpr int SIFT_MAXOCT = 16, SIFT_MAXBATCH = IMAGE_MAXBATCH, SIFT_BORDER = 5, SIFT_STEPS = 5, SIFT_ORI_BINS = 36, SIFT_MAXPEAK = 18;
 constexpr int SIFT_KP_CAP = 1 << 16;    // refined cells per image
 constexpr int SIFT_ORI_CAP = 1 << 17;   // oriented key points per image before retainBest
 constexpr int SIFT_KSTRIDE = 256;       // floats per Gaussian kernel (ksize <= 255)
@@ -46,10 +48,6 @@ struct SiftGeom {
 // the taps of one blur, a kernel argument: every lane reads tap t at the same time, so they come in through scalar loads
 struct SiftTaps {
     float k[SIFT_KSTRIDE];
-};
-
-struct SiftImages {
-    const uint8_t *img[SIFT_MAXBATCH];
 };
 
 __device__ __forceinline__ int reflect101(int p, int n)
@@ -81,7 +79,7 @@ __device__ __forceinline__ void linear_tab(int d, int n, int &s0, int &s1, float
     a1 = fx;
 }
 
-__global__ __launch_bounds__(256) void sift_init_kernel(SiftImages im, int w, int h, int c, float *__restrict__ base_all,
+__global__ __launch_bounds__(256) void sift_init_kernel(ImageBatch im, int w, int h, int c, float *__restrict__ base_all,
                                                         long long img_stride)
 {
     const int dx = blockIdx.x * 256 + threadIdx.x, dy = blockIdx.y;
@@ -753,13 +751,6 @@ int sift_check_params(const svo_sift_params *prm, svo_sift_params &p, int w, int
     return SVO_OK;
 }
 
-template <class T> T *bump(uint8_t *&p, size_t count)
-{
-    T *r = reinterpret_cast<T *>(p);
-    p += (count * sizeof(T) + 255) & ~(size_t)255;
-    return r;
-}
-
 int sift_plan(svo_ctx *ctx, int w, int h, int c, const svo_sift_params &p, int B, SiftPlan &pl)
 {
     SiftGeom &g = pl.g;
@@ -864,12 +855,9 @@ int sift_build_pyramids(svo_ctx *ctx, const SiftPlan &pl, const uint8_t *const *
 {
     hipStream_t st = ctx->stream;
     const SiftGeom &g = pl.g;
-    SiftImages im;
-    for (int k = 0; k < SIFT_MAXBATCH; k++)
-        im.img[k] = k < nb ? d_images[k] : nullptr;
     const int W = g.w[0], H = g.h[0];
-    hipLaunchKernelGGL(sift_init_kernel, dim3((W + 255) / 256, H, nb), dim3(256), 0, st, im, pl.w, pl.h, pl.c, pl.base,
-                       pl.base_img);
+    hipLaunchKernelGGL(sift_init_kernel, dim3((W + 255) / 256, H, nb), dim3(256), 0, st, make_image_batch(d_images, nb), pl.w, pl.h, pl.c,
+                       pl.base, pl.base_img);
     for (int o = 0; o < g.no; o++) {
         const int w = g.w[o], h = g.h[o];
         const long long px = (long long)w * h;
@@ -946,8 +934,6 @@ int sift_detect(svo_ctx *ctx, const SiftPlan &pl, int nb, int n_features, const 
     return SVO_OK;
 }
 
-bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -983,18 +969,15 @@ int svo_sift_extract_batch(svo_ctx *ctx, const uint8_t *const *images, int n_ima
     SiftPlan pl;
     if ((rc = sift_plan(ctx, w, h, c, p, n_images, pl)))
         return rc;
-    const size_t img_bytes = (size_t)w * h * c, e = (size_t)n_images * cap;
+    const size_t e = (size_t)n_images * cap;
     const uint8_t *ptrs[SIFT_MAXBATCH];
     SiftOut out{xy, size, angle, response, octave, cap};
     float *d_desc = desc;
+    if ((rc = stage_images(ctx, images, n_images, (size_t)w * h * c, mem, ptrs)))
+        return rc;
     if (mem == SVO_MEM_HOST) {
-        if ((rc = ctx->sift_img.ensure(img_bytes * n_images + 256)) || (rc = ctx->sift_out.ensure(e * (6 + (desc ? 128 : 0)) * 4 + 2048)))
+        if ((rc = ctx->sift_out.ensure(e * (6 + (desc ? 128 : 0)) * 4 + 2048)))
             return rc;
-        for (int k = 0; k < n_images; k++) {
-            uint8_t *slot = ctx->sift_img.as<uint8_t>() + (size_t)k * img_bytes;
-            SVO_HIP(hipMemcpyAsync(slot, images[k], img_bytes, hipMemcpyHostToDevice, st));
-            ptrs[k] = slot;
-        }
         uint8_t *q = ctx->sift_out.as<uint8_t>();
         out.xy = bump<float>(q, 2 * e);
         out.size = bump<float>(q, e);
@@ -1002,17 +985,13 @@ int svo_sift_extract_batch(svo_ctx *ctx, const uint8_t *const *images, int n_ima
         out.resp = bump<float>(q, e);
         out.oct = bump<int>(q, e);
         d_desc = desc ? bump<float>(q, 128 * e) : nullptr;
-    } else {
-        for (int k = 0; k < n_images; k++)
-            ptrs[k] = images[k];
     }
     if ((rc = sift_build_pyramids(ctx, pl, ptrs, n_images)) || (rc = sift_detect(ctx, pl, n_images, p.n_features, out, d_desc)))
         return rc;
     // the one wait: the counts
     int counts[3 * SIFT_MAXBATCH];
-    SVO_HIP(hipMemcpyAsync(counts, pl.counts, sizeof(int) * 3 * n_images, hipMemcpyDeviceToHost, st));
-    SVO_HIP(hipStreamSynchronize(st));
-    rc = SVO_OK;
+    if ((rc = read_counts(ctx, pl.counts, 3 * n_images, counts)))
+        return rc;
     for (int k = 0; k < n_images; k++) {
         const int nc = counts[k], no = counts[n_images + k], nk = counts[2 * n_images + k];
         n[k] = nk;
@@ -1027,19 +1006,11 @@ int svo_sift_extract_batch(svo_ctx *ctx, const uint8_t *const *images, int n_ima
         }
     }
     if (mem == SVO_MEM_HOST) {
-        for (int k = 0; k < n_images; k++) {
-            const size_t m = (size_t)(n[k] < cap ? n[k] : cap), b = (size_t)k * cap;
-            if (!m)
-                continue;
-            SVO_HIP(hipMemcpyAsync(xy + 2 * b, out.xy + 2 * b, m * 8, hipMemcpyDeviceToHost, st));
-            SVO_HIP(hipMemcpyAsync(size + b, out.size + b, m * 4, hipMemcpyDeviceToHost, st));
-            SVO_HIP(hipMemcpyAsync(angle + b, out.angle + b, m * 4, hipMemcpyDeviceToHost, st));
-            SVO_HIP(hipMemcpyAsync(response + b, out.resp + b, m * 4, hipMemcpyDeviceToHost, st));
-            SVO_HIP(hipMemcpyAsync(octave + b, out.oct + b, m * 4, hipMemcpyDeviceToHost, st));
-            if (desc)
-                SVO_HIP(hipMemcpyAsync(desc + 128 * b, d_desc + 128 * b, m * 512, hipMemcpyDeviceToHost, st));
-        }
-        SVO_HIP(hipStreamSynchronize(st));
+        const HostColumn cols[6] = {{xy, out.xy, 8},         {size, out.size, 4},  {angle, out.angle, 4},
+                                    {response, out.resp, 4}, {octave, out.oct, 4}, {desc, d_desc, 128 * sizeof(float)}};
+        const int rc_copy = copy_rows_to_host(st, cols, 6, n_images, cap, n);
+        if (rc_copy)
+            return rc_copy;
     }
     return rc;
 }
@@ -1061,16 +1032,16 @@ int svo_sift_describe(svo_ctx *ctx, const uint8_t *image, int w, int h, int c, c
     SiftPlan pl;
     if ((rc = sift_plan(ctx, w, h, c, p, 1, pl)))
         return rc;
-    const size_t img_bytes = (size_t)w * h * c, e = (size_t)n;
-    const uint8_t *d_img = image;
+    const size_t e = (size_t)n;
+    const uint8_t *d_img = nullptr;
     const float *dxy = xy, *dsize = size, *dang = angle;
     const int *doct = octave;
     float *ddesc = desc;
+    if ((rc = stage_images(ctx, &image, 1, (size_t)w * h * c, mem, &d_img)))
+        return rc;
     if (mem == SVO_MEM_HOST) {
-        if ((rc = ctx->sift_img.ensure(img_bytes + 256)) || (rc = ctx->sift_out.ensure(e * (5 + 128) * 4 + 2048)))
+        if ((rc = ctx->sift_out.ensure(e * (5 + 128) * 4 + 2048)))
             return rc;
-        SVO_HIP(hipMemcpyAsync(ctx->sift_img.p, image, img_bytes, hipMemcpyHostToDevice, st));
-        d_img = ctx->sift_img.as<uint8_t>();
         uint8_t *q = ctx->sift_out.as<uint8_t>();
         float *a = bump<float>(q, 2 * e), *b = bump<float>(q, e), *cc = bump<float>(q, e);
         int *d = bump<int>(q, e);
@@ -1126,15 +1097,8 @@ int svo_sift_pyramid(svo_ctx *ctx, const uint8_t *image, int w, int h, int c, co
     SiftPlan pl;
     if ((rc = sift_plan(ctx, w, h, c, p, 1, pl)))
         return rc;
-    const uint8_t *d_img = image;
-    if (mem == SVO_MEM_HOST) {
-        const size_t img_bytes = (size_t)w * h * c;
-        if ((rc = ctx->sift_img.ensure(img_bytes + 256)))
-            return rc;
-        SVO_HIP(hipMemcpyAsync(ctx->sift_img.p, image, img_bytes, hipMemcpyHostToDevice, st));
-        d_img = ctx->sift_img.as<uint8_t>();
-    }
-    if ((rc = sift_build_pyramids(ctx, pl, &d_img, 1)))
+    const uint8_t *d_img = nullptr;
+    if ((rc = stage_images(ctx, &image, 1, (size_t)w * h * c, mem, &d_img)) || (rc = sift_build_pyramids(ctx, pl, &d_img, 1)))
         return rc;
     const SiftGeom &g = pl.g;
     const int last = g.no - 1;

@@ -28,9 +28,10 @@
 
 namespace {
 
+#include "feature_batch.hip.h"
 #include "integral_scan.hip.h"
 
-constexpr int SURF_MAXBATCH = INTEGRAL_MAXBATCH, SURF_MAXOCT = 8, SURF_MAXCAND = 65536;
+constexpr int SURF_MAXBATCH = IMAGE_MAXBATCH, SURF_MAXOCT = 8, SURF_MAXCAND = 65536;
 constexpr int SURF_ORI_RADIUS = 6, SURF_PATCH = 20, SURF_P1 = SURF_PATCH + 1;
 constexpr int SURF_DESC_THREADS = 128;
 
@@ -73,7 +74,7 @@ __device__ __forceinline__ int surf_box(const int *__restrict__ p, int pitch, co
 }
 
 // ---- 1. grey image ----
-__global__ __launch_bounds__(256) void surf_grey_kernel(IntegralImages im, int n_px, uint8_t *__restrict__ grey_all, long long stride)
+__global__ __launch_bounds__(256) void surf_grey_kernel(ImageBatch im, int n_px, uint8_t *__restrict__ grey_all, long long stride)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_px)
@@ -573,15 +574,6 @@ __global__ __launch_bounds__(SURF_DESC_THREADS) void surf_describe_kernel(const 
 }
 
 // ---- host side ----
-bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
-template <class T> T *bump(uint8_t *&p, size_t count)
-{
-    T *r = reinterpret_cast<T *>(p);
-    p += (count * sizeof(T) + 255) & ~(size_t)255;
-    return r;
-}
-
 // U9: getGaussianKernel(n, sigma, CV_32F), n > 7
 void surf_gaussian(int n, double sigma, float *c)
 {
@@ -618,7 +610,7 @@ int surf_check(const svo_surf_params *prm, svo_surf_params &p, int w, int h, int
         svo_set_error("svo_surf: extended (128-float) descriptors are not provided");
         return SVO_ERR_ARG;
     }
-    if (255ll * w * h > 2147483647ll) {
+    if (!integral_fits_int32(w, h)) {
         svo_set_error("svo_surf: the int32 integral image of %d x %d pixels could overflow (255 w h > 2^31 - 1)", w, h);
         return SVO_ERR_ARG;
     }
@@ -659,15 +651,15 @@ int surf_prepare(svo_ctx *ctx, const uint8_t *const *d_images, int nb, int w, in
     pl.sum_stride = integral_img_stride(w, h);
     pl.grey_stride = ((long long)w * h + 255) & ~255ll;
     int rc;
-    if ((rc = ctx->surf_sum.ensure((size_t)pl.sum_stride * nb * 4 + (c == 3 ? (size_t)pl.grey_stride * nb : 0))))
+    // the scans are queued before the grey kernel and the gather: all three only read the images, and the grey planes lie in the
+    // buffer integral_images sizes
+    if ((rc = integral_images(ctx, d_images, nb, w, h, c, c == 3 ? (size_t)pl.grey_stride * nb : 0)))
         return rc;
-    pl.sum = ctx->surf_sum.as<int>();
-    IntegralImages im;
-    for (int k = 0; k < SURF_MAXBATCH; k++)
-        im.img[k] = k < nb ? d_images[k] : nullptr;
+    pl.sum = ctx->feat_sum.as<int>();
     if (c == 3) {
-        uint8_t *grey = ctx->surf_sum.as<uint8_t>() + (size_t)pl.sum_stride * nb * 4;
-        hipLaunchKernelGGL(surf_grey_kernel, dim3((w * h + 255) / 256, nb), dim3(256), 0, st, im, w * h, grey, pl.grey_stride);
+        uint8_t *grey = ctx->feat_sum.as<uint8_t>() + (size_t)pl.sum_stride * nb * 4;
+        hipLaunchKernelGGL(surf_grey_kernel, dim3((w * h + 255) / 256, nb), dim3(256), 0, st, make_image_batch(d_images, nb), w * h, grey,
+                           pl.grey_stride);
         pl.grey = grey;
     } else {
         // grey images of a batch need not be evenly spaced: the descriptor kernel takes image 0's address and a stride, so a
@@ -679,17 +671,15 @@ int surf_prepare(svo_ctx *ctx, const uint8_t *const *d_images, int nb, int w, in
             pl.grey = d_images[0];
             pl.grey_stride = nb > 1 ? (long long)(d_images[1] - d_images[0]) : 0;
         } else {
-            if ((rc = ctx->surf_img.ensure((size_t)pl.grey_stride * nb + 256)))
+            // device images only (staged host images are evenly spaced), so ctx->feat_img holds nothing of this call yet
+            if ((rc = ctx->feat_img.ensure((size_t)pl.grey_stride * nb + 256)))
                 return rc;
             for (int k = 0; k < nb; k++)
-                SVO_HIP(hipMemcpyAsync(ctx->surf_img.as<uint8_t>() + (size_t)k * pl.grey_stride, d_images[k], (size_t)w * h,
+                SVO_HIP(hipMemcpyAsync(ctx->feat_img.as<uint8_t>() + (size_t)k * pl.grey_stride, d_images[k], (size_t)w * h,
                                        hipMemcpyDeviceToDevice, st));
-            pl.grey = ctx->surf_img.as<uint8_t>();
+            pl.grey = ctx->feat_img.as<uint8_t>();
         }
     }
-    hipLaunchKernelGGL(integral_row_scan_kernel, dim3(h, nb), dim3(256), 0, st, im, w, h, c, ctx->surf_sum.as<int>(), pl.sum_stride);
-    hipLaunchKernelGGL(integral_col_scan_kernel, dim3((w + 63) / 64, nb), dim3(64), 0, st, w, h, ctx->surf_sum.as<int>(),
-                       pl.sum_stride);
     SVO_HIP(hipGetLastError());
     pl.det = pl.trace = nullptr;
     if (!planes)
@@ -708,21 +698,6 @@ int surf_prepare(svo_ctx *ctx, const uint8_t *const *d_images, int nb, int w, in
                            pl.g, o, pl.det, pl.trace);
     }
     SVO_HIP(hipGetLastError());
-    return SVO_OK;
-}
-
-// host images of a call -> device copies in ctx->surf_img (grey images stay where surf_prepare can use them in place)
-int surf_stage_images(svo_ctx *ctx, const uint8_t *const *images, int nb, size_t img_bytes, const uint8_t **ptrs)
-{
-    const size_t slot = (img_bytes + 255) & ~(size_t)255;
-    int rc;
-    if ((rc = ctx->surf_img.ensure(slot * nb + 256)))
-        return rc;
-    for (int k = 0; k < nb; k++) {
-        uint8_t *dst = ctx->surf_img.as<uint8_t>() + (size_t)k * slot;
-        SVO_HIP(hipMemcpyAsync(dst, images[k], img_bytes, hipMemcpyHostToDevice, ctx->stream));
-        ptrs[k] = dst;
-    }
     return SVO_OK;
 }
 
@@ -770,11 +745,9 @@ int svo_surf_layers(svo_ctx *ctx, const uint8_t *image, int w, int h, int c, con
         return rc;
     SVO_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const uint8_t *d_img = image;
-    if (mem == SVO_MEM_HOST && (rc = surf_stage_images(ctx, &image, 1, (size_t)w * h * c, &d_img)))
-        return rc;
+    const uint8_t *d_img = nullptr;
     SurfPlan pl;
-    if ((rc = surf_prepare(ctx, &d_img, 1, w, h, c, p, true, pl)))
+    if ((rc = stage_images(ctx, &image, 1, (size_t)w * h * c, mem, &d_img)) || (rc = surf_prepare(ctx, &d_img, 1, w, h, c, p, true, pl)))
         return rc;
     const SurfGeom &g = pl.g;
     const int last = g.n_oct - 1;
@@ -809,13 +782,8 @@ int svo_surf_extract_batch(svo_ctx *ctx, const uint8_t *const *images, int n_ima
     const bool host = mem == SVO_MEM_HOST;
     const size_t e = (size_t)n_images * cap, nc = (size_t)n_images * SURF_MAXCAND;
     const uint8_t *ptrs[SURF_MAXBATCH];
-    if (host) {
-        if ((rc = surf_stage_images(ctx, images, n_images, (size_t)w * h * c, ptrs)))
-            return rc;
-    } else {
-        for (int k = 0; k < n_images; k++)
-            ptrs[k] = images[k];
-    }
+    if ((rc = stage_images(ctx, images, n_images, (size_t)w * h * c, mem, ptrs)))
+        return rc;
     if ((rc = ctx->surf_work.ensure(256 + nc * (16 + 16 + 4) + 3 * 256 + (host ? e * (7 + (desc ? 64 : 0)) * 4 + 8 * 256 : 0))))
         return rc;
     uint8_t *q = ctx->surf_work.as<uint8_t>();
@@ -854,36 +822,24 @@ int svo_surf_extract_batch(svo_ctx *ctx, const uint8_t *const *images, int n_ima
                            out.size, out.angle, (const uint8_t *)nullptr, d_counts, 0, cap, p.upright ? 1 : 0, wt, d_desc);
     SVO_HIP(hipGetLastError());
     // the one wait: the counts
-    int counts[SURF_MAXBATCH];
-    SVO_HIP(hipMemcpyAsync(counts, d_counts, sizeof(int) * n_images, hipMemcpyDeviceToHost, st));
-    SVO_HIP(hipStreamSynchronize(st));
-    rc = SVO_OK;
+    if ((rc = read_counts(ctx, d_counts, n_images, n)))
+        return rc;
     for (int k = 0; k < n_images; k++) {
-        n[k] = counts[k];
-        if (counts[k] > SURF_MAXCAND) {
-            svo_set_error("svo_surf_extract_batch: image %d has %d key points (the work arrays hold %d)", k, counts[k], SURF_MAXCAND);
+        if (n[k] > SURF_MAXCAND) {
+            svo_set_error("svo_surf_extract_batch: image %d has %d key points (the work arrays hold %d)", k, n[k], SURF_MAXCAND);
             return SVO_ERR_CAPACITY;
         }
-        if (counts[k] > cap && rc == SVO_OK) {
-            svo_set_error("svo_surf_extract_batch: image %d yields %d key points, cap is %d", k, counts[k], cap);
+        if (n[k] > cap && rc == SVO_OK) {
+            svo_set_error("svo_surf_extract_batch: image %d yields %d key points, cap is %d", k, n[k], cap);
             rc = SVO_ERR_CAPACITY;
         }
     }
     if (host) {
-        for (int k = 0; k < n_images; k++) {
-            const size_t m = (size_t)(n[k] < cap ? n[k] : cap), b = (size_t)k * cap;
-            if (!m)
-                continue;
-            SVO_HIP(hipMemcpyAsync(xy + 2 * b, out.xy + 2 * b, m * 8, hipMemcpyDeviceToHost, st));
-            SVO_HIP(hipMemcpyAsync(size + b, out.size + b, m * 4, hipMemcpyDeviceToHost, st));
-            SVO_HIP(hipMemcpyAsync(angle + b, out.angle + b, m * 4, hipMemcpyDeviceToHost, st));
-            SVO_HIP(hipMemcpyAsync(response + b, out.resp + b, m * 4, hipMemcpyDeviceToHost, st));
-            SVO_HIP(hipMemcpyAsync(octave + b, out.oct + b, m * 4, hipMemcpyDeviceToHost, st));
-            SVO_HIP(hipMemcpyAsync(laplacian + b, out.lap + b, m * 4, hipMemcpyDeviceToHost, st));
-            if (desc)
-                SVO_HIP(hipMemcpyAsync(desc + 64 * b, d_desc + 64 * b, m * 256, hipMemcpyDeviceToHost, st));
-        }
-        SVO_HIP(hipStreamSynchronize(st));
+        const HostColumn cols[7] = {{xy, out.xy, 8},      {size, out.size, 4},     {angle, out.angle, 4}, {response, out.resp, 4},
+                                    {octave, out.oct, 4}, {laplacian, out.lap, 4}, {desc, d_desc, 64 * sizeof(float)}};
+        const int rc_copy = copy_rows_to_host(st, cols, 7, n_images, cap, n);
+        if (rc_copy)
+            return rc_copy;
     }
     return rc;
 }
@@ -904,12 +860,14 @@ int svo_surf_describe(svo_ctx *ctx, const uint8_t *image, int w, int h, int c, c
     hipStream_t st = ctx->stream;
     const bool host = mem == SVO_MEM_HOST;
     const size_t e = (size_t)n;
-    const uint8_t *d_img = image;
+    const uint8_t *d_img = nullptr;
     const float *dxy = xy, *dsize = size;
     float *dang = angle_out, *ddesc = desc;
     uint8_t *dkept = kept;
+    if ((rc = stage_images(ctx, &image, 1, (size_t)w * h * c, mem, &d_img)))
+        return rc;
     if (host) {
-        if ((rc = surf_stage_images(ctx, &image, 1, (size_t)w * h * c, &d_img)) || (rc = ctx->surf_work.ensure(e * (4 * 68 + 1) + 6 * 256)))
+        if ((rc = ctx->surf_work.ensure(e * (4 * 68 + 1) + 6 * 256)))
             return rc;
         uint8_t *q = ctx->surf_work.as<uint8_t>();
         float *a = bump<float>(q, 2 * e), *b = bump<float>(q, e);

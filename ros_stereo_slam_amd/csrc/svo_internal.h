@@ -137,19 +137,22 @@ struct svo_ctx {
     DevBuf sor_grid;
     // essential.hip: normalised points, the RANSAC's per-iteration models / counts / state, recoverPose's candidate masks
     DevBuf ess;
-    // sift.hip: the scale space (Gaussian and DoG layers of every image of a batch), the detector's work arrays, staged
-    // images and key points, the output block of host calls
-    DevBuf sift_pyr, sift_work, sift_img, sift_out;
-    // brief.hip: the integral images of a batch, staged images, the filter's and the descriptor kernel's work arrays, the test
-    // tables on the device (three slots of 2048 bytes: 16 / 32 / 64-byte descriptors); brief_pattern: the tables set through
-    // svo_brief_set_pattern (brief_has_pattern[k] == 0: the default), brief_pat_live[k]: slot k of brief_pat holds the current table
-    DevBuf brief_sum, brief_img, brief_work, brief_pat;
+    // sift.hip, brief.hip, surf.hip (feature_batch.hip.h, integral_scan.hip.h): the staged host images of a call (or surf.hip's
+    // gathered grey device images), and the integral images of a batch with surf.hip's grey planes behind them.  One of each for
+    // the three modules: every call fills them anew on the context's one stream, and DevBuf::ensure only ever grows a buffer
+    DevBuf feat_img, feat_sum;
+    // sift.hip: the scale space (Gaussian and DoG layers of every image of a batch), the detector's work arrays and key points,
+    // the output block of host calls
+    DevBuf sift_pyr, sift_work, sift_out;
+    // brief.hip: the filter's and the descriptor kernel's work arrays, the test tables on the device (three slots of 2048 bytes:
+    // 16 / 32 / 64-byte descriptors); brief_pattern: the tables set through svo_brief_set_pattern (brief_has_pattern[k] == 0: the
+    // default), brief_pat_live[k]: slot k of brief_pat holds the current table
+    DevBuf brief_work, brief_pat;
     int8_t brief_pattern[3][2048];
     int brief_has_pattern[3] = {0, 0, 0};
     int brief_pat_live[3] = {0, 0, 0};
-    // surf.hip: the integral images of a batch, staged and grey images, the det / trace planes of every layer, the detector's
-    // candidate lists with the staged outputs of host calls
-    DevBuf surf_sum, surf_img, surf_planes, surf_work;
+    // surf.hip: the det / trace planes of every layer, the detector's candidate lists with the staged outputs of host calls
+    DevBuf surf_planes, surf_work;
 };
 
 // Low-latency host wait for everything queued on the context's stream: records an event and
