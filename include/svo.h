@@ -830,6 +830,47 @@ int svo_pg_write_g2o(const svo_posegraph *pg, const char *path);
 /* the inverse: replace the graph by a .g2o file (VERTEX_SE3:QUAT / EDGE_SE3:QUAT / FIX 0; the
  * information matrices are ignored -- the reference leaves them at identity, poseGraph.h:102,122) */
 int svo_pg_read_g2o(svo_posegraph *pg, const char *path);
+/* ---- per-edge information matrices and measured loop closures ---------------------------------
+ * An edge's error is e = [t ; s q_xyz] of Z^-1 Xi^-1 Xj (g2o's order: translation first); its information Om is a symmetric
+ * positive-definite 6 x 6 matrix in those coordinates, passed as the 21 numbers of its upper triangle, row-major (what an
+ * EDGE_SE3:QUAT line carries).  chi2 = e^T Om e, H = J^T Om J, b = J^T Om e.  A graph on which no information other than
+ * the identity was ever set is optimised by the same kernel, to the same bits, as before these calls existed; the exact
+ * identity is stored as "none".  SVO_ERR_ARG, with a text that names the edge and the graph left as it was: an entry that
+ * is not finite, or a matrix whose 6 x 6 Cholesky factorisation meets a pivot <= 0.                                    */
+/* edge(previous vertex -> vertex from_id) with measurement meas7 (tx ty tz qx qy qz qw, quaternion normalised on entry;
+ * NULL = identity = svo_pg_add_loop_closure) and information info21 (NULL = I).
+ * What addLoopClosure(T, fromID) would do if it read its T (poseGraph.h:113-126; dump.cpp:331-348 produces that T). */
+int svo_pg_add_loop_closure_measured(svo_posegraph *pg, int from_id, const double *meas7, const double *info21);
+int svo_pg_set_edge_information(svo_posegraph *pg, int e, const double *info21);   /* NULL resets to identity */
+int svo_pg_get_edge_information(const svo_posegraph *pg, int e, double *info21);  /* identity when none stored */
+/* svo_pg_read_g2o that KEEPS the information of EDGE_SE3:QUAT lines: a line carries none (identity) or exactly 21 numbers,
+ * any other count is SVO_ERR_ARG with the line number.  svo_pg_write_g2o writes stored information as %.17g and, for an
+ * edge that stores none, the integers 1 / 0 of the identity.                                                         */
+int svo_pg_read_g2o_info(svo_posegraph *pg, const char *path);
+
+/* ---- the measurement of a loop closure: getLCMeasurement, dump.cpp:331-348 -------------------- */
+typedef struct svo_closure_params {
+    double f_thr;       /* 1.0: PyrLKtrackFrame2Frame's filter, src/tracking.cpp:75; <= 0 skips it */
+    int pnp_iterations; /* 100, 0.1, 0.999: dump.cpp:340 */
+    double pnp_reproj_err, pnp_confidence;
+    uint64_t seed;
+} svo_closure_params;
+void svo_closure_default_params(svo_closure_params *p);
+/* newest: the newest frame's image with its n points (xy2 in that image, xyz3 in THAT CAMERA's frame); matched: the image of the
+ * matched frame.  LK newest -> matched, compaction by status, F-matrix RANSAC at f_thr (confidence 0.99, seed + 1), compaction
+ * by mask, PnP-RANSAC (seed + 2), then Rodrigues, R <- R^T, t <- -R tvec: meas7 = X_newest^-1 * X_matched, i.e. the measurement
+ * of the edge svo_pg_add_loop_closure_measured adds.  The quaternion of R (row-major r00 .. r22), in this order of operations:
+ *   tr = r00 + r11 + r22;
+ *   tr > 0:                 s = 2 sqrt(tr + 1),            q = ((r21 - r12) / s, (r02 - r20) / s, (r10 - r01) / s, s / 4)
+ *   else r00 largest:       s = 2 sqrt(1 + r00 - r11 - r22), q = (s / 4, (r01 + r10) / s, (r02 + r20) / s, (r21 - r12) / s)
+ *   else r11 > r22:         s = 2 sqrt(1 + r11 - r00 - r22), q = ((r01 + r10) / s, s / 4, (r12 + r21) / s, (r02 - r20) / s)
+ *   else:                   s = 2 sqrt(1 + r22 - r00 - r11), q = ((r02 + r20) / s, (r12 + r21) / s, s / 4, (r10 - r01) / s)
+ * ("r00 largest": r00 > r11 and r00 > r22), divided by sqrt(((x x + y y) + z z) + w w), negated if w < 0 (so w >= 0).
+ * images / xy2 / xyz3 follow `mem`; K4 / p / meas7 / n_tracked (points PnP saw) / n_inliers: HOST.  The call synchronises.
+ * SVO_ERR_TRACKING_LOST below 6 PnP inliers (meas7 untouched; the counts are written).                             */
+int svo_closure_measure(svo_ctx *ctx, const uint8_t *newest, const uint8_t *matched, int w, int h, int c, const float *xy2,
+                        const float *xyz3, int n, const double *K4, const svo_closure_params *p, double *meas7,
+                        int *n_tracked, int *n_inliers, int mem);
 
 /* ---- data formats either side of the path (host code, no GPU work) -------------------------- */
 /* KITTI odometry pose files: one pose per line, 12 numbers = the 3x4 [R|t]

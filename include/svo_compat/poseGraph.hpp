@@ -8,10 +8,27 @@
 
 namespace svo_compat {
 
+// The 6 x 6 `information` member (Eigen::Matrix<double, 6, 6> upstream, include/poseGraph.h:42): identity by default,
+// element access M(r, c) as Eigen's -- an Eigen matrix is copied into it entry by entry.
+struct Matrix6d {
+    double m[36] = {1, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 1};
+    static Matrix6d Identity() { return Matrix6d(); }
+    double &operator()(int r, int c) { return m[6 * r + c]; }
+    double operator()(int r, int c) const { return m[6 * r + c]; }
+};
+
 class globalPoseGraph {
   public:
     int globalNodeID = 0;          // include/poseGraph.h:38
     bool loopClosureFlag = false;  // :39
+    // :42 -- the information matrix of new edges, in g2o's order (translation, then the quaternion's vector part).  The
+    // reference declares it and leaves its setInformation(information) calls commented out (:103,122): applied to the edges
+    // augmentNode / addLoopClosure add only when INFORMATION_FLAG is set.
+    Matrix6d information = Matrix6d::Identity();
+    bool INFORMATION_FLAG = false;
+    // true: addLoopClosure(T, fromID) uses T as the edge's measurement (what getLCMeasurement, dump.cpp:331-348, produces);
+    // false: the reference's behaviour, T is never read and the measurement is the identity
+    bool MEASURED_LC_FLAG = false;
     std::string outFileName = "poseGraph.g2o";  // :56
     int optimizeIterations = 10;   // optimizer.optimize(10), :130
     bool writeResultFile = true;   // optimizer.save("result.g2o"), :131
@@ -33,12 +50,26 @@ class globalPoseGraph {
         double p[7];
         iso_to_pose7(globalT, p);
         check(svo_pg_augment_node(pg_, p));
+        if (INFORMATION_FLAG) {  // edge->setInformation(information), :103
+            double om[21];
+            info21(om);
+            check(svo_pg_set_edge_information(pg_, svo_pg_num_edges(pg_) - 1, om));
+        }
         globalNodeID++;
     }
-    // :113-126 -- T is unused by the reference: the measurement is the identity
-    void addLoopClosure(const Isometry3d & /*T*/, int fromID)
+    // :113-126 -- T is unused by the reference (the measurement is the identity) unless MEASURED_LC_FLAG is set
+    void addLoopClosure(const Isometry3d &T, int fromID)
     {
-        check(svo_pg_add_loop_closure(pg_, fromID));
+        if (!MEASURED_LC_FLAG && !INFORMATION_FLAG)
+            check(svo_pg_add_loop_closure(pg_, fromID));
+        else {
+            double z[7], om[21];
+            if (MEASURED_LC_FLAG)
+                iso_to_pose7(T, z);
+            if (INFORMATION_FLAG)
+                info21(om);
+            check(svo_pg_add_loop_closure_measured(pg_, fromID, MEASURED_LC_FLAG ? z : nullptr, INFORMATION_FLAG ? om : nullptr));
+        }
         loopClosureFlag = true;
     }
     // :128-138 -- 10 Gauss-Newton iterations over the whole graph, every estimate returned
@@ -67,6 +98,14 @@ class globalPoseGraph {
     svo_posegraph *handle() { return pg_; }
 
   private:
+    // the upper triangle of `information`, row-major: what the C ABI and an EDGE_SE3:QUAT line carry
+    void info21(double *om) const
+    {
+        int k = 0;
+        for (int i = 0; i < 6; i++)
+            for (int j = i; j < 6; j++)
+                om[k++] = information(i, j);
+    }
     svo_ctx *ctx_;
     svo_posegraph *pg_ = nullptr;
 };

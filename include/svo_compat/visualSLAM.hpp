@@ -196,6 +196,42 @@ class visualSLAM {
         inlierReferencePyrLKPts = finalInlierRef;
     }
 
+    // ---- dump.cpp:331-348: the measurement of a loop closure, X_ref^-1 X_match, into lcMeasurementT ----
+    // PyrLKtrackFrame2Frame(imref, imtrk, refKF.refPts, refKF.pts3d) + solvePnPRansac(100, 0.1, 0.999) + Rodrigues, R = R.t(),
+    // tv = -R * tv as ONE library call (svo_closure_measure, seeds ransacSeed + 1 / + 2).  The dump's call site is commented
+    // out (:401) and nothing there looks at the inlier count: here fewer than 6 inliers return false and leave lcMeasurementT
+    // as it was.  With poseGraph.MEASURED_LC_FLAG set, poseGraph.addLoopClosure(lcMeasurementT, matchKF.idx) uses it.
+    struct metaData {
+        int idx = 0;
+        std::vector<Point2f> refPts;
+        std::vector<Point3f> pts3d;  // in the camera frame of frame idx
+    };
+    Isometry3d lcMeasurementT = Isometry3d::Identity();
+    int lcMeasurementTracked = 0, lcMeasurementInliers = 0;
+    bool getLCMeasurement(const Mat &imref, const Mat &imtrk, const std::vector<Point2f> &refPts, const std::vector<Point3f> &pts3d)
+    {
+        if (mat_rows(imref) != mat_rows(imtrk) || mat_cols(imref) != mat_cols(imtrk) || mat_channels(imref) != mat_channels(imtrk) ||
+            refPts.size() != pts3d.size())
+            throw SvoError(SVO_ERR_ARG, "getLCMeasurement: the images differ in size, or the point sets in length");
+        svo_closure_params prm;
+        svo_closure_default_params(&prm);
+        prm.seed = ransacSeed;
+        const double K4[4] = {focal_x, focal_y, cx, cy};
+        double z[7];
+        const int rc = svo_closure_measure(ctx_, mat_data(imref), mat_data(imtrk), mat_cols(imref), mat_rows(imref),
+                                           mat_channels(imref), f(refPts), f3(pts3d), (int)refPts.size(), K4, &prm, z,
+                                           &lcMeasurementTracked, &lcMeasurementInliers, SVO_MEM_HOST);
+        if (rc == SVO_ERR_TRACKING_LOST)
+            return false;
+        check(rc);
+        lcMeasurementT = pose7_to_iso(z);
+        return true;
+    }
+    bool getLCMeasurement(const metaData &refKF, const metaData &matchKF)
+    {
+        return getLCMeasurement(loadImageL(refKF.idx), loadImageL(matchKF.idx), refKF.refPts, refKF.pts3d);
+    }
+
     // ---- src/keyFrameManagement.cpp:33-46 ----
     std::vector<Point3f> update3dtransformation(std::vector<Point3f> &pt3d, const Mat34d &pose4dTransform)
     {

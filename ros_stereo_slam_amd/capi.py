@@ -1644,6 +1644,71 @@ class KeyframeMap:
             pass
 
 
+INFO_TRIU = np.triu_indices(6)
+
+
+def _info21(info):
+    """None, 21 numbers or a 6 x 6 matrix -> None or a contiguous float64 [21] (upper triangle, row-major)"""
+    if info is None:
+        return None
+    a = np.asarray(info, np.float64)
+    if a.shape == (6, 6):
+        a = a[INFO_TRIU]
+    return np.ascontiguousarray(a, np.float64).reshape(21)
+
+
+def info_matrix(info21) -> np.ndarray:
+    """The symmetric 6 x 6 matrix of 21 upper-triangle numbers"""
+    M = np.zeros((6, 6))
+    M[INFO_TRIU] = np.asarray(info21, np.float64).reshape(21)
+    return M + np.triu(M, 1).T
+
+
+class ClosureParams(C.Structure):
+    _fields_ = [("f_thr", C.c_double), ("pnp_iterations", C.c_int), ("pnp_reproj_err", C.c_double),
+                ("pnp_confidence", C.c_double), ("seed", C.c_uint64)]
+
+
+def closure_params(**overrides) -> ClosureParams:
+    p = ClosureParams()
+    load().svo_closure_default_params(C.byref(p))
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise TypeError(f"svo_closure_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+@_ctx_method
+def measure_closure(self, newest, matched, xy, xyz, K4, size=None, **params):
+    """getLCMeasurement (``svo_closure_measure``): the relative pose X_newest^-1 X_matched from the newest frame's image, its
+    points ``xy`` [n, 2] and their 3-D positions ``xyz`` [n, 3] in that camera's frame, and the matched frame's image.
+    Host arrays (images [h, w, c] uint8), or device tensors / addresses with ``size=(w, h, c, n)``.
+    -> (rc, meas7 or None, n_tracked, n_inliers); rc is SVO_OK or SVO_ERR_TRACKING_LOST (fewer than 6 PnP inliers)."""
+    prm = closure_params(**params)
+    if size is None:
+        newest = np.ascontiguousarray(newest, np.uint8)
+        matched = np.ascontiguousarray(matched, np.uint8)
+        if newest.ndim == 2:
+            newest, matched = newest[:, :, None], matched[:, :, None]
+        assert newest.shape == matched.shape
+        h, w, c = newest.shape
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        assert len(xy) == len(xyz)
+        n, mem = len(xy), MEM_HOST
+    else:
+        (w, h, c, n), mem = size, MEM_DEVICE
+    K = np.ascontiguousarray(K4, np.float64).reshape(4)
+    meas = np.zeros(7)
+    ntrk, ninl = C.c_int(), C.c_int()
+    rc = self.lib.svo_closure_measure(self._h, _ptr(newest), _ptr(matched), int(w), int(h), int(c), _ptr(xy), _ptr(xyz), int(n),
+                                      _ptr(K), C.byref(prm), _ptr(meas), C.byref(ntrk), C.byref(ninl), mem)
+    if rc not in (SVO_OK, SVO_ERR_TRACKING_LOST):
+        _check(rc)
+    return rc, (meas if rc == SVO_OK else None), ntrk.value, ninl.value
+
+
 class PoseGraph:
     """SE3 pose graph on the GPU (``svo_posegraph``), mirroring globalPoseGraph
     (include/poseGraph.h:36-179).  Poses: tx ty tz qx qy qz qw."""
@@ -1657,8 +1722,27 @@ class PoseGraph:
     def augment_node(self, pose7):
         _check(self.ctx.lib.svo_pg_augment_node(self._h, _ptr(np.ascontiguousarray(pose7, np.float64))))
 
-    def add_loop_closure(self, from_id: int):
-        _check(self.ctx.lib.svo_pg_add_loop_closure(self._h, int(from_id)))
+    def add_loop_closure(self, from_id: int, meas7=None, info21=None):
+        """Edge (previous vertex -> from_id).  Without arguments: the reference's identity closure
+        (``svo_pg_add_loop_closure``).  ``meas7``: the measured relative pose (tx ty tz qx qy qz qw, e.g. from
+        ``measure_closure``); ``info21``: the upper triangle of the 6 x 6 information matrix, row-major, or the matrix."""
+        if meas7 is None and info21 is None:
+            _check(self.ctx.lib.svo_pg_add_loop_closure(self._h, int(from_id)))
+            return
+        z = None if meas7 is None else np.ascontiguousarray(meas7, np.float64).reshape(7)
+        om = _info21(info21)   # z / om stay referenced until the call has returned
+        _check(self.ctx.lib.svo_pg_add_loop_closure_measured(self._h, int(from_id), _ptr(z), _ptr(om)))
+
+    def set_edge_information(self, e: int, info21):
+        """``svo_pg_set_edge_information``: 21 numbers (upper triangle, row-major), a 6 x 6 matrix, or None = identity."""
+        om = _info21(info21)
+        _check(self.ctx.lib.svo_pg_set_edge_information(self._h, int(e), _ptr(om)))
+
+    def edge_information(self, e: int) -> np.ndarray:
+        """The 21 numbers of edge e's information matrix (the identity's when none is stored)."""
+        out = np.zeros(21)
+        _check(self.ctx.lib.svo_pg_get_edge_information(self._h, int(e), _ptr(out)))
+        return out
 
     def augment_nodes(self, poses7, closure_from=None):
         """``svo_pg_augment_nodes``: poses7 [n, 7]; closure_from [n] int32 (-1: none): the closure edge staged before node i."""
@@ -1697,8 +1781,10 @@ class PoseGraph:
             res.append((a.value, b.value, z))
         return res
 
-    def read_g2o(self, path):
-        _check(self.ctx.lib.svo_pg_read_g2o(self._h, str(path).encode()))
+    def read_g2o(self, path, information: bool = False):
+        """information=True keeps the information matrices of the EDGE_SE3:QUAT lines (``svo_pg_read_g2o_info``)."""
+        fn = self.ctx.lib.svo_pg_read_g2o_info if information else self.ctx.lib.svo_pg_read_g2o
+        _check(fn(self._h, os.fspath(path).encode()))
 
     def write_g2o(self, path):
         _check(self.ctx.lib.svo_pg_write_g2o(self._h, os.fspath(path).encode()))

@@ -1838,6 +1838,173 @@ int svo_pnp_ladder(svo_ctx *ctx, const float *obj_f, const float *img_f, int n_f
     return SVO_OK;
 }
 
+void svo_closure_default_params(svo_closure_params *p)
+{
+    if (!p)
+        return;
+    p->f_thr = 1.0;          // src/tracking.cpp:75
+    p->pnp_iterations = 100; // dump.cpp:340
+    p->pnp_reproj_err = 0.1;
+    p->pnp_confidence = 0.999;
+    p->seed = 0;
+}
+
+// getLCMeasurement (dump.cpp:331-348) from the stages svo_vo_localize is made of: PyrLKtrackFrame2Frame (LK, compaction by
+// status, F-matrix RANSAC, compaction by mask), solvePnPRansac, Rodrigues / transpose / -R tvec, and the pose as the 7 numbers
+// of a pose-graph measurement.  A closure is measured once per detected loop: the call owns its pyramids and work buffer.
+int svo_closure_measure(svo_ctx *ctx, const uint8_t *newest, const uint8_t *matched, int w, int h, int c, const float *xy2,
+                        const float *xyz3, int n, const double *K4, const svo_closure_params *p, double *meas7, int *n_tracked,
+                        int *n_inliers, int mem)
+{
+    SVO_CHECK_ARG(ctx && newest && matched && w > 0 && h > 0 && (c == 1 || c == 3) && n >= 0 && K4 && meas7);
+    SVO_CHECK_ARG(n == 0 || (xy2 && xyz3));
+    SVO_CHECK_ARG(mem == SVO_MEM_HOST || mem == SVO_MEM_DEVICE);
+    svo_closure_params prm;
+    svo_closure_default_params(&prm);
+    if (p)
+        prm = *p;
+    SVO_CHECK_ARG(prm.pnp_iterations > 0 && prm.pnp_reproj_err > 0 && prm.pnp_confidence > 0 && prm.pnp_confidence < 1);
+    SVO_HIP(hipSetDevice(ctx->device));
+    if (n_tracked)
+        *n_tracked = 0;
+    if (n_inliers)
+        *n_inliers = 0;
+    if (n == 0) {
+        svo_set_error("closure measurement: no points");
+        return SVO_ERR_TRACKING_LOST;
+    }
+    struct Owned {  // released on every way out
+        svo_ctx *ctx;
+        svo_pyramid *pn = nullptr, *pm = nullptr;
+        DevBuf buf;
+        ~Owned()
+        {
+            (void)hipStreamSynchronize(ctx->stream);
+            if (pn)
+                svo_pyramid_destroy(ctx, pn);
+            if (pm)
+                svo_pyramid_destroy(ctx, pm);
+            buf.release();
+        }
+    } own{ctx};
+    int rc;
+    if ((rc = svo_pyramid_create(ctx, w, h, c, SVO_MAX_LEVELS, &own.pn)) ||
+        (rc = svo_pyramid_create(ctx, w, h, c, SVO_MAX_LEVELS, &own.pm)))
+        return rc;
+    // one block: [images] [points in] then the sets of the stages, every piece 256-byte aligned
+    const size_t img = ((size_t)w * h * c + 255) & ~(size_t)255, np = (size_t)n + 1;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t s2 = al(np * 8), s3 = al(np * 12), s1 = al(np), si = al(np * 4);
+    const size_t total = 2 * img + 6 * s2 + 3 * s3 + 2 * s1 + si + al(sizeof(PnpRecord)) + 256;
+    if ((rc = own.buf.ensure(total)))
+        return rc;
+    uint8_t *base = own.buf.as<uint8_t>(), *cur = base;
+    auto take = [&](size_t b) {
+        uint8_t *r = cur;
+        cur += b;
+        return r;
+    };
+    uint8_t *d_img0 = take(img), *d_img1 = take(img);
+    float *in2 = reinterpret_cast<float *>(take(s2)), *nxt = reinterpret_cast<float *>(take(s2));
+    float *a_ref = reinterpret_cast<float *>(take(s2)), *a_trk = reinterpret_cast<float *>(take(s2));
+    float *b_ref = reinterpret_cast<float *>(take(s2)), *b_trk = reinterpret_cast<float *>(take(s2));
+    float *in3 = reinterpret_cast<float *>(take(s3)), *a_3d = reinterpret_cast<float *>(take(s3));
+    float *b_3d = reinterpret_cast<float *>(take(s3));
+    uint8_t *status = take(s1), *mask = take(s1);
+    int *idx = reinterpret_cast<int *>(take(si));
+    PnpRecord *d_rec = reinterpret_cast<PnpRecord *>(take(al(sizeof(PnpRecord))));
+    int *d_cnt = reinterpret_cast<int *>(take(256));
+    hipStream_t st = ctx->stream;
+    SVO_HIP(hipMemsetAsync(d_rec, 0, al(sizeof(PnpRecord)) + 256, st));  // the record and the counts
+    const uint8_t *i0 = newest, *i1 = matched;
+    const float *p2 = xy2, *p3 = xyz3;
+    if (mem == SVO_MEM_HOST) {
+        SVO_HIP(hipMemcpyAsync(d_img0, newest, (size_t)w * h * c, hipMemcpyHostToDevice, st));
+        SVO_HIP(hipMemcpyAsync(d_img1, matched, (size_t)w * h * c, hipMemcpyHostToDevice, st));
+        SVO_HIP(hipMemcpyAsync(in2, xy2, (size_t)n * 8, hipMemcpyHostToDevice, st));
+        SVO_HIP(hipMemcpyAsync(in3, xyz3, (size_t)n * 12, hipMemcpyHostToDevice, st));
+        i0 = d_img0;
+        i1 = d_img1;
+        p2 = in2;
+        p3 = in3;
+    }
+    if ((rc = svo_build_pyramid_from_device(ctx, own.pn, i0)) || (rc = svo_build_pyramid_from_device(ctx, own.pm, i1)))
+        return rc;
+    // PyrLKtrackFrame2Frame (src/tracking.cpp:46-91)
+    if ((rc = svo_launch_lk(ctx, own.pn, own.pm, p2, n, nxt, status, nullptr, nullptr)) ||
+        (rc = svo_launch_compact(ctx, status, n, nullptr, p2, 2, a_ref, nxt, 2, a_trk, p3, 3, a_3d, d_cnt)))
+        return rc;
+    const float *trk2 = a_trk, *trk3 = a_3d;
+    const int *d_n = d_cnt;
+    if (prm.f_thr > 0) {
+        if ((rc = svo_launch_fransac(ctx, a_ref, a_trk, n, d_cnt, prm.f_thr, 0.99, 1000, prm.seed + 1, mask, nullptr, nullptr,
+                                     nullptr)) ||
+            (rc = svo_launch_compact(ctx, mask, n, d_cnt, a_ref, 2, b_ref, a_trk, 2, b_trk, a_3d, 3, b_3d, d_cnt + 1)))
+            return rc;
+        trk2 = b_trk;
+        trk3 = b_3d;
+        d_n = d_cnt + 1;
+    }
+    // solvePnPRansac (dump.cpp:340)
+    if ((rc = svo_launch_pnp_ransac(ctx, trk3, trk2, n, d_n, K4, prm.pnp_iterations, prm.pnp_reproj_err, prm.pnp_confidence,
+                                    prm.seed + 2, 20, idx, nullptr, d_rec)))
+        return rc;
+    hipLaunchKernelGGL(store_count_kernel, dim3(1), dim3(1), 0, st, d_n, &d_rec->n_tracked);
+    SVO_HIP(hipMemcpyAsync(ctx->pinned, d_rec, sizeof(PnpRecord), hipMemcpyDeviceToHost, st));
+    SVO_HIP(hipStreamSynchronize(st));
+    const PnpRecord rec = *reinterpret_cast<const PnpRecord *>(ctx->pinned);
+    if (n_tracked)
+        *n_tracked = rec.n_tracked;
+    if (n_inliers)
+        *n_inliers = rec.n_inliers;
+    if (rec.n_inliers < 6) {
+        svo_set_error("closure measurement: %d PnP inliers of %d tracked points", rec.n_inliers, rec.n_tracked);
+        return SVO_ERR_TRACKING_LOST;
+    }
+    // Rodrigues; R = R^T; t = -R * tvec (dump.cpp:342-345)
+    double R[9], t[3];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++)
+            R[3 * i + j] = rec.R[3 * j + i];
+    for (int i = 0; i < 3; i++)
+        t[i] = -(R[3 * i] * rec.tvec[0] + R[3 * i + 1] * rec.tvec[1] + R[3 * i + 2] * rec.tvec[2]);
+    // the quaternion of R (svo.h states the order of operations)
+    double q[4];
+    const double tr = R[0] + R[4] + R[8];
+    if (tr > 0) {
+        const double s = 2. * sqrt(tr + 1.);
+        q[0] = (R[7] - R[5]) / s;
+        q[1] = (R[2] - R[6]) / s;
+        q[2] = (R[3] - R[1]) / s;
+        q[3] = s / 4.;
+    } else if (R[0] > R[4] && R[0] > R[8]) {
+        const double s = 2. * sqrt(1. + R[0] - R[4] - R[8]);
+        q[0] = s / 4.;
+        q[1] = (R[1] + R[3]) / s;
+        q[2] = (R[2] + R[6]) / s;
+        q[3] = (R[7] - R[5]) / s;
+    } else if (R[4] > R[8]) {
+        const double s = 2. * sqrt(1. + R[4] - R[0] - R[8]);
+        q[0] = (R[1] + R[3]) / s;
+        q[1] = s / 4.;
+        q[2] = (R[5] + R[7]) / s;
+        q[3] = (R[2] - R[6]) / s;
+    } else {
+        const double s = 2. * sqrt(1. + R[8] - R[0] - R[4]);
+        q[0] = (R[2] + R[6]) / s;
+        q[1] = (R[5] + R[7]) / s;
+        q[2] = s / 4.;
+        q[3] = (R[3] - R[1]) / s;
+    }
+    const double nrm = sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
+    const double sgn = q[3] / nrm < 0 ? -1. : 1.;
+    for (int k = 0; k < 3; k++)
+        meas7[k] = t[k];
+    for (int k = 0; k < 4; k++)
+        meas7[3 + k] = sgn * (q[k] / nrm);
+    return SVO_OK;
+}
+
 int svo_vo_get_keyframe_cloud(svo_vo *v, float *xyz_cam, int cap, int *n, int mem)
 {
     SVO_CHECK_ARG(v && n);

@@ -4,6 +4,9 @@
 //   initializeGraph :69-84, augmentNode :87-111, addLoopClosure :113-126,
 //   globalOptimize :128-138 (Gauss-Newton, 10 iterations, BlockSolver<6,6> + sparse
 //   Cholesky, identity information), saveStructure :140-179.
+// Beyond the reference: per-edge information matrices (its own `information` member, :42, whose setInformation calls are
+// commented out) and loop closures that carry a measured relative pose -- a second instantiation of the linearisation,
+// launched only for a graph that stores a non-identity matrix.
 //
 // One Gauss-Newton iteration on the context's stream (f64 throughout):
 //   linearize  one thread per edge: error e = toVectorMQT(Z^-1 Xi^-1 Xj), analytic 6x6
@@ -90,10 +93,23 @@ __device__ inline void q_to_R(const double *q, double *R)
 // per-edge outputs: 3 blocks + 2 gradients + chi2, one record of EO_FIELDS doubles per edge
 enum { EO_HII = 0, EO_HIJ = 36, EO_HJJ = 72, EO_BI = 108, EO_BJ = 114, EO_CHI2 = 120, EO_FIELDS = 122 };
 
+// Index of entry (i, j), i <= j, of a symmetric 6 x 6 matrix stored as its upper triangle, row-major (g2o's order)
+__host__ __device__ constexpr int pg_tri(int i, int j)
+{
+    const int a = i <= j ? i : j, b = i <= j ? j : i;
+    return 6 * a - a * (a - 1) / 2 + (b - a);
+}
+
+// WEIGHTED = false: identity information, chi2 = e^T e, H = J^T J -- the kernel of every graph that stores no information.
+// WEIGHTED = true: a second instantiation, launched only for a graph with at least one stored information matrix:
+// `info` holds 21 doubles per edge (pg_tri), chi2 = e^T (Om e), b = J^T (Om e), H = J^T (Om J).  Om J is never held as a
+// whole: per output column q the six values w = Om J[:, q] are formed and dotted with the columns of Ji and Jj.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(128) void pg_linearize_kernel(const double *__restrict__ pose, const int *__restrict__ efrom,
                                                            const int *__restrict__ eto, const double *__restrict__ meas,
                                                            int ne, double *__restrict__ out, double *__restrict__ part,
-                                                           unsigned *__restrict__ ticket, double *__restrict__ chi2_out)
+                                                           unsigned *__restrict__ ticket, double *__restrict__ chi2_out,
+                                                           const double *__restrict__ info)
 {
     __shared__ double s_chi[128];
     __shared__ bool s_last;
@@ -109,9 +125,27 @@ __global__ __launch_bounds__(128) void pg_linearize_kernel(const double *__restr
     const double s = E[6] < 0 ? -1. : 1.;
     const double err[6] = {E[0], E[1], E[2], s * E[3], s * E[4], s * E[5]};
     double chi = 0;
+    double Om[WEIGHTED ? 21 : 1], we[6];  // we = Om e
+    if constexpr (WEIGHTED) {
 #pragma unroll
-    for (int k = 0; k < 6; k++)
-        chi += err[k] * err[k];
+        for (int k = 0; k < 21; k++)
+            Om[k] = info[21 * (size_t)e + k];
+#pragma unroll
+        for (int r = 0; r < 6; r++) {
+            double acc = 0;
+#pragma unroll
+            for (int k = 0; k < 6; k++)
+                acc += Om[pg_tri(r, k)] * err[k];
+            we[r] = acc;
+        }
+#pragma unroll
+        for (int k = 0; k < 6; k++)
+            chi += err[k] * we[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 6; k++)
+            chi += err[k] * err[k];
+    }
     // chi2 of the whole graph rides along: a fixed tree per workgroup, and the workgroup that finishes last adds the
     // workgroups' sums in index order (the ticket resets itself for the next launch) -- no launch of its own, and
     // BEFORE the blocks are formed and stored, so that the fence has one store to wait for
@@ -197,6 +231,54 @@ __global__ __launch_bounds__(128) void pg_linearize_kernel(const double *__restr
     if (live) {
         double *o = out + (size_t)e * EO_FIELDS;
         o[EO_CHI2] = chi;
+        if constexpr (WEIGHTED) {
+#pragma unroll
+            for (int p = 0; p < 6; p++) {
+                double si = 0, sj = 0;
+#pragma unroll
+                for (int k = 0; k < 6; k++) {
+                    si += Ji[6 * k + p] * we[k];
+                    sj += Jj[6 * k + p] * we[k];
+                }
+                o[EO_BI + p] = si;
+                o[EO_BJ + p] = sj;
+            }
+#pragma unroll
+            for (int q = 0; q < 6; q++) {
+                double wi[6], wj[6];  // Om Ji[:, q], Om Jj[:, q]
+#pragma unroll
+                for (int r = 0; r < 6; r++) {
+                    double a = 0, b = 0;
+#pragma unroll
+                    for (int k = 0; k < 6; k++) {
+                        a += Om[pg_tri(r, k)] * Ji[6 * k + q];
+                        b += Om[pg_tri(r, k)] * Jj[6 * k + q];
+                    }
+                    wi[r] = a;
+                    wj[r] = b;
+                }
+#pragma unroll
+                for (int p = 0; p < 6; p++) {
+                    double a = 0, b = 0, c = 0;
+#pragma unroll
+                    for (int k = 0; k < 6; k++) {
+                        a += Ji[6 * k + p] * wi[k];
+                        b += Ji[6 * k + p] * wj[k];
+                        c += Jj[6 * k + p] * wj[k];
+                    }
+                    o[EO_HIJ + 6 * p + q] = b;
+                    // the diagonal blocks are symmetric: the upper triangle is computed, the lower mirrors it bit for bit
+                    if (p <= q) {
+                        o[EO_HII + 6 * p + q] = a;
+                        o[EO_HJJ + 6 * p + q] = c;
+                        if (p < q) {
+                            o[EO_HII + 6 * q + p] = a;
+                            o[EO_HJJ + 6 * q + p] = c;
+                        }
+                    }
+                }
+            }
+        } else
 #pragma unroll
         for (int p = 0; p < 6; p++) {
             double si = 0, sj = 0;
@@ -1659,11 +1741,21 @@ struct svo_posegraph {
     std::vector<double> pose;  // 7 per vertex
     std::vector<int> efrom, eto;
     std::vector<double> meas;  // 7 per edge
+    // Information matrices, lazily: EMPTY while every edge has the identity (no vector exists until a non-identity
+    // matrix arrives, and the identity kernel runs); else 21 per edge (upper triangle, row-major) with has_info[e] == 0
+    // and the identity's numbers for the edges that store none.  n_info: edges with has_info set.
+    std::vector<double> info;
+    std::vector<char> has_info;
+    int n_info = 0;
     int prev = -1;
     // What the device already holds.  The graph only grows between two solves (augmentNode /
     // addLoopClosure append), and after a solve the device poses ARE the host poses, so the next
     // solve uploads the new vertices and edges only.  initializeGraph / read_g2o / a failed solve reset this.
     int dev_nv = 0, dev_ne = 0;
+    // d_info follows the edges the way d_meas does: dev_ninfo edges' matrices are on the device (0: none, or changed
+    // under an edge already uploaded -- the next weighted solve uploads all of them).  The elimination structure below
+    // does not depend on the information and is not rebuilt for it.
+    int dev_ninfo = 0;
     // The elimination structure (separators, segments, gather lists) of the graph as last built; reused
     // as long as no vertex or edge was added.  The host copies stay alive here so that their uploads
     // need no synchronisation of their own.
@@ -1673,12 +1765,79 @@ struct svo_posegraph {
     size_t s_wc_blocks = 0;
     size_t o_seg_start = 0, o_seg_len = 0, o_sepidx = 0, o_lsep = 0, o_rsep = 0, o_rb_row = 0, o_rb_col = 0, o_rptr = 0,
            o_rsrc = 0, o_rowseg = 0, o_cptr = 0, o_clrow = 0, o_cedge = 0, o_ctr = 0, o_cwbase = 0, o_csep = 0, o_terms = 0;
-    DevBuf d_pose, d_from, d_to, d_meas, d_eo, d_incptr, d_inc, d_struct, d_Dg, d_Cc, d_rneg, d_Y,
+    DevBuf d_pose, d_from, d_to, d_meas, d_info, d_eo, d_incptr, d_inc, d_struct, d_Dg, d_Cc, d_rneg, d_Y,
         d_Wl, d_Wr, d_Wc, d_R, d_Lo, d_Tinv, d_rR, d_xR, d_misc, d_dx, d_res;
     int refine = 0;  // iterative-refinement passes per Gauss-Newton iteration (svo_pg_set_refinement)
     int nv() const { return (int)(pose.size() / 7); }
     int ne() const { return (int)efrom.size(); }
 };
+
+static const double PG_INFO_IDENTITY[21] = {1, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 1, 0, 1};
+
+static void pg_drop_info(svo_posegraph *g)
+{
+    g->info.clear();
+    g->has_info.clear();
+    g->n_info = 0;
+    g->dev_ninfo = 0;
+}
+
+// A usable information matrix is finite and positive definite (host 6 x 6 Cholesky: every pivot > 0); `what` names the edge
+static int pg_check_info(const double *info21, const char *what, int e)
+{
+    for (int k = 0; k < 21; k++)
+        if (!std::isfinite(info21[k])) {
+            svo_set_error("pose graph: %s %d: information entry %d is not finite", what, e, k);
+            return SVO_ERR_ARG;
+        }
+    double L[36];
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j <= i; j++) {
+            double v = info21[pg_tri(j, i)];
+            for (int k = 0; k < j; k++)
+                v -= L[6 * i + k] * L[6 * j + k];
+            if (i == j) {
+                if (!(v > 0)) {
+                    svo_set_error("pose graph: %s %d: information matrix is not positive definite (pivot %d = %g)", what, e, i, v);
+                    return SVO_ERR_ARG;
+                }
+                L[6 * i + i] = sqrt(v);
+            } else
+                L[6 * i + j] = v / L[6 * j + j];
+        }
+    return SVO_OK;
+}
+
+// Stores the (checked) information of edge e; NULL or the exact identity = none.  The edge must exist.
+static void pg_store_info(svo_posegraph *g, int e, const double *info21)
+{
+    const bool none = !info21 || !memcmp(info21, PG_INFO_IDENTITY, sizeof(PG_INFO_IDENTITY));
+    if (g->info.empty()) {
+        if (none)
+            return;
+        g->has_info.assign(g->ne(), 0);
+        g->info.resize((size_t)21 * g->ne());
+        for (int k = 0; k < g->ne(); k++)
+            memcpy(&g->info[(size_t)21 * k], PG_INFO_IDENTITY, sizeof(PG_INFO_IDENTITY));
+    }
+    g->n_info += (none ? 0 : 1) - (g->has_info[e] ? 1 : 0);
+    g->has_info[e] = none ? 0 : 1;
+    memcpy(&g->info[(size_t)21 * e], none ? PG_INFO_IDENTITY : info21, sizeof(PG_INFO_IDENTITY));
+    if (g->n_info == 0)
+        pg_drop_info(g);  // all identity again: back to the identity kernel
+    else if (e < g->dev_ninfo)
+        g->dev_ninfo = 0;  // changed under an uploaded edge: the next solve uploads the buffer again
+}
+
+// a new edge was appended to efrom / eto / meas: the information vector, where one exists, follows
+static void pg_append_info(svo_posegraph *g, const double *info21)
+{
+    if (!g->info.empty()) {
+        g->has_info.push_back(0);
+        g->info.insert(g->info.end(), PG_INFO_IDENTITY, PG_INFO_IDENTITY + 21);
+    }
+    pg_store_info(g, g->ne() - 1, info21);
+}
 
 extern "C" {
 
@@ -1699,7 +1858,7 @@ int svo_pg_destroy(svo_posegraph *g)
         return SVO_OK;
     (void)hipSetDevice(g->ctx->device);
     (void)hipStreamSynchronize(g->ctx->stream);
-    DevBuf *bufs[] = {&g->d_pose, &g->d_from, &g->d_to, &g->d_meas, &g->d_eo,  &g->d_incptr, &g->d_inc, &g->d_struct,
+    DevBuf *bufs[] = {&g->d_pose, &g->d_from, &g->d_to, &g->d_meas, &g->d_info, &g->d_eo,  &g->d_incptr, &g->d_inc, &g->d_struct,
                       &g->d_Dg,   &g->d_Cc,   &g->d_rneg, &g->d_Y,     &g->d_Wl,
                       &g->d_Wr,   &g->d_Wc,   &g->d_R,    &g->d_Lo, &g->d_Tinv, &g->d_rR,  &g->d_xR,  &g->d_misc, &g->d_dx, &g->d_res};
     for (DevBuf *b : bufs)
@@ -1715,6 +1874,7 @@ int svo_pg_initialize(svo_posegraph *g)
     g->efrom.clear();
     g->eto.clear();
     g->meas.clear();
+    pg_drop_info(g);
     g->prev = 0;
     g->dev_nv = g->dev_ne = 0;
     g->built_nv = g->built_ne = -1;
@@ -1737,6 +1897,7 @@ int svo_pg_augment_node(svo_posegraph *g, const double *pose7)
     g->efrom.push_back(g->prev);
     g->eto.push_back(cur);
     g->meas.insert(g->meas.end(), z, z + 7);
+    pg_append_info(g, nullptr);
     g->prev = cur;
     return SVO_OK;
 }
@@ -1748,6 +1909,54 @@ int svo_pg_add_loop_closure(svo_posegraph *g, int from_id)
     g->efrom.push_back(g->prev);
     g->eto.push_back(from_id);
     g->meas.insert(g->meas.end(), id, id + 7);
+    pg_append_info(g, nullptr);
+    return SVO_OK;
+}
+
+int svo_pg_add_loop_closure_measured(svo_posegraph *g, int from_id, const double *meas7, const double *info21)
+{
+    SVO_CHECK_ARG(g && from_id >= 0 && from_id < g->nv() && g->prev >= 0);
+    double z[7] = {0, 0, 0, 0, 0, 0, 1};
+    if (meas7) {
+        memcpy(z, meas7, sizeof(z));
+        double nrm = 0;
+        for (int k = 0; k < 7; k++) {
+            if (!std::isfinite(z[k])) {
+                svo_set_error("pose graph: closure %d -> %d: measurement entry %d is not finite", g->prev, from_id, k);
+                return SVO_ERR_ARG;
+            }
+            nrm += k >= 3 ? z[k] * z[k] : 0.;
+        }
+        if (!(nrm > 0)) {
+            svo_set_error("pose graph: closure %d -> %d: the measurement's quaternion is zero", g->prev, from_id);
+            return SVO_ERR_ARG;
+        }
+        q_normalize(z + 3);
+    }
+    int rc;
+    if (info21 && (rc = pg_check_info(info21, "new edge", g->ne())))
+        return rc;
+    g->efrom.push_back(g->prev);
+    g->eto.push_back(from_id);
+    g->meas.insert(g->meas.end(), z, z + 7);
+    pg_append_info(g, info21);
+    return SVO_OK;
+}
+
+int svo_pg_set_edge_information(svo_posegraph *g, int e, const double *info21)
+{
+    SVO_CHECK_ARG(g && e >= 0 && e < g->ne());
+    int rc;
+    if (info21 && (rc = pg_check_info(info21, "edge", e)))
+        return rc;
+    pg_store_info(g, e, info21);
+    return SVO_OK;
+}
+
+int svo_pg_get_edge_information(const svo_posegraph *g, int e, double *info21)
+{
+    SVO_CHECK_ARG(g && e >= 0 && e < g->ne() && info21);
+    memcpy(info21, g->info.empty() ? PG_INFO_IDENTITY : &g->info[(size_t)21 * e], sizeof(PG_INFO_IDENTITY));
     return SVO_OK;
 }
 
@@ -2074,6 +2283,12 @@ int svo_pg_optimize(svo_posegraph *g, int iters, double *chi2)
         (rc = ensure_keep(g->d_to, (size_t)ne * 4, (size_t)g->dev_ne * 4, st)) ||
         (rc = ensure_keep(g->d_meas, (size_t)ne * 56, (size_t)g->dev_ne * 56, st)))
         return rc;
+    // the weighted linearisation runs only for a graph that stores at least one non-identity information matrix
+    const bool weighted = g->n_info > 0;
+    if (!weighted || g->dev_ninfo > ne || g->dev_ninfo > g->dev_ne)
+        g->dev_ninfo = 0;
+    if (weighted && (rc = ensure_keep(g->d_info, (size_t)ne * 168, (size_t)g->dev_ninfo * 168, st)))
+        return rc;
     if ((rc = g->d_eo.ensure((size_t)ne * EO_FIELDS * 8)) || (rc = g->d_incptr.ensure((size_t)(nv + 1) * 4)) ||
         (rc = g->d_inc.ensure((size_t)2 * ne * 4)) || (rc = g->d_struct.ensure(g->h_struct.size() * 4 + 16)) ||
         (rc = g->d_Dg.ensure((size_t)nb * 288)) || (rc = g->d_Cc.ensure((size_t)nb * 288)) ||
@@ -2094,6 +2309,9 @@ int svo_pg_optimize(svo_posegraph *g, int iters, double *chi2)
         SVO_HIP(hipMemcpyAsync(g->d_to.as<int>() + e0, g->eto.data() + e0, cnt * 4, hipMemcpyHostToDevice, st));
         SVO_HIP(hipMemcpyAsync(g->d_meas.as<double>() + 7 * e0, g->meas.data() + 7 * e0, cnt * 56, hipMemcpyHostToDevice, st));
     }
+    if (weighted && ne > g->dev_ninfo)
+        SVO_HIP(hipMemcpyAsync(g->d_info.as<double>() + 21 * (size_t)g->dev_ninfo, g->info.data() + 21 * (size_t)g->dev_ninfo,
+                               (size_t)(ne - g->dev_ninfo) * 168, hipMemcpyHostToDevice, st));
     if (rebuild) {
         SVO_HIP(hipMemcpyAsync(g->d_incptr.p, g->h_incptr.data(), (size_t)(nv + 1) * 4, hipMemcpyHostToDevice, st));
         SVO_HIP(hipMemcpyAsync(g->d_inc.p, g->h_inc.data(), (size_t)2 * ne * 4, hipMemcpyHostToDevice, st));
@@ -2101,7 +2319,7 @@ int svo_pg_optimize(svo_posegraph *g, int iters, double *chi2)
         g->built_nv = nv;
         g->built_ne = ne;
     }
-    g->dev_nv = g->dev_ne = 0;  // until this solve has succeeded the device copy is not to be trusted
+    g->dev_nv = g->dev_ne = g->dev_ninfo = 0;  // until this solve has succeeded the device copy is not to be trusted
     const int *ds = g->d_struct.as<int>();
     double *d_chi = g->d_misc.as<double>();
     int *d_status = reinterpret_cast<int *>(d_chi + iters + 2);
@@ -2134,9 +2352,14 @@ int svo_pg_optimize(svo_posegraph *g, int iters, double *chi2)
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)seg_lds));
     ScopedKernelTime tm(ctx, SVO_K_POSEGRAPH);
     for (int it = 0; it <= iters; it++) {
-        hipLaunchKernelGGL(pg_linearize_kernel, dim3((ne + 127) / 128), dim3(128), 0, st, g->d_pose.as<double>(),
-                           g->d_from.as<int>(), g->d_to.as<int>(), g->d_meas.as<double>(), ne, eo, d_part, d_ticket,
-                           d_chi + it);
+        if (weighted)
+            hipLaunchKernelGGL(pg_linearize_kernel<true>, dim3((ne + 127) / 128), dim3(128), 0, st, g->d_pose.as<double>(),
+                               g->d_from.as<int>(), g->d_to.as<int>(), g->d_meas.as<double>(), ne, eo, d_part, d_ticket,
+                               d_chi + it, g->d_info.as<double>());
+        else
+            hipLaunchKernelGGL(pg_linearize_kernel<false>, dim3((ne + 127) / 128), dim3(128), 0, st, g->d_pose.as<double>(),
+                               g->d_from.as<int>(), g->d_to.as<int>(), g->d_meas.as<double>(), ne, eo, d_part, d_ticket,
+                               d_chi + it, static_cast<const double *>(nullptr));
         if (it == iters)
             break;
         hipLaunchKernelGGL(pg_assemble_kernel, dim3((nb + PG_ASM_ROWS - 1) / PG_ASM_ROWS), dim3(PG_ASM_ROWS * 78), 0, st, nb,
@@ -2221,6 +2444,7 @@ int svo_pg_optimize(svo_posegraph *g, int iters, double *chi2)
     g->pose.swap(hpose);
     g->dev_nv = nv;  // device poses == host poses, edges unchanged: the next solve uploads what is appended
     g->dev_ne = ne;
+    g->dev_ninfo = weighted ? ne : 0;
     return SVO_OK;
 }
 
@@ -2241,9 +2465,13 @@ int svo_pg_write_g2o(const svo_posegraph *g, const char *path)
         const double *z = &g->meas[7 * e];
         fprintf(f, "EDGE_SE3:QUAT %d %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g", g->efrom[e], g->eto[e], z[0], z[1],
                 z[2], z[3], z[4], z[5], z[6]);
-        for (int i = 0; i < 6; i++)
-            for (int j = i; j < 6; j++)
-                fprintf(f, " %d", i == j ? 1 : 0);
+        if (!g->info.empty() && g->has_info[e])
+            for (int k = 0; k < 21; k++)
+                fprintf(f, " %.17g", g->info[(size_t)21 * e + k]);
+        else  // no stored information: the integers of the identity, as the reference's files have them
+            for (int i = 0; i < 6; i++)
+                for (int j = i; j < 6; j++)
+                    fprintf(f, " %d", i == j ? 1 : 0);
         fprintf(f, "\n");
     }
     fclose(f);
@@ -2255,7 +2483,7 @@ int svo_pg_write_g2o(const svo_posegraph *g, const char *path)
  * the upper-triangular information matrix, ignored: the reference leaves it at identity,
  * poseGraph.h:102-104,122], FIX id (only vertex 0 may be fixed, as upstream fixes it, :75).  Vertex
  * ids must be 0..n-1 (any order in the file); other tags are skipped.                          */
-int svo_pg_read_g2o(svo_posegraph *g, const char *path)
+static int pg_read_g2o(svo_posegraph *g, const char *path, const bool keep_info)
 {
     SVO_CHECK_ARG(g && path);
     FILE *f = fopen(path, "r");
@@ -2265,7 +2493,8 @@ int svo_pg_read_g2o(svo_posegraph *g, const char *path)
     }
     std::vector<std::pair<int, std::vector<double>>> verts;
     std::vector<int> ef, et;
-    std::vector<double> em;
+    std::vector<double> em, einfo;  // einfo: 21 per edge
+    std::vector<char> ehas;
     char line[4096], tag[64];
     int rc = SVO_OK, lineno = 0;
     while (fgets(line, sizeof(line), f)) {
@@ -2286,12 +2515,42 @@ int svo_pg_read_g2o(svo_posegraph *g, const char *path)
             q_normalize(p + 3);
             verts.emplace_back(id, std::vector<double>(p, p + 7));
         } else if (!strcmp(tag, "EDGE_SE3:QUAT")) {
-            int i, j;
+            int i, j, used = 0;
             double z[7];
-            if (sscanf(rest, "%d %d %lf %lf %lf %lf %lf %lf %lf", &i, &j, z, z + 1, z + 2, z + 3, z + 4, z + 5, z + 6) != 9) {
+            if (sscanf(rest, "%d %d %lf %lf %lf %lf %lf %lf %lf%n", &i, &j, z, z + 1, z + 2, z + 3, z + 4, z + 5, z + 6, &used) != 9) {
                 svo_set_error("%s:%d: malformed EDGE_SE3:QUAT", path, lineno);
                 rc = SVO_ERR_ARG;
                 break;
+            }
+            if (keep_info) {  // none (identity) or exactly the 21 numbers of the upper triangle
+                double om[22];
+                int cnt = 0;
+                const char *c = rest + used;
+                for (;;) {
+                    char *end = nullptr;
+                    const double v = strtod(c, &end);
+                    if (end == c)
+                        break;
+                    if (cnt < 22)
+                        om[cnt] = v;
+                    cnt++;
+                    c = end;
+                }
+                while (*c == ' ' || *c == '\t' || *c == '\r' || *c == '\n')
+                    c++;
+                if ((cnt != 0 && cnt != 21) || *c) {
+                    svo_set_error("%s:%d: EDGE_SE3:QUAT with %d information numbers (0 or 21 expected)", path, lineno, cnt);
+                    rc = SVO_ERR_ARG;
+                    break;
+                }
+                if (cnt == 21 && pg_check_info(om, "edge", (int)ef.size())) {
+                    const std::string why = svo_last_error();
+                    svo_set_error("%s:%d: %s", path, lineno, why.c_str());
+                    rc = SVO_ERR_ARG;
+                    break;
+                }
+                ehas.push_back(cnt == 21);
+                einfo.insert(einfo.end(), cnt == 21 ? om : PG_INFO_IDENTITY, (cnt == 21 ? om : PG_INFO_IDENTITY) + 21);
             }
             q_normalize(z + 3);
             ef.push_back(i);
@@ -2333,10 +2592,17 @@ int svo_pg_read_g2o(svo_posegraph *g, const char *path)
     g->efrom = ef;
     g->eto = et;
     g->meas = em;
+    pg_drop_info(g);
+    for (size_t e = 0; e < ehas.size(); e++)
+        if (ehas[e])
+            pg_store_info(g, (int)e, &einfo[21 * e]);
     g->prev = n - 1;
     g->dev_nv = g->dev_ne = 0;
     g->built_nv = g->built_ne = -1;
     return SVO_OK;
 }
+
+int svo_pg_read_g2o(svo_posegraph *g, const char *path) { return pg_read_g2o(g, path, false); }
+int svo_pg_read_g2o_info(svo_posegraph *g, const char *path) { return pg_read_g2o(g, path, true); }
 
 }  // extern "C"
