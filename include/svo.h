@@ -216,6 +216,41 @@ int svo_stereo_reproject(svo_ctx *ctx, const int16_t *disp, const uint8_t *image
                          const double *Q16, float disp_scale, float z_min, float z_max, int flip_y,
                          float *xyz_out, float *bgr_out, int *n_out, int mem);
 
+/* ---- the disparity WLS filter around the matcher, src/StereoCV.cpp:25-28,51-59 (commented out upstream) ----
+ * ximgproc::createDisparityWLSFilter(matcher) + createRightMatcher(matcher) + filter(disp, grey, out, rdisp): left-right
+ * confidence from the two matchers' maps and their local variance, then the fast global smoother (three iterations of a
+ * horizontal and a vertical tridiagonal solve per line) of disparity x confidence and of confidence, guided by the left
+ * image.  The recipe, point by point (W1..W6, each marked recalled or ours): tests/wls_numpy.py, DESIGN.md section 10h;
+ * the float32 operation order is fixed there and the results are bit-identical to that restatement.                    */
+typedef struct svo_wls_params {
+    double lambda, sigma_color;
+    int lrc_thresh, depth_discontinuity_radius;
+    float roll_off;
+    int use_confidence;
+    int roi_left, roi_right, roi_top, roi_bottom; /* offsets of the ROI from the image's four edges */
+} svo_wls_params;
+/* createDisparityWLSFilter(matcher)'s values for a left matcher (W2): lambda 8000, sigma 1.5, LRC threshold 24,
+ * roll-off 0.001, radius ceil(block / 2), the ROI offsets from the matcher's disparity range and block.  The reference
+ * then sets lambda 400 and sigma 0.4 (src/StereoCV.cpp:57-58).                                                       */
+void svo_wls_default_params(const svo_sgbm_params *left, svo_wls_params *out);
+/* createRightMatcher(matcher), SGBM case (W1); run it as svo_sgbm_compute(ctx, right_params, RIGHT, LEFT, ...)       */
+void svo_sgbm_right_matcher_params(const svo_sgbm_params *left, svo_sgbm_params *right);
+/* n_pairs (1..16) maps of h x w int16 (disparity x 16) from the left and the right matcher, guide: n_pairs x h x w x c
+ * (c = 1 or 3) -> filtered: n_pairs x h x w int16 (the input left map outside the ROI), confidence (may be NULL):
+ * n_pairs x h x w float, conf x 255, zero outside the ROI and all zero without use_confidence.  disp_right may be NULL
+ * only when use_confidence == 0.  SVO_ERR_ARG, with the outputs untouched: n_pairs outside 1..16, c not 1 or 3, an
+ * empty ROI or a negative offset, lambda < 0, sigma_color <= 0, depth_discontinuity_radius < 0.  SVO_ERR_CAPACITY: a
+ * radius above 255, 2^30 pixels or more per call.                                                                    */
+int svo_wls_filter(svo_ctx *ctx, const svo_wls_params *p, const int16_t *disp_left, const int16_t *disp_right,
+                   const uint8_t *guide, int w, int h, int c, int n_pairs, int16_t *filtered, float *confidence, int mem);
+/* The whole chain on the device: both matchers on the pairs (arguments as svo_sgbm_compute's; the right matcher only
+ * when use_confidence is set or disp_right is asked for), grey conversion, the filter with the grey left image as guide.
+ * disp_left, disp_right and confidence may be NULL.  Refusals are those of svo_sgbm_compute and svo_wls_filter, with
+ * every output untouched.                                                                                             */
+int svo_sgbm_wls_compute(svo_ctx *ctx, const svo_sgbm_params *sgbm, const svo_wls_params *wls, const uint8_t *left,
+                         const uint8_t *right, int w, int h, int c, int n_pairs, int16_t *filtered, int16_t *disp_left,
+                         int16_t *disp_right, float *confidence, int mem);
+
 /* ---- SIFT: detection and descriptors of OpenCV 3.2's xfeatures2d::SIFT (src/StereoCV.cpp:64-88, 123-147) ----
  * The reference pairs features by SIFT::create(N) -> detect / compute -> convertTo(CV_32F) -> BFMatcher().knnMatch(2) -> ratio
  * 0.8 -> findFundamentalMat; svo_sift_extract_batch produces the features, svo_knn_match (SVO_MATCH_L2_F32, dim 128) and

@@ -52,10 +52,21 @@ class StereoProcess {
         Mat disp(lImg.rows, lImg.cols, kDisp16S);
         if (disp.elemSize() != 2)
             throw std::runtime_error("stereoMatch: this Mat type has no 16-bit elements");
+        if (WLS_FLAG) {
+            wlsMatch(prm, disp);
+            return disp;
+        }
         check(svo_sgbm_compute(ctx(), &prm, lImg.data, rImg.data, lImg.cols, lImg.rows, 3, 1,
                                reinterpret_cast<int16_t *>(disp.data), SVO_MEM_HOST));
         return disp;
     }
+    // src/StereoCV.cpp:25-28,51-59, commented out upstream: createDisparityWLSFilter(matcher), createRightMatcher(matcher),
+    // right_matcher->compute(grayIm2, grayIm1, rdisp), setLambda(lambda), setSigmaColor(sigma), filter(disp, grayIm1, filtDisp,
+    // rdisp).  WLS_FLAG = true (opt-in): stereoMatch returns filtDisp (svo_sgbm_wls_compute) and leaves getConfidenceMap()'s
+    // values (CV_32F, conf x 255) in confidenceMap.  lambda and sigma are the reference's own.
+    bool WLS_FLAG = false;
+    double lambda = 400, sigma = 0.4;
+    Mat confidenceMap;
 
     // src/StereoCV.cpp:227-250: Q from stereoRectify, reprojectImageTo3D, points with Z > 5 or Z <= 0.01 skipped,
     // (X, -Y, Z) and lImg's B, G, R as floats in row-major order
@@ -340,6 +351,19 @@ class StereoProcess {
         check(rc);
         tri3dPoints = out3d;
     }
+    void wlsMatch(const svo_sgbm_params &prm, Mat &disp)
+    {
+        svo_wls_params wls;
+        svo_wls_default_params(&prm, &wls);
+        wls.lambda = lambda;
+        wls.sigma_color = sigma;
+        confidenceMap = Mat(lImg.rows, lImg.cols, kConf32F);
+        if (confidenceMap.elemSize() != 4)
+            throw std::runtime_error("stereoMatch: this Mat type has no 32-bit float elements");
+        check(svo_sgbm_wls_compute(ctx(), &prm, &wls, lImg.data, rImg.data, lImg.cols, lImg.rows, 3, 1,
+                                   reinterpret_cast<int16_t *>(disp.data), nullptr, nullptr,
+                                   reinterpret_cast<float *>(confidenceMap.data), SVO_MEM_HOST));
+    }
     // src/StereoCV.cpp:123-147: SIFT(10000) on both images, knnMatch(desc1, desc2, 2), m.distance < 0.8 * n.distance
     void siftRatioPairs(const Mat &im1, const Mat &im2, std::vector<Point2f> &pt1, std::vector<Point2f> &pt2)
     {
@@ -355,6 +379,11 @@ class StereoProcess {
     static constexpr int kDisp16S = CV_16SC1;
 #else
     static constexpr int kDisp16S = 3;  // CV_16SC1
+#endif
+#if defined(SVO_WITH_OPENCV) && defined(CV_32FC1)
+    static constexpr int kConf32F = CV_32FC1;
+#else
+    static constexpr int kConf32F = 5;  // CV_32FC1
 #endif
     svo_ctx *ctx_ = nullptr;
     // a float colour as a uint8_t field of pcl::PointXYZRGB holds it: clamped to 0..255 (NaN to 0), then truncated

@@ -53,6 +53,8 @@ struct KeyPoint {
 constexpr int CV_8U = 0, CV_64F = 6, CV_8UC1 = 0, CV_8UC3 = 16;
 // the disparity maps of StereoProcess::stereoMatch (src/StereoCV.cpp:53: StereoSGBM::compute writes CV_16S)
 constexpr int CV_16S = 3, CV_16SC1 = 3;
+// the confidence map of the disparity WLS filter (StereoProcess::confidenceMap)
+constexpr int CV_32F = 5, CV_32FC1 = 5;
 // A dense continuous matrix with cv::Mat's shallow-copy semantics (by value = ref-counted header
 // copy, no element copy): CV_8UC1 / CV_8UC3 images and the CV_64F matrices (K, R, t, rvec, tvec,
 // [R|t]) the reference passes through its member functions as cv::Mat.
@@ -71,7 +73,7 @@ struct Mat {
     int type() const { return type_; }
     int depth() const { return type_ & 7; }
     int channels() const { return (type_ >> 3) + 1; }
-    size_t elemSize() const { return (size_t)channels() * (depth() == CV_64F ? 8 : depth() == CV_16S ? 2 : 1); }
+    size_t elemSize() const { return (size_t)channels() * (depth() == CV_64F ? 8 : depth() == CV_32F ? 4 : depth() == CV_16S ? 2 : 1); }
     bool empty() const { return data == nullptr || rows == 0 || cols == 0; }
     bool isContinuous() const { return true; }
     uint8_t *ptr() { return data; }

@@ -493,6 +493,113 @@ def stereo_reproject(self, disp, image, Q, disp_scale=1.0, z_min=0.01, z_max=5.0
     return xyz[:k].copy(), (bgr[:k].copy() if bgr is not None else None)
 
 
+class WlsParams(C.Structure):
+    """``svo_wls_params``: the DisparityWLSFilter's settings (``lambda_`` is the header's ``lambda``)."""
+    _fields_ = [("lambda_", C.c_double), ("sigma_color", C.c_double), ("lrc_thresh", C.c_int),
+                ("depth_discontinuity_radius", C.c_int), ("roll_off", C.c_float), ("use_confidence", C.c_int),
+                ("roi_left", C.c_int), ("roi_right", C.c_int), ("roi_top", C.c_int), ("roi_bottom", C.c_int)]
+
+
+def sgbm_right_params(left: SgbmParams) -> SgbmParams:
+    """``svo_sgbm_right_matcher_params``: createRightMatcher(matcher)'s parameters; run as ``ctx.sgbm(right, left, ...)``."""
+    r = SgbmParams()
+    load().svo_sgbm_right_matcher_params(C.byref(left), C.byref(r))
+    return r
+
+
+def wls_params(sgbm: SgbmParams | None = None, **overrides) -> WlsParams:
+    """``svo_wls_default_params`` for a left matcher (default: the reference's), then the overrides."""
+    p = WlsParams()
+    load().svo_wls_default_params(C.byref(sgbm if sgbm is not None else sgbm_params()), C.byref(p))
+    for k, v in overrides.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def _wls_prm(sgbm: SgbmParams | None, wls) -> WlsParams:
+    return wls if isinstance(wls, WlsParams) else wls_params(sgbm, **(wls or {}))
+
+
+@_ctx_method
+def wls_filter(self, disp_left, disp_right, guide, wls=None, sgbm=None, want_confidence=True):
+    """``svo_wls_filter``: int16 maps (h x w or n x h x w) of the left and the right matcher (disp_right may be None
+    without use_confidence), guide h x w (x c) or n x h x w x c uint8 -> (filtered, confidence or None), numpy arrays
+    for host inputs and device tensors for device inputs.  ``wls``: a WlsParams or a dict of overrides of the defaults
+    for the left matcher ``sgbm`` (a SgbmParams; default the reference's)."""
+    prm = _wls_prm(sgbm, wls)
+    dev = _is_device(disp_left)
+    shape = tuple(disp_left.shape)
+    single = len(shape) == 2
+    n, h, w = (1, *shape) if single else shape
+    gshape = tuple(guide.shape)
+    c = 1 if len(gshape) == (2 if single else 3) else gshape[-1]
+    assert gshape[:(2 if single else 3)] == shape
+    if dev:
+        import torch
+
+        lt, gt = disp_left.contiguous(), guide.contiguous()
+        rt = disp_right.contiguous() if disp_right is not None else None
+        out = torch.empty((n, h, w), dtype=torch.int16, device=disp_left.device)
+        conf = torch.empty((n, h, w), dtype=torch.float32, device=disp_left.device) if want_confidence else None
+        torch.cuda.synchronize(disp_left.device)
+        _check(self.lib.svo_wls_filter(self._h, C.byref(prm), _ptr(lt), _ptr(rt), _ptr(gt), w, h, c, n, _ptr(out), _ptr(conf),
+                                       MEM_DEVICE))
+        _check(self.lib.svo_ctx_sync(self._h))
+    else:
+        lt = np.ascontiguousarray(disp_left, np.int16)
+        rt = np.ascontiguousarray(disp_right, np.int16) if disp_right is not None else None
+        gt = np.ascontiguousarray(guide, np.uint8)
+        out = np.empty((n, h, w), np.int16)
+        conf = np.empty((n, h, w), np.float32) if want_confidence else None
+        _check(self.lib.svo_wls_filter(self._h, C.byref(prm), _ptr(lt), _ptr(rt), _ptr(gt), w, h, c, n, _ptr(out), _ptr(conf),
+                                       MEM_HOST))
+    if single:
+        return out[0], (conf[0] if conf is not None else None)
+    return out, conf
+
+
+@_ctx_method
+def sgbm_wls(self, left, right, wls=None, want_maps=True, want_confidence=True, **params):
+    """``svo_sgbm_wls_compute``: both matchers and the filter on one pair or a batch (shapes as ``sgbm``) -> (filtered,
+    disp_left, disp_right, confidence); the last three are None when not asked for (disp_right also without
+    use_confidence's right matcher unless want_maps).  ``wls``: a WlsParams or a dict of overrides of the defaults for
+    these matcher parameters; ``params``: the matcher's."""
+    sp = sgbm_params(**params)
+    prm = _wls_prm(sp, wls)
+    dev = _is_device(left)
+    assert dev == _is_device(right), "left and right must live in the same memory"
+    shape = tuple(left.shape)
+    assert tuple(right.shape) == shape
+    single = len(shape) in (2, 3)
+    if len(shape) == 2:
+        n, h, w, c = 1, shape[0], shape[1], 1
+    elif len(shape) == 3:
+        n, (h, w, c) = 1, shape
+    else:
+        n, h, w, c = shape
+    if dev:
+        import torch
+
+        lt, rt = left.contiguous(), right.contiguous()
+        mk = lambda dt: torch.empty((n, h, w), dtype=dt, device=left.device)
+        i16, f32, mem = torch.int16, torch.float32, MEM_DEVICE
+        torch.cuda.synchronize(left.device)
+    else:
+        lt, rt = np.ascontiguousarray(left, np.uint8), np.ascontiguousarray(right, np.uint8)
+        mk = lambda dt: np.empty((n, h, w), dt)
+        i16, f32, mem = np.int16, np.float32, MEM_HOST
+    out = mk(i16)
+    dl, dr = (mk(i16), mk(i16)) if want_maps else (None, None)
+    conf = mk(f32) if want_confidence else None
+    _check(self.lib.svo_sgbm_wls_compute(self._h, C.byref(sp), C.byref(prm), _ptr(lt), _ptr(rt), w, h, c, n, _ptr(out),
+                                         _ptr(dl), _ptr(dr), _ptr(conf), mem))
+    if dev:
+        _check(self.lib.svo_ctx_sync(self._h))
+    res = (out, dl, dr, conf)
+    return tuple(a[0] if single and a is not None else a for a in res)
+
+
 MATH_FN = {"sin": 0, "cos": 1, "acos": 2, "cbrt": 3, "log": 4, "exp": 5}
 MATH_EXP = MATH_FN["exp"]
 

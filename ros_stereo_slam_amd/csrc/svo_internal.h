@@ -153,6 +153,12 @@ struct svo_ctx {
     int brief_pat_live[3] = {0, 0, 0};
     // surf.hip: the det / trace planes of every layer, the detector's candidate lists with the staged outputs of host calls
     DevBuf surf_planes, surf_work;
+    // wls.hip: the filter's float planes, the two matchers' maps with the filtered map / confidence / grey guide behind them, and
+    // the weight table on the device with the sigma and channel count it was built for (wls_lut_c == 0: none yet)
+    DevBuf wls_work, wls_maps, wls_lut;
+    std::vector<float> wls_lut_host;
+    double wls_lut_sigma = 0;
+    int wls_lut_c = 0;
 };
 
 // Low-latency host wait for everything queued on the context's stream: records an event and
