@@ -120,6 +120,10 @@ def test_cv_resize_is_bilinear_in_11_bit_fixed_point():
     Y = np.clip((np.arange(dh) + 0.5) * sy - 0.5, 0, g.shape[0] - 1)
     ref = ndimage.map_coordinates(g.astype(np.float64), np.meshgrid(Y, X, indexing="ij"), order=1, mode="nearest")
     assert np.abs(out.astype(np.float64) - ref).max() <= 1.0
+    # and exactly the fixed-point recipe as tests/orb_numpy.py restates it (every ratio and odd size: test_orb_numpy.py)
+    import orb_numpy
+
+    assert np.array_equal(out, orb_numpy.resize_linear(g, dw, dh))
     assert np.array_equal(orc.resize_linear(g, g.shape[1], g.shape[0]), g)      # the identity map is exact
     flat = np.full((50, 70), 93, np.uint8)
     assert np.all(orc.resize_linear(flat, 58, 42) == 93)
