@@ -108,6 +108,10 @@ int svo_pyramid_create(svo_ctx *ctx, int width, int height, int channels, int le
                        svo_pyramid **out);
 int svo_pyramid_destroy(svo_ctx *ctx, svo_pyramid *pyr);
 int svo_pyramid_build(svo_ctx *ctx, svo_pyramid *pyr, const uint8_t *image, int mem);
+/* *out = 1 when the image the pyramid was last built from has B == G == R in every pixel (3-channel pyramids only;
+ * 1- and 4-channel pyramids and pyramids never built say 0): the word the build leaves on the device for the tracker,
+ * which then sums one channel of a grey frame stored as BGR.  Read back in stream order (tests and tools). */
+int svo_pyramid_is_mono(svo_ctx *ctx, const svo_pyramid *pyr, int *out);
 /* copy one level out (tests).  out holds w*h*c bytes. */
 int svo_pyramid_get_level(svo_ctx *ctx, const svo_pyramid *pyr, int level, uint8_t *out,
                           int mem, int *w, int *h);
@@ -123,6 +127,16 @@ int svo_grid_keypoints(svo_ctx *ctx, int rows, int cols, int step, float *out_xy
 int svo_lk_track(svo_ctx *ctx, const svo_pyramid *prev, const svo_pyramid *next,
                  const float *prev_pts, int n, float *next_pts, uint8_t *status, float *err,
                  float *min_eig, int mem);
+
+/* Up to 16 independent tracking passes of one geometry in ONE launch, as the lock-step front-ends queue them (device
+ * pointers throughout, asynchronous on the context's stream).  d_err, d_min_eig, d_gates and their entries may be NULL;
+ * a job whose *d_gates[a] == 0 writes nothing.  Tests and tools. */
+int svo_lk_track_jobs(svo_ctx *ctx, int n_jobs, svo_pyramid *const *prev, const svo_pyramid *const *next,
+                      const float *const *d_prev_pts, const int *n, float *const *d_next_pts, uint8_t *const *d_status,
+                      float *const *d_err, float *const *d_min_eig, const int *const *d_gates);
+/* svo_pyramid_build of a device image behind a gate, as the chain runner queues it: with *d_gate == 0 (a device int) the
+ * pyramid is left as it was.  d_gate may be NULL.  Asynchronous on the context's stream. */
+int svo_pyramid_build_gated(svo_ctx *ctx, svo_pyramid *pyr, const uint8_t *d_image, const int *d_gate);
 
 /* ---- order-preserving compaction by a byte mask -------------------------------------------- */
 /* replaces the push_back filters of src/tracking.cpp:20-27 (status), :35-42 and :66-84 (mask).

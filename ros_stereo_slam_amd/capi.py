@@ -94,6 +94,17 @@ class Pyramid:
         _check(self.ctx.lib.svo_pyramid_build(self.ctx._h, self._h, _ptr(image), mem))
         return self
 
+    def build_gated(self, d_image, d_gate):
+        """Build from a device image unless the device int ``d_gate`` is 0 (``svo_pyramid_build_gated``); asynchronous."""
+        _check(self.ctx.lib.svo_pyramid_build_gated(self.ctx._h, self._h, _ptr(d_image), _ptr(d_gate)))
+        return self
+
+    def is_mono(self) -> bool:
+        """True when the image of the last build had B == G == R in every pixel (3-channel pyramids only)."""
+        out = C.c_int()
+        _check(self.ctx.lib.svo_pyramid_is_mono(self.ctx._h, self._h, C.byref(out)))
+        return bool(out.value)
+
     def level(self, l: int) -> np.ndarray:
         w, h = C.c_int(), C.c_int()
         _check(self.ctx.lib.svo_pyramid_get_level(self.ctx._h, self._h, l, None, MEM_HOST,
@@ -184,6 +195,17 @@ class Context:
         _check(self.lib.svo_lk_track(self._h, prev._h, nxt._h, _ptr(pts), n, _ptr(out), _ptr(status),
                                      _ptr(err), _ptr(mineig), MEM_DEVICE))
 
+    def lk_track_jobs(self, jobs):
+        """``svo_lk_track_jobs``: one launch for up to 16 ``(prev, next, pts, out, status, err, mineig, gate)`` tuples of
+        device tensors (err, mineig, gate may be None); asynchronous on the ctx stream."""
+        k = len(jobs)
+        P = C.c_void_p * k
+
+        def col(i):
+            return P(*[(j[i]._h if i < 2 else _ptr(j[i])).value for j in jobs])
+
+        n = (C.c_int * k)(*[int(j[2].shape[0]) for j in jobs])
+        _check(self.lib.svo_lk_track_jobs(self._h, k, col(0), col(1), col(2), n, col(3), col(4), col(5), col(6), col(7)))
 
 # ---- phase-2 entry points: compaction, F-RANSAC, triangulation (host-array forms) ----------
 def _ctx_method(fn):

@@ -2065,4 +2065,44 @@ int svo_vo_get_stage_us(const svo_vo *v, double *us, int cap, int *n_frames)
     return SVO_OK;
 }
 
+// ---- the lock-step launches with their gates, as entry points of their own (tests and tools) --------------------------------
+
+int svo_pyramid_build_gated(svo_ctx *ctx, svo_pyramid *pyr, const uint8_t *d_image, const int *d_gate)
+{
+    SVO_CHECK_ARG(ctx && pyr && d_image);
+    return svo_build_pyramids_from_device(ctx, 1, &pyr, &d_image, &d_gate);
+}
+
+int svo_lk_track_jobs(svo_ctx *ctx, int n_jobs, svo_pyramid *const *prev, const svo_pyramid *const *next,
+                      const float *const *d_prev_pts, const int *n, float *const *d_next_pts, uint8_t *const *d_status,
+                      float *const *d_err, float *const *d_min_eig, const int *const *d_gates)
+{
+    SVO_CHECK_ARG(ctx && n_jobs >= 1 && n_jobs <= SVO_LK_MAX_JOBS && prev && next && d_prev_pts && n && d_next_pts && d_status);
+    LkJob lk[SVO_LK_MAX_JOBS];
+    for (int a = 0; a < n_jobs; a++) {
+        SVO_CHECK_ARG(prev[a] && next[a] && d_prev_pts[a] && d_next_pts[a] && d_status[a] && n[a] >= 0);
+        SVO_CHECK_ARG(prev[a]->w == next[a]->w && prev[a]->h == next[a]->h && prev[a]->c == next[a]->c &&
+                      prev[a]->levels == next[a]->levels);
+        if (!prev[a]->has_deriv) {
+            svo_pyramid *pv = prev[a];
+            int rc = svo_build_derivatives(ctx, 1, &pv);
+            if (rc)
+                return rc;
+        }
+        LkJob &q = lk[a];
+        q.prev = prev[a]->dev;
+        q.next = next[a]->dev;
+        q.dprev = prev[a]->dbase;
+        q.prev_pts = d_prev_pts[a];
+        q.n_cap = n[a];
+        q.d_n = nullptr;
+        q.next_pts = d_next_pts[a];
+        q.status = d_status[a];
+        q.err = d_err ? d_err[a] : nullptr;
+        q.min_eig = d_min_eig ? d_min_eig[a] : nullptr;
+        q.gate = d_gates ? d_gates[a] : nullptr;
+    }
+    return svo_launch_lk_batch(ctx, n_jobs, lk, prev[0]);
+}
+
 }  // extern "C"

@@ -50,6 +50,7 @@ struct LkParams {
     int interleave;              // 1: keypoint = workgroup index (a lone launch: balance before L2 locality), 0: XCD bands
     int lattice;                 // 0: every level interpolates its patches, integer positions too (SVO_LK_LATTICE=0, for A/B and tests)
     int cell_cache;              // 0: every iteration reloads and pairs its two tile rows, same cell or not (SVO_LK_CELL_CACHE=0, for A/B and tests)
+    int mono;                    // 0: grey frames stored as BGR get the three-channel arithmetic too (SVO_LK_MONO=0, for A/B and tests)
 };
 static_assert(sizeof(LkBatch) + sizeof(LkParams) <= 4096, "kernel arguments are limited to 4 KB");
 
@@ -120,44 +121,59 @@ __device__ __forceinline__ double wave_sum_exact(int v)
     return (double)shi * 65536. + (double)slo;
 }
 
-// the same total rounded to float (round to nearest even of the exact integer, like the double
-// path): the total nearly always fits 32 bits, then one v_cvt_f32_i32 does it (scalar test)
-__device__ __forceinline__ float wave_sum_float(int v)
+// MUL (1 or 3) in the sums below: the one-channel body of the tracker (lk_track_kernel, "mono") sums a third of the
+// elements of a grey frame stored as BGR, and every three-channel total is exactly MUL times its total.  The factor is
+// applied to the EXACT INTEGER total, on the scalar unit, before the one rounding to float, so the float is the one the
+// three-channel sum gives, bit for bit.  Ranges with MUL = 3: a lane's one-channel partial is a third of its
+// three-channel one (|v| < 2^30 / 3), so the split halves behave as before, |total| < 2^37 / 3, and MUL * total is below
+// 2^37 like the three-channel total: exact as a long long and as a double.
+
+// the same total (times MUL) rounded to float (round to nearest even of the exact integer, like the double
+// path): it nearly always fits 32 bits, then one v_cvt_f32_i32 does it (scalar test)
+template <int MUL = 1> __device__ __forceinline__ float wave_sum_float(int v)
 {
     const int slo = wave_total_lane63(v & 0xffff), shi = wave_total_lane63(v >> 16);
-    const long long t = (long long)shi * 65536 + slo;
+    const long long t = ((long long)shi * 65536 + slo) * MUL;
     if (t == (long long)(int)t)
         return (float)(int)t;
-    return (float)((double)shi * 65536. + (double)slo);
+    return (float)(((double)shi * 65536. + (double)slo) * (double)MUL);  // |total| < 2^37: exact
 }
 
 // Two exact totals at once.  When every lane's partials lie in [-2^25, 2^25) -- nearly always: a
 // lane would need a mean |residual * derivative| above 1.6e6 per element to leave it -- neither the
 // totals nor any partial sum of the butterflies can leave int32, so one DPP chain per total does
 // it; otherwise the split path.  Both are exact: the choice never changes a result.
-__device__ __forceinline__ void wave_sum2_float(int a, int b, float &fa, float &fb)
+// With MUL = 3 the narrow range is [-2^23, 2^23) per lane -- the same bound per element, a lane has a third of them --
+// so that the 64-lane total lies in [-2^29, 2^29) and three times it in [-3 * 2^29, 3 * 2^29), inside int32: one
+// s_mul_i32 before the v_cvt_f32_i32.
+template <int MUL = 1> __device__ __forceinline__ void wave_sum2_float(int a, int b, float &fa, float &fb)
 {
-    const unsigned wide = ((unsigned)(a + (1 << 25)) | (unsigned)(b + (1 << 25))) >> 26;
+    constexpr int NB = MUL == 1 ? 25 : 23;
+    static_assert(MUL == 1 || MUL == 3, "the narrow range is worked out for these");
+    const unsigned wide = ((unsigned)(a + (1 << NB)) | (unsigned)(b + (1 << NB))) >> (NB + 1);
     if (__builtin_amdgcn_ballot_w64(wide != 0) == 0) {
-        fa = (float)wave_total_lane63(a);
-        fb = (float)wave_total_lane63(b);
+        fa = (float)(wave_total_lane63(a) * MUL);
+        fb = (float)(wave_total_lane63(b) * MUL);
     } else {
-        fa = wave_sum_float(a);
-        fb = wave_sum_float(b);
+        fa = wave_sum_float<MUL>(a);
+        fb = wave_sum_float<MUL>(b);
     }
 }
 
+template <int MUL = 1>
 __device__ __forceinline__ void wave_sum3_float(int a, int b, int c, float &fa, float &fb, float &fc)
 {
-    const unsigned wide = ((unsigned)(a + (1 << 25)) | (unsigned)(b + (1 << 25)) | (unsigned)(c + (1 << 25))) >> 26;
+    constexpr int NB = MUL == 1 ? 25 : 23;
+    static_assert(MUL == 1 || MUL == 3, "the narrow range is worked out for these");
+    const unsigned wide = ((unsigned)(a + (1 << NB)) | (unsigned)(b + (1 << NB)) | (unsigned)(c + (1 << NB))) >> (NB + 1);
     if (__builtin_amdgcn_ballot_w64(wide != 0) == 0) {
-        fa = (float)wave_total_lane63(a);
-        fb = (float)wave_total_lane63(b);
-        fc = (float)wave_total_lane63(c);
+        fa = (float)(wave_total_lane63(a) * MUL);
+        fb = (float)(wave_total_lane63(b) * MUL);
+        fc = (float)(wave_total_lane63(c) * MUL);
     } else {
-        fa = (float)wave_sum_exact(a);
-        fb = (float)wave_sum_exact(b);
-        fc = (float)wave_sum_exact(c);
+        fa = (float)(wave_sum_exact(a) * (double)MUL);  // |total| < 2^37: the product is exact
+        fb = (float)(wave_sum_exact(b) * (double)MUL);
+        fc = (float)(wave_sum_exact(c) * (double)MUL);
     }
 }
 
@@ -358,6 +374,10 @@ __device__ __forceinline__ bool uniform(bool c) { return __builtin_amdgcn_ballot
 typedef short short2v __attribute__((ext_vector_type(2)));
 constexpr int npairs(int c) { return (SEG * c + 1) / 2; }
 constexpr int ndwords(int c) { return ((SEG + 1) * c + 3) / 4; }  // packed dwords of one (SEG+1)-pixel row run
+// The arithmetic below is written for CA channels per pixel out of the S the level STORES: CA == S everywhere but in the
+// one-channel body for grey frames stored as BGR (CA = 1, S = 3), which takes channel 0 of every pixel.  Element k of a
+// lane's run is byte (of an image row run) / entry (of a derivative row run) elem_at(k, CA, S).
+constexpr int elem_at(int k, int ca, int s) { return (k / ca) * s + k % ca; }
 
 __device__ __forceinline__ int sdot2(int a, int b, int c)
 {
@@ -414,13 +434,13 @@ __device__ __forceinline__ int column_pair(const unsigned (&up)[ndwords(C)], con
 
 // The (SEG+1)*C column pairs of a lane's two row runs.  They depend on the staged tile and on the integer
 // cell of the sampling position only, not on its fractions.
-template <int C>
-__device__ __forceinline__ void lane_column_pairs(const unsigned (&up)[ndwords(C)], const unsigned (&lo)[ndwords(C)],
-                                                  int (&V)[(SEG + 1) * C])
+template <int CA, int S>
+__device__ __forceinline__ void lane_column_pairs(const unsigned (&up)[ndwords(S)], const unsigned (&lo)[ndwords(S)],
+                                                  int (&V)[(SEG + 1) * CA])
 {
-    ForEachElem<C, (SEG + 1) * C>::run([&](auto kc) {
+    ForEachElem<CA, (SEG + 1) * CA>::run([&](auto kc) {
         constexpr int k = decltype(kc)::value;
-        V[k] = column_pair<C, k>(up, lo);
+        V[k] = column_pair<S, elem_at(k, CA, S)>(up, lo);
     });
 }
 
@@ -451,13 +471,13 @@ __device__ __forceinline__ void samples_of_pairs(const int (&V)[(SEG + 1) * C], 
     }
 }
 
-template <int C, int SHIFT>
-__device__ __forceinline__ void lane_samples(const unsigned (&up)[ndwords(C)], const unsigned (&lo)[ndwords(C)],
-                                             int wv0, int wv1, int (&out)[npairs(C)])
+template <int CA, int S, int SHIFT>
+__device__ __forceinline__ void lane_samples(const unsigned (&up)[ndwords(S)], const unsigned (&lo)[ndwords(S)],
+                                             int wv0, int wv1, int (&out)[npairs(CA)])
 {
-    int V[(SEG + 1) * C];
-    lane_column_pairs<C>(up, lo, V);
-    samples_of_pairs<C, SHIFT>(V, wv0, wv1, out);
+    int V[(SEG + 1) * CA];
+    lane_column_pairs<CA, S>(up, lo, V);
+    samples_of_pairs<CA, SHIFT>(V, wv0, wv1, out);
 }
 
 // low (HI = false) or high (HI = true) int16 halves of two dwords as a pair: (x.half, y.half)
@@ -470,19 +490,19 @@ template <bool HI> __device__ __forceinline__ int half_pair(int x, int y)
 // One lane's share of  sum |J - I|  over its 7*C patch elements (the err output of the reference,
 // level 0, once per keypoint): lane_samples, then per element pair one v_pk_sub_i16 against the
 // packed template.
-template <int C>
+template <int CA, int S>
 __device__ __forceinline__ int lane_abs_residual(const uint8_t *lds, int off, int wv0, int wv1,
-                                                 const int (&Ivp)[npairs(C)])
+                                                 const int (&Ivp)[npairs(CA)])
 {
-    constexpr int NE = SEG * C;
-    unsigned r0[ndwords(C)], r1[ndwords(C)];
-    load_row_packed<C>(lds, off, r0);
-    load_row_packed<C>(lds, off + Tile<C, TS>::ROW, r1);
-    int Jp[npairs(C)];
-    lane_samples<C, W_BITS - 5>(r0, r1, wv0, wv1, Jp);
+    constexpr int NE = SEG * CA;
+    unsigned r0[ndwords(S)], r1[ndwords(S)];
+    load_row_packed<S>(lds, off, r0);
+    load_row_packed<S>(lds, off + Tile<S, TS>::ROW, r1);
+    int Jp[npairs(CA)];
+    lane_samples<CA, S, W_BITS - 5>(r0, r1, wv0, wv1, Jp);
     int s = 0;
 #pragma unroll
-    for (int j = 0; j < npairs(C); j++) {
+    for (int j = 0; j < npairs(CA); j++) {
         const short2v d = __builtin_bit_cast(short2v, Jp[j]) - __builtin_bit_cast(short2v, Ivp[j]);
         const int d0 = d.x, d1 = d.y;
         s += (d0 < 0 ? -d0 : d0) + (2 * j + 1 < NE ? (d1 < 0 ? -d1 : d1) : 0);
@@ -493,13 +513,13 @@ __device__ __forceinline__ int lane_abs_residual(const uint8_t *lds, int off, in
 // The iteration samples the staged J tile in two halves.  "Load and pair": the lane's two row runs at the
 // guess's integer cell, as column pairs.  They do not depend on the guess's fractions, so the iteration loop
 // keeps them while the guess stays in its cell and the tile is not re-staged.
-template <int C>
-__device__ __forceinline__ void lane_load_pairs(const uint8_t *lds, int off, int (&V)[(SEG + 1) * C])
+template <int CA, int S>
+__device__ __forceinline__ void lane_load_pairs(const uint8_t *lds, int off, int (&V)[(SEG + 1) * CA])
 {
-    unsigned r0[ndwords(C)], r1[ndwords(C)];
-    load_row_packed<C>(lds, off, r0);
-    load_row_packed<C>(lds, off + Tile<C, TS>::ROW, r1);
-    lane_column_pairs<C>(r0, r1, V);
+    unsigned r0[ndwords(S)], r1[ndwords(S)];
+    load_row_packed<S>(lds, off, r0);
+    load_row_packed<S>(lds, off + Tile<S, TS>::ROW, r1);
+    lane_column_pairs<CA, S>(r0, r1, V);
 }
 
 // "Weigh and dot", the iteration's form of the residual sums:  sum (J - I) * Ix = sum J * Ix - sum I * Ix, and
@@ -541,8 +561,13 @@ __device__ __forceinline__ void lane_mismatch(const int (&V)[(SEG + 1) * C], int
 // more than one (svo_vo_run_chunks, chunks that share a context).
 // WANT_ERR = false: no job of the launch asks for the level-0 residual (the front-end never does).  The template
 // patch then dies with step 1 of a level instead of occupying its registers through the iteration loop.
+// Register budget: <1, *, *> compile to the 64 / 70 registers they had before the kernel held two bodies.  With both bodies
+// <3, *, false> wants 98 registers (one body alone: 96): the launch bound forces it back to 96 = five waves per SIMD, without
+// scratch.  Measured on colour frames: without the bound (104 allocated, four waves) the 16-job launch
+// is 28 us of 700 slower, with it 8 us -- the bound is not what colour frames pay.  <3, *, true> takes 102 (100 before), the
+// same allocation of 104.
 template <int C, int NJ, bool WANT_ERR>
-__global__ __launch_bounds__(64 * WAVES, 4) void lk_track_kernel(LkBatchN<NJ> batch, LkParams prm)
+__global__ __launch_bounds__(64 * WAVES, C == 3 && !WANT_ERR ? 5 : 4) void lk_track_kernel(LkBatchN<NJ> batch, LkParams prm)
 {
     const LkJob &job = batch.j[blockIdx.y];
     if (job.gate && *job.gate == 0)
@@ -587,355 +612,38 @@ __global__ __launch_bounds__(64 * WAVES, 4) void lk_track_kernel(LkBatchN<NJ> ba
     int st = 1;
     float errv = 0.f, mineig0 = 0.f;
 
-    for (int level = prm.max_level; level >= 0; level--) {
-        const int lw = prev.w[level], lh = prev.h[level];
-        const uint8_t *I = prev.lvl[level];
-        const uint8_t *J = next.lvl[level];
-        const int pitch = prev.pitch[level];
-        const float scale = 1.f / (float)(1 << level);
-        float px = ptx * scale, py = pty * scale;
-        float nxp, nyp;
-        if (level == prm.max_level) {
-            nxp = px;
-            nyp = py;
+    // The levels (lk_levels.hip.h, included once per body), written once for CA channels of arithmetic per pixel out of the C the pyramids store.  CA == C is the
+    // tracker as it always was.  CA = 1 with C = 3 is the one-channel body for GREY frames stored as BGR: with B == G == R in
+    // both images every patch element, derivative and product of the window exists three times with the same value, and
+    // since every sum below is an exact integer that is rounded once, the three-channel total is exactly three times the
+    // total over channel 0.  That body reads bytes 3 p of the staged image tiles and every third entry of the derivative
+    // tile (tiles, staging, LDS layout and the lane <-> window mapping are the same: the pyramids keep their layout for
+    // everybody else), keeps 7 patch elements per lane instead of 21, and multiplies the exact totals -- the normal
+    // matrix, the two mismatch sums of every iteration, the level-0 residual -- by MUL = 3 before their rounding
+    // (wave_sum*_float<MUL>).  Everything after the rounding is this same code: the same result bit for bit.
+    if constexpr (C == 3) {
+        // Wave-uniform, per job (the jobs of one launch may differ): the "channels agree" words of both pyramids, which sit
+        // in front of level 0's padded buffer (svo_internal.h) -- two scalar loads and a scalar branch.
+        bool mono = false;
+        if (prm.mono) {
+            const int *wp = svo_pyr_words(prev.lvl[0] - (ptrdiff_t)SVO_PYR_PAD * prev.pitch[0] - SVO_PYR_PAD * C);
+            const int *wn = svo_pyr_words(next.lvl[0] - (ptrdiff_t)SVO_PYR_PAD * next.pitch[0] - SVO_PYR_PAD * C);
+            mono = uniform(wp[SVO_PYR_MONO] & wn[SVO_PYR_MONO]) != 0;
+        }
+        // the three-channel body first: it is the fall-through of the branch (colour frames measured 2 us of 700 faster so)
+        if (!mono) {
+            constexpr int CA = 3, MUL = C / CA;
+            static_assert(CA == C || (CA == 1 && C == 3), "the one-channel body is for three equal channels");
+#include "lk_levels.hip.h"
         } else {
-            nxp = outx * 2.f;
-            nyp = outy * 2.f;
+            constexpr int CA = 1, MUL = C / CA;
+            static_assert(CA == C || (CA == 1 && C == 3), "the one-channel body is for three equal channels");
+#include "lk_levels.hip.h"
         }
-        outx = nxp;
-        outy = nyp;
-        px -= half;
-        py -= half;
-        const int ipx = uniform_int_of(floorf(px)), ipy = uniform_int_of(floorf(py));
-        if (ipx < -WIN || ipx >= lw || ipy < -WIN || ipy >= lh) {
-            if (level == 0) {
-                st = 0;
-                errv = 0.f;
-            }
-            continue;
-        }
-        // ---- 1. previous-image tile -> template patch; derivative tile -> derivative patches, normal matrix ----
-        // Both tiles' loads are issued at once: T is written to LDS as soon as it has arrived, the eight vectors
-        // of D stay in flight (in registers) while the template patch is formed from T, and take T's place after.
-        //
-        // A window that starts on an integer position (both fractions exactly 0: the lattice points of a keyframe at
-        // the levels whose scale divides the grid step) has the weights (2^14, 0, 0, 0), and the interpolation is the
-        // identity:  (2^14 p + 2^8) >> 9 == 32 p  and  (2^14 4d + 4 2^13) >> 16 == d.  Such a level unpacks what it
-        // staged instead of interpolating it (IDENT): the same patches bit for bit, a quarter of the instructions.
-        // The choice is the kernel's own, from the fractions, valid for any point; it is made BEFORE the loads are
-        // issued, so that no branch falls inside the window in which the loads are in flight.
-        const float fa = px - (float)ipx, fb = py - (float)ipy;
-        int Ivp[npairs(C)], Ixp[npairs(C)], Iyp[npairs(C)];  // packed int16 pairs (low = even element)
-        auto patches = [&](auto ident_c) {
-            constexpr bool IDENT = decltype(ident_c)::value;
-            constexpr int NE = SEG * C, NV = (SEG + 1) * C;
-            int wv0 = 0, wv1 = 0;  // (w00 | w10 << 16), (w01 | w11 << 16)
-            if constexpr (!IDENT) {
-                int w00, w01, w10, w11;
-                bilinear_weights(fa, fb, w00, w01, w10, w11);
-                wv0 = (w00 & 0xffff) | (w10 << 16);
-                wv1 = (w01 & 0xffff) | (w11 << 16);
-            }
-            wave_lds_sync();
-            TileLoad<C, PT> tload;
-            tile_issue<C, PT>(tload, I, pitch, ipx - 1, ipy - 1, lane);
-            DtileLoad<C> dload;
-            dtile_issue<C>(dload, dprev + prm.doff[level], prm.dpitch[level], ipx, ipy, lane);
-            tile_commit<C, PT, DtileLoad<C>::N>(tload, T, lane);
-            const uint8_t *Ts = T + tload.shift;
-            wave_lds_sync();
-
-            const int toff = (int)(Ts - lds) + (wy + 1) * TROW + (wx + 1) * C;
-            if constexpr (IDENT) {
-                // element k is byte k of the lane's row run, times 32: one permute spreads two bytes over the
-                // halves of a dword, one shift scales both (32 * 255 stays inside its half)
-                unsigned t0[ndwords(C)];
-                load_row_packed<C>(lds, toff, t0);
-                ForEachElem<C, npairs(C)>::run([&](auto jc) {
-                    constexpr int j = decltype(jc)::value, k0 = 2 * j, k1 = 2 * j + 1;
-                    constexpr unsigned hi = k1 < NE ? 4u + (unsigned)(k1 & 3) : 0x0cu;
-                    constexpr unsigned sel = (unsigned)(k0 & 3) | (0x0cu << 8) | (hi << 16) | (0x0cu << 24);
-                    Ivp[j] = (int)(__builtin_amdgcn_perm(t0[(k1 < NE ? k1 : k0) >> 2], t0[k0 >> 2], sel) << 5);
-                });
-            } else {
-                unsigned t0[ndwords(C)], t1[ndwords(C)];
-                load_row_packed<C>(lds, toff, t0);
-                load_row_packed<C>(lds, toff + TROW, t1);
-                lane_samples<C, W_BITS - 5>(t0, t1, wv0, wv1, Ivp);
-            }
-            // the Scharr derivatives of the window's 22x22 neighbourhood come from the derivative level
-            // (zero outside the image: the level's border is zero); the tile takes the place of T.
-            // The template patch is finished before the staging starts: its operands are inputs of the asm that
-            // hands the staging its lane index (otherwise the compiler carries raw tile rows across the loads).
-            int dl = lane;
-            static_assert(npairs(C) == 11 || npairs(C) == 4, "list the template registers below");
-            if constexpr (npairs(C) == 11)
-                asm volatile("" : "+v"(dl) : "v"(Ivp[0]), "v"(Ivp[1]), "v"(Ivp[2]), "v"(Ivp[3]), "v"(Ivp[4]), "v"(Ivp[5]),
-                             "v"(Ivp[6]), "v"(Ivp[7]), "v"(Ivp[8]), "v"(Ivp[9]), "v"(Ivp[10]));
-            else
-                asm volatile("" : "+v"(dl) : "v"(Ivp[0]), "v"(Ivp[1]), "v"(Ivp[2]), "v"(Ivp[3]));
-            wave_lds_sync();
-            dtile_commit<C>(dload, DB, dl);
-            const int *D = reinterpret_cast<const int *>(DB + dload.shift);
-            wave_lds_sync();
-            constexpr int DROW = DTile<C>::ROW / 4;
-            int dlane = wy * DROW + wx * C;  // this lane's first tile entry
-            // Derivative tile entries are (4 dx | 4 dy << 16) (pyramid.hip; |4 d| <= 16320: int16).
-            if constexpr (IDENT) {
-                // element k is entry k of the lane's row run: the low (x) / high (y) halves of two entries packed by
-                // one permute, the factor 4 dropped by one packed arithmetic shift.  The spare lane (63) selects
-                // zero bytes: Ix = Iy = 0 there, as its zero weights give in the interpolating path.
-                const int *d0 = D + dlane;
-                int e[NE + 1];
-#pragma unroll
-                for (int k = 0; k < NE; k++)
-                    e[k] = d0[k];
-                e[NE] = 0;
-                // (The selectors do not depend on the level.  Left to itself the compiler forms them once, before
-                // the level loop, and keeps them and their constants in registers across the iteration loop, which
-                // has none to spare: so from an opaque copy of the lane, the constants as literals of the VOP2 forms.)
-                int sl = lane;
-                asm volatile("" : "+v"(sl));
-                const int spare = sl < 3 * WIN ? 0 : -1;
-                unsigned selx, sely;  // 0x05040100 / 0x07060302: the low / high halves of two dwords; 0x0c: a zero byte
-                asm("v_and_b32 %0, 0x09080d0c, %1\n\tv_xor_b32 %0, 0x05040100, %0" : "=v"(selx) : "v"(spare));
-                asm("v_and_b32 %0, 0x0b0a0f0e, %1\n\tv_xor_b32 %0, 0x07060302, %0" : "=v"(sely) : "v"(spare));
-                const short2v two = {2, 2};
-#pragma unroll
-                for (int j = 0; j < npairs(C); j++) {
-                    const unsigned lo = (unsigned)e[2 * j], hi = (unsigned)e[2 * j + 1 < NE ? 2 * j + 1 : NE];
-                    Ixp[j] = __builtin_bit_cast(int, (short2v)(__builtin_bit_cast(short2v, __builtin_amdgcn_perm(hi, lo, selx)) >> two));
-                    Iyp[j] = __builtin_bit_cast(int, (short2v)(__builtin_bit_cast(short2v, __builtin_amdgcn_perm(hi, lo, sely)) >> two));
-                }
-            } else {
-                // As for the image samples, the VERTICAL neighbours of column k are paired once (element k uses
-                // columns k and k + C): 2 permutes per column instead of 4 per element.  With the factor 4 the
-                // descale by 2^14 is "take the high half" -- the permute that packs two elements does it, no shift:
-                //   (4 (sum w d) + 4 RD) >> 16  ==  (sum w d + RD) >> 14.
-                constexpr int RD4 = 4 << (W_BITS - 1);
-                // the spare lane (63) interpolates its derivative patch with zero weights: Ix = Iy = 0 there, so
-                // its share of every sum below and in the iterations is 0 without any masking
-                const int wq0 = active ? wv0 : 0, wq1 = active ? wv1 : 0;
-                // x then y, each from its own read of the tile rows: half the registers in flight
-                {
-                    const int *d0 = D + dlane, *d1 = d0 + DROW;
-                    int vx[NV], sx[NE + 1];
-                    ForEachElem<C, NV>::run([&](auto kc) {
-                        constexpr int k = decltype(kc)::value;
-                        vx[k] = half_pair<false>(d0[k], d1[k]);
-                    });
-                    sx[NE] = 0;
-#pragma unroll
-                    for (int k = 0; k < NE; k++)
-                        sx[k] = sdot2(vx[k + C], wq1, sdot2_sconst(vx[k], wq0, RD4));
-#pragma unroll
-                    for (int j = 0; j < npairs(C); j++)
-                        Ixp[j] = half_pair<true>(sx[2 * j], sx[2 * j + 1 < NE ? 2 * j + 1 : NE]);
-                }
-                // the y pass starts when the x pass is done (left alone the compiler merges the two and needs 106
-                // registers; at most 104 keep a fifth wave slot's worth of every SIMD free for the short kernels)
-                asm volatile("" : "+v"(dlane), "+v"(Ixp[npairs(C) - 1]));
-                {
-                    const int *d0 = D + dlane, *d1 = d0 + DROW;
-                    int vy[NV], sy[NE + 1];
-                    ForEachElem<C, NV>::run([&](auto kc) {
-                        constexpr int k = decltype(kc)::value;
-                        vy[k] = half_pair<true>(d0[k], d1[k]);
-                    });
-                    sy[NE] = 0;
-#pragma unroll
-                    for (int k = 0; k < NE; k++)
-                        sy[k] = sdot2(vy[k + C], wq1, sdot2_sconst(vy[k], wq0, RD4));
-#pragma unroll
-                    for (int j = 0; j < npairs(C); j++)
-                        Iyp[j] = half_pair<true>(sy[2 * j], sy[2 * j + 1 < NE ? 2 * j + 1 : NE]);
-                }
-            }
-        };
-        if (prm.lattice && uniform(fa == 0.f && fb == 0.f))
-            patches(std::true_type());
-        else
-            patches(std::false_type());
-        int a11 = 0, a12 = 0, a22 = 0;
-#pragma unroll
-        for (int j = 0; j < npairs(C); j++) {
-            a11 = sdot2(Ixp[j], Ixp[j], a11);  // sums of squares of int16 pairs, exact
-            a12 = sdot2(Ixp[j], Iyp[j], a12);
-            a22 = sdot2(Iyp[j], Iyp[j], a22);
-        }
-        int neg_c1 = 0, neg_c2 = 0;  // - sum I * Ix, - sum I * Iy of this lane (see lane_mismatch)
-#pragma unroll
-        for (int j = 0; j < npairs(C); j++) {
-            neg_c1 = sdot2(Ivp[j], Ixp[j], neg_c1);
-            neg_c2 = sdot2(Ivp[j], Iyp[j], neg_c2);
-        }
-        neg_c1 = -neg_c1;
-        neg_c2 = -neg_c2;
-        // The template patch has one use left, the level-0 residual after the iterations.  At C = 3 it waits for it in the
-        // LDS the J tile leaves free (the wave's area is sized by the derivative tile, which is consumed by now) instead
-        // of in 11 registers the iteration loop needs: lane l's dwords at PARK + 4 l + 256 k, conflict-free.
-        constexpr bool PARK_IVP = WANT_ERR && C == 3;
-        constexpr int PARK = Tile<C, TS>::BYTES;
-        static_assert(!PARK_IVP || PARK + npairs(C) * 256 <= Lds<C>::WAVE_BYTES, "no room for the parked template patch");
-        if constexpr (PARK_IVP) {
-            if (level == 0) {
-                wave_lds_sync();
-                int *park = reinterpret_cast<int *>(lds + PARK) + lane;
-#pragma unroll
-                for (int k = 0; k < npairs(C); k++)
-                    park[64 * k] = Ivp[k];
-            }
-        }
-        float A11, A12, A22;
-        wave_sum3_float(a11, a12, a22, A11, A12, A22);
-        A11 *= FLT_SCALE;
-        A12 *= FLT_SCALE;
-        A22 *= FLT_SCALE;
-        float Dd = A11 * A22 - A12 * A12;
-        const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) /
-                             (float)(2 * WIN * WIN);
-        if (level == 0)
-            mineig0 = minEig;
-        if (uniform(minEig < prm.min_eig_thr || Dd < 1.1920928955078125e-7f)) {
-            if (level == 0)
-                st = 0;
-            continue;
-        }
-        Dd = 1.f / Dd;
-        // The reference scales the mismatch sums by 2^-20 before the 2x2 solve.  A power of two commutes with
-        // every rounding of  (A12 b2 - A22 b1) Dd  (no overflow: |b| < 2^31, no underflow: Dd <= 8.4e6 and the
-        // difference is a multiple of an ulp of its terms), so it is applied to Dd once per level instead of to
-        // both sums in every iteration: the same step bit for bit.
-        const float Dds = Dd * FLT_SCALE;
-
-        // ---- 2. iterate on the next image out of an LDS tile ----
-        nxp -= half;
-        nyp -= half;
-        float pdx = 0.f, pdy = 0.f;
-        const int lane_off = wy * Tile<C, TS>::ROW + wx * C;  // this lane's row run inside the window
-        int ox = 0, oy = 0;
-        bool have_tile = false;
-        int tj_off = 0;          // LDS byte offset of the staged tile's pixel (0, 0): TJ's offset + the staging shift
-        bool stepped = false;    // at least one Newton step taken: the output is nxp + half (else the guess itself)
-        bool out_set = false;    // left through the oscillation test: the output (backed off half a step) is written there
-        // The iterations of a level, as passes over pixel cells: the column pairs of the lane's two row runs depend on
-        // the staged tile and on the guess's integer cell (inx, iny) only, so the inner loop keeps them in registers
-        // and goes on for as long as the guess stays in its cell (after the first step of a level: about every
-        // second iteration).  A guess that leaves the cell returns to the outer loop, which re-stages the tile when
-        // the guess has drifted off it and loads and pairs the rows of the new cell.  Wave-uniform integers: scalar
-        // compares and scalar branches.  With prm.cell_cache == 0 every iteration returns to the outer loop.
-        float fx = floorf(nxp), fy = floorf(nyp);
-        int inx = uniform_int_of(fx), iny = uniform_int_of(fy);
-        bool more = prm.max_count > 0;
-        if (more && (inx < -WIN || inx >= lw || iny < -WIN || iny >= lh)) {
-            if (level == 0)
-                st = 0;
-            more = false;
-        }
-        int j = 0;
-        while (more) {
-            if (!have_tile || inx < ox || inx > ox + 2 * JR || iny < oy || iny > oy + 2 * JR) {
-                ox = inx - JR;
-                oy = iny - JR;
-                wave_lds_sync();
-                tj_off = (int)(TJ - lds) + uniform(stage_tile<C, TS>(TJ, J, pitch, ox, oy, lane));
-                wave_lds_sync();
-                have_tile = true;
-            }
-            int V[(SEG + 1) * C];
-            lane_load_pairs<C>(lds, lane_off + (tj_off + (iny - oy) * Tile<C, TS>::ROW + (inx - ox) * C), V);
-            const int cx = inx, cy = iny;
-            for (;;) {
-                int wv0, wv1;
-                bilinear_weight_pairs(nxp - fx, nyp - fy, wv0, wv1);
-                int s1, s2;
-                lane_mismatch<C>(V, wv0, wv1, Ixp, Iyp, neg_c1, neg_c2, s1, s2);
-                float b1, b2;
-                wave_sum2_float(s1, s2, b1, b2);
-                const float dx = (A12 * b2 - A22 * b1) * Dds;
-                const float dy = (A12 * b1 - A11 * b2) * Dds;
-                nxp += dx;
-                nyp += dy;
-                stepped = true;
-                more = false;
-                // |dx|^2 + |dy|^2 <= eps^2 in double, as the reference; only a step that is small in float
-                // can pass, so the double arithmetic is skipped for all the others
-                if (uniform(fmaxf(fabsf(dx), fabsf(dy)) <= prm.eps_pre) &&
-                    uniform((double)dx * (double)dx + (double)dy * (double)dy <= prm.eps_sq))
-                    break;
-                // fabs((double)x) < 0.01  <=>  |x| <= 0.01f for a float x: 0.01f is the largest float below 0.01
-                if (j > 0 && uniform(fabsf(dx + pdx) <= 0.01f && fabsf(dy + pdy) <= 0.01f)) {
-                    outx = (nxp + half) - dx * 0.5f;
-                    outy = (nyp + half) - dy * 0.5f;
-                    out_set = true;
-                    break;
-                }
-                pdx = dx;
-                pdy = dy;
-                if (++j >= prm.max_count)
-                    break;
-                fx = floorf(nxp);
-                fy = floorf(nyp);
-                inx = uniform_int_of(fx);
-                iny = uniform_int_of(fy);
-                if (inx < -WIN || inx >= lw || iny < -WIN || iny >= lh) {
-                    if (level == 0)
-                        st = 0;
-                    break;
-                }
-                more = true;
-                if (!prm.cell_cache || inx != cx || iny != cy)
-                    break;  // another cell: load and pair its rows
-            }
-        }
-        // the reference keeps nextPt = guess + half up to date inside the loop; the same float operations
-        // in the same order, once, after it
-        if (stepped && !out_set) {
-            outx = nxp + half;
-            outy = nyp + half;
-        }
-
-        // ---- 3. level-0 residual (err output of calcOpticalFlowPyrLK) ----
-        if (st && level == 0) {
-            const float qx = outx - half, qy = outy - half;
-            const int iqx = uniform_int_of(floorf(qx)), iqy = uniform_int_of(floorf(qy));
-            if (iqx < -WIN || iqx >= lw || iqy < -WIN || iqy >= lh) {
-                st = 0;
-                continue;
-            }
-            // without WANT_ERR no caller of this launch reads err: only the bounds test above affects its outputs
-            if constexpr (WANT_ERR) {
-                if (uniform(err == nullptr))
-                    continue;  // this job's caller does not read it
-                if (!have_tile || iqx < ox || iqx > ox + 2 * JR || iqy < oy || iqy > oy + 2 * JR) {
-                    ox = iqx - JR;
-                    oy = iqy - JR;
-                    wave_lds_sync();
-                    tj_off = (int)(TJ - lds) + uniform(stage_tile<C, TS>(TJ, J, pitch, ox, oy, lane));
-                    wave_lds_sync();
-                    have_tile = true;
-                }
-                int w00, w01, w10, w11;
-                bilinear_weights(qx - (float)iqx, qy - (float)iqy, w00, w01, w10, w11);
-                int Iv0[npairs(C)];
-                if constexpr (PARK_IVP) {
-                    const int *park = reinterpret_cast<const int *>(lds + PARK) + lane;
-#pragma unroll
-                    for (int k = 0; k < npairs(C); k++)
-                        Iv0[k] = park[64 * k];
-                } else {
-#pragma unroll
-                    for (int k = 0; k < npairs(C); k++)
-                        Iv0[k] = Ivp[k];
-                }
-                int s1 = lane_abs_residual<C>(lds, lane_off + (tj_off + (iqy - oy) * Tile<C, TS>::ROW + (iqx - ox) * C),
-                                              (w00 & 0xffff) | (w10 << 16), (w01 & 0xffff) | (w11 << 16), Iv0);
-                if (!active)
-                    s1 = 0;
-                const long long sabs = (long long)wave_sum_exact(s1);  // < 2^24
-                errv = (float)sabs / (float)(32 * WIN * C * WIN);
-            }
-        }
+    } else {
+        constexpr int CA = C, MUL = C / CA;
+        static_assert(CA == C || (CA == 1 && C == 3), "the one-channel body is for three equal channels");
+#include "lk_levels.hip.h"
     }
 
     if (lane == 0) {
@@ -1014,6 +722,10 @@ int svo_launch_lk_batch(svo_ctx *ctx, int n_jobs, const LkJob *jobs, const svo_p
     // them in every iteration (the same values), for an A/B and for the tests that compare the two
     static const int cell_cache = getenv("SVO_LK_CELL_CACHE") ? atoi(getenv("SVO_LK_CELL_CACHE")) : 1;
     prm.cell_cache = cell_cache;
+    // grey frames stored as BGR take the one-channel body (the kernel's own choice per job, from the pyramids' words);
+    // SVO_LK_MONO=0 keeps the three-channel arithmetic (the same values), for an A/B and for the tests that compare the two
+    static const int mono = getenv("SVO_LK_MONO") ? atoi(getenv("SVO_LK_MONO")) : 1;
+    prm.mono = mono;
     // the level-0 residual is compiled in only where some job of the launch asks for it
     bool want_err = false;
     for (int k = 0; k < n_jobs; k++)

@@ -197,21 +197,37 @@ __device__ __forceinline__ void down_tile(const uint8_t *__restrict__ src, int s
 }
 
 // one row of the padded level 0 from the raw image, one thread per output dword
+// C == 3 also answers "does a pixel of this image have B != G or G != R?" for the bytes it copies anyway (the pyramid's
+// "channels agree" word, svo_internal.h): a pixel is grey iff byte i equals byte i + 1 for every i of its row with
+// i % 3 != 2, and the thread that copies row bytes k .. k+3 of an IMAGE row (not a border row, which repeats one) owns the
+// pairs that start there.  The pair (k+3, k+4) needs one byte of the neighbouring dword: the interior path has fetched it
+// (an aligned dword pair holds at least five bytes from k on), the edge path reads it.  Returns true when a pair differs.
 template <int C>
-__device__ __forceinline__ void pad_copy_row(const uint8_t *__restrict__ src, uint8_t *__restrict__ padded, int w, int h,
+__device__ __forceinline__ bool pad_copy_row(const uint8_t *__restrict__ src, uint8_t *__restrict__ padded, int w, int h,
                                              int pitch, int row, int d)
 {
     const int Y = reflect101(row - SVO_PYR_PAD, h);
     const uint8_t *srow = src + (size_t)Y * w * C;
     uint32_t out = 0;
+    bool colour = false;
     const int k = d * 4 - SVO_PYR_PAD * C;  // byte index inside the source row of the dword's first byte
+    const bool image_row = C == 3 && row >= SVO_PYR_PAD && row < SVO_PYR_PAD + h;
     if (k >= 0 && k + 4 <= w * C && (Y < h - 1 || k + 8 <= w * C) && (Y > 0 || k >= 4)) {
         // interior: four consecutive source bytes, fetched as two aligned dwords (the source rows have
         // no particular alignment); neither dword reaches outside the image buffer
         const uintptr_t a = reinterpret_cast<uintptr_t>(srow + k);
         const uint32_t *p = reinterpret_cast<const uint32_t *>(a & ~(uintptr_t)3);
-        const uint32_t lo = p[0], hi = (a & 3) ? p[1] : 0u;
+        const uint32_t lo = p[0], hi = (C == 3 || (a & 3)) ? p[1] : 0u;
         out = __builtin_amdgcn_alignbyte(hi, lo, (unsigned)(a & 3));
+        if (image_row) {
+            // bytes k+1 .. k+4 beside bytes k .. k+3; k % 3 == d % 3 (the pad is a whole number of pixels), which tells
+            // the pairs that cross from one pixel into the next: they are masked out.  Where k + 4 is the row's end,
+            // pair (k+3, k+4) is such a crossing.
+            const uint32_t nxt = (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * ((unsigned)(a & 3) + 1u)));  // bytes k+1 .. k+4
+            const int m = d % 3;
+            const uint32_t own = m == 0 ? 0xff00ffffu : m == 1 ? 0xffff00ffu : 0x00ffff00u;
+            colour = ((out ^ nxt) & own) != 0;
+        }
     } else {
 #pragma unroll
         for (int b = 0; b < 4; b++) {
@@ -222,8 +238,18 @@ __device__ __forceinline__ void pad_copy_row(const uint8_t *__restrict__ src, ui
                 out |= (uint32_t)srow[X * C + ch] << (8 * b);
             }
         }
+        if (image_row) {
+            // the ends of a row, the first dword of the image and the last bytes of its last row: pair by pair
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const int i = k + b;
+                if (i >= 0 && i + 1 < w * C && i % 3 != 2)
+                    colour = colour || srow[i] != srow[i + 1];
+            }
+        }
     }
     reinterpret_cast<uint32_t *>(padded + (size_t)row * pitch)[d] = out;
+    return colour;
 }
 
 // launch 1: workgroups [0, n_tiles) build level 1 from the raw image, the rest the padded level 0
@@ -244,8 +270,16 @@ template <int C, int NJ> __global__ __launch_bounds__(PB) void pyr_base_kernel(P
     if (d >= (b.pitch[0] >> 2))
         return;
     uint8_t *padded = b.lvl[job][0] - (size_t)SVO_PYR_PAD * b.pitch[0] - SVO_PYR_PAD * C;
+    bool colour = false;
     for (int row = rb * ROWS_PER_BLOCK, rend = min(row + ROWS_PER_BLOCK, b.h[0] + 2 * SVO_PYR_PAD); row < rend; row++)
-        pad_copy_row<C>(b.img[job], padded, b.w[0], b.h[0], b.pitch[0], row, d);
+        colour = pad_copy_row<C>(b.img[job], padded, b.w[0], b.h[0], b.pitch[0], row, d) || colour;
+    if constexpr (C == 3) {
+        // a wave that saw a colour pixel says so: every writer stores the same value, so one lane's plain store does
+        // (no atomic); a grey image causes no store at all.  pyr_finish_kernel publishes and clears the word.
+        const unsigned long long saw = __builtin_amdgcn_ballot_w64(colour);
+        if (saw != 0 && (int)(threadIdx.x & 63) == __builtin_ctzll(saw))
+            svo_pyr_words(padded)[SVO_PYR_COLOUR_SEEN] = 1;
+    }
 }
 
 // launches 2 and 3: level l from level l - 1
@@ -379,6 +413,7 @@ __device__ __forceinline__ void scharr_row(const uint8_t *__restrict__ lvl, int 
 struct FinishPlan {
     int border_y0[SVO_MAX_LEVELS + 1];  // first blockIdx.y of level l's border role (l >= 1); [levels] = end
     int scharr_y0[SVO_MAX_LEVELS + 1];  // first blockIdx.y of level l's Scharr role; [levels] = end
+    int publish;                        // 1: the launch ends a build from raw images (0: svo_build_derivatives)
 };
 template <int C, int NJ> __global__ __launch_bounds__(PB) void pyr_finish_kernel(PyrBuildN<NJ> b, FinishPlan plan)
 {
@@ -386,6 +421,15 @@ template <int C, int NJ> __global__ __launch_bounds__(PB) void pyr_finish_kernel
     const int job = blockIdx.z, by = blockIdx.y;
     if (b.gate[job] && *b.gate[job] == 0)
         return;
+    if constexpr (C == 3) {
+        // one thread per pyramid publishes what the base launch saw (same stream, finished by now) and clears the
+        // collecting word for the next build; a gated build has left above and keeps both words
+        if (plan.publish && blockIdx.x == 0 && by == 0 && threadIdx.x == 0) {
+            int *words = svo_pyr_words(b.lvl[job][0] - (size_t)SVO_PYR_PAD * b.pitch[0] - SVO_PYR_PAD * C);
+            words[SVO_PYR_MONO] = words[SVO_PYR_COLOUR_SEEN] == 0;
+            words[SVO_PYR_COLOUR_SEEN] = 0;
+        }
+    }
     if (by < plan.border_y0[b.levels]) {
         int l = 1;
         for (int i = 2; i < b.levels; i++)
@@ -472,8 +516,9 @@ template <int C> static int launch_finish(svo_ctx *ctx, int k, const PyrBuild &b
         }
     }
     plan.scharr_y0[b.levels] = y;
+    plan.publish = borders ? 1 : 0;
     if (y == 0)
-        return SVO_OK;
+        return SVO_OK;  // one level and no derivatives: nothing to finish; the pyramid never reports mono
     if (k <= PYR_FEW)
         hipLaunchKernelGGL((pyr_finish_kernel<C, PYR_FEW>), dim3(xmax, y, k), dim3(PB), 0, ctx->stream, pyr_few(b), plan);
     else
@@ -605,6 +650,8 @@ int svo_pyramid_create_ex(svo_ctx *ctx, int width, int height, int channels, int
     size_t off = 0;
     int w = width, h = height;
     for (int l = 0; l < SVO_MAX_LEVELS; l++) {
+        if (l == 0)
+            off = SVO_PYR_HEADER;  // the pyramid's device words (svo_pyr_words), in front of level 0's padded buffer
         p->off[l] = off;
         p->dev.w[l] = w;
         p->dev.h[l] = h;
@@ -693,6 +740,17 @@ int svo_pyramid_build(svo_ctx *ctx, svo_pyramid *pyr, const uint8_t *image, int 
         return rc;
     if (mem == SVO_MEM_HOST)
         SVO_HIP(hipStreamSynchronize(ctx->stream));
+    return SVO_OK;
+}
+
+int svo_pyramid_is_mono(svo_ctx *ctx, const svo_pyramid *pyr, int *out)
+{
+    SVO_CHECK_ARG(ctx && pyr && out);
+    int word = 0;
+    SVO_HIP(hipMemcpyAsync(&word, svo_pyr_words(pyr->base + pyr->off[0]) + SVO_PYR_MONO, sizeof(int), hipMemcpyDeviceToHost,
+                           ctx->stream));
+    SVO_HIP(hipStreamSynchronize(ctx->stream));
+    *out = word != 0;
     return SVO_OK;
 }
 

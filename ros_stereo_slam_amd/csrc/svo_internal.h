@@ -59,6 +59,20 @@ struct PyrDev {
     int c;
 };
 
+// Two device words per pyramid live in a header of SVO_PYR_HEADER bytes in front of level 0's padded buffer, i.e. at
+// lvl[0] - PAD * pitch[0] - PAD * c - SVO_PYR_HEADER: whoever holds the PyrDev finds them, no pointer of their own.
+//   SVO_PYR_MONO         1: the image the pyramid was last built from has B == G == R in every pixel (c == 3 only;
+//                        pyramids of 1 or 4 channels, and pyramids never built, say 0).  Published by the finishing launch
+//                        of a build, left alone by a gated build and by svo_build_derivatives.
+//   SVO_PYR_COLOUR_SEEN  collects during the base launch of a build, cleared when SVO_PYR_MONO is published
+#define SVO_PYR_HEADER 256
+enum { SVO_PYR_MONO = 0, SVO_PYR_COLOUR_SEEN = 1 };
+// `padded`: the first byte of level 0's padded buffer
+__host__ __device__ __forceinline__ int *svo_pyr_words(const uint8_t *padded)
+{
+    return reinterpret_cast<int *>(const_cast<uint8_t *>(padded) - SVO_PYR_HEADER);
+}
+
 struct svo_pyramid {
     int w, h, c, levels;
     uint8_t *base;   // one HBM allocation, padded levels back to back (256-B aligned each)
