@@ -921,6 +921,78 @@ int svo_closure_measure(svo_ctx *ctx, const uint8_t *newest, const uint8_t *matc
                         const float *xyz3, int n, const double *K4, const svo_closure_params *p, double *meas7,
                         int *n_tracked, int *n_inliers, int mem);
 
+/* ---- point-to-plane ICP between clouds and the information of the edge it yields ---------------
+ * PoseGraphOptimize of the Python prototype (src/ROSslam.py:34-73): pairwiseRegistration = a coarse and a fine
+ * open3d registration_icp(TransformationEstimationPointToPlane) and get_information_matrix_from_point_clouds.
+ * Open3D is recalled, not linked: tests/icp_numpy.py states every recalled point and every choice of ours, and the
+ * device is held to that restatement bit for bit.
+ *
+ * svo_cloud: a resident TARGET cloud of 1 <= n <= 4194304 float32 points with its search index (Morton order and the
+ * 64-way box hierarchy of svo_sor_filter_large), built once at creation and reused by every search: each ICP
+ * iteration, both passes, the information matrix and the normals.  A point with a non-finite coordinate is
+ * SVO_ERR_ARG whose text names the first offending index (indices are part of the results, nothing is dropped).
+ * xyz follows `mem`; the call synchronises.  Normals are n x 3 DOUBLES in the points' order (Open3D's type).      */
+typedef struct svo_cloud svo_cloud;
+int svo_cloud_create(svo_ctx *ctx, const float *xyz, int n, int mem, svo_cloud **out);
+int svo_cloud_destroy(svo_cloud *cloud);
+int svo_cloud_size(const svo_cloud *cloud);
+int svo_cloud_has_normals(const svo_cloud *cloud);
+int svo_cloud_set_normals(svo_cloud *cloud, const double *normals, int mem);
+int svo_cloud_get_normals(svo_cloud *cloud, double *normals, int mem); /* SVO_ERR_STATE without normals */
+/* The k nearest points of every point, itself included (KDTreeSearchParamKNN), ordered by (d2, index); d2 =
+ * (dx dx + dy dy) + dz dz in double.  idx_out: n x k ints following `mem`, rows shorter than k (n < k) end in -1.
+ * k in 3 .. 64, else SVO_ERR_ARG.  Exact: equal to brute force over the whole cloud.                               */
+int svo_cloud_knn(svo_cloud *cloud, int k, int *idx_out, int mem);
+/* estimate_normals(KDTreeSearchParamKNN(knn)), knn in 3 .. 64 (Open3D's default: 30): per point the mean and the
+ * covariance sum of its neighbours in double, in the neighbour order above; the eigenvector of the smallest
+ * eigenvalue by 8 cyclic Jacobi sweeps, normalised, sign as the solver leaves it (never oriented); a point with
+ * fewer than 3 neighbours, or a zero / non-finite vector, gets (0, 0, 1).  Asynchronous on the context's stream.   */
+int svo_cloud_estimate_normals(svo_cloud *cloud, int knn);
+
+typedef struct svo_icp_params {
+    int max_iteration;       /* 30: ICPConvergenceCriteria's defaults */
+    double relative_fitness; /* 1e-6 */
+    double relative_rmse;    /* 1e-6 */
+} svo_icp_params;
+void svo_icp_default_params(svo_icp_params *p);
+/* The correspondences of T src in the target: per source point the nearest target point (distance as above, the
+ * lowest target index on a tie) when d2 < max_dist^2, else -1; fitness = n_corr / n_src, rmse = sqrt(sum d2 / n_corr)
+ * (0 without correspondences).  T16: 4 x 4 row-major HOST doubles, source coordinates -> target frame.  corr_out
+ * (optional, n_src ints) and src_xyz follow `mem`; the scalars are HOST.  The call synchronises.                  */
+int svo_icp_correspondences(svo_ctx *ctx, const float *src_xyz, int n_src, svo_cloud *target, double max_dist,
+                            const double *T16, int *corr_out, double *fitness, double *rmse, int mem);
+/* J^T J (upper triangle, row-major, 21 HOST doubles) and J^T r (6) of ONE point-to-plane step at T16: r = (s - t) . n,
+ * J = [s x n, n], summed over the correspondences on the fixed tree of DESIGN.md section 10i.  SVO_ERR_STATE when the
+ * target has no normals.                                                                                          */
+int svo_icp_normal_equations(svo_ctx *ctx, const float *src_xyz, int n_src, svo_cloud *target, double max_dist,
+                             const double *T16, double *JtJ21, double *Jtr6, int *n_corr, int mem);
+/* registration_icp(source, target, max_dist, T_init, TransformationEstimationPointToPlane(), criteria).  The solve,
+ * the update of T and the convergence test run on the device: every iteration is queued at once, iterations after
+ * the stop leave at once, and the host waits once.  iterations: updates applied (1 .. max_iteration).  corr_out
+ * (optional, follows `mem`): the correspondences of the final T.  SVO_ERR_STATE: the target has no normals;
+ * SVO_ERR_ARG: max_dist <= 0, n_src < 1, max_iteration < 1.                                                       */
+int svo_icp_point_to_plane(svo_ctx *ctx, const float *src_xyz, int n_src, svo_cloud *target, double max_dist,
+                           const double *T_init16, const svo_icp_params *params, double *T_out16, double *fitness,
+                           double *rmse, int *iterations, int *corr_out, int mem);
+/* get_information_matrix_from_point_clouds: Lambda = sum G^T G over the correspondences of T src at max_dist, G =
+ * [-[t]x | I3] at the TARGET point t: 6 x 6 row-major, rotation first, then translation.  No normals needed.       */
+int svo_icp_information(svo_ctx *ctx, const float *src_xyz, int n_src, svo_cloud *target, double max_dist,
+                        const double *T16, double *info36, int *n_corr, int mem);
+/* pairwiseRegistration: ICP at dist_coarse from the identity, ICP at dist_fine from its result, the information at
+ * dist_fine; one index, one wait.  fitness / rmse / iterations (optional): [2] = coarse, fine.                    */
+int svo_icp_pairwise(svo_ctx *ctx, const float *src_xyz, int n_src, svo_cloud *target, double dist_coarse,
+                     double dist_fine, const svo_icp_params *params, double *T_out16, double *info36, double *fitness2,
+                     double *rmse2, int *iterations2, int *n_corr, int mem);
+/* Host code.  Lambda is the information of a LEFT perturbation T <- exp([w ; v]) T in the target frame; an edge whose
+ * measurement is Z = T has the error e = [t ; s q_xyz] of Z^-1 Xi^-1 Xj = M [w ; v] to first order, M = the adjoint of
+ * T^-1 reordered to translation first with the rotation rows halved.  info21 = the upper triangle, row-major, of
+ * M^-T Lambda M^-1 (M^-1 = [0, 2R ; R, 2 [t]x R] in closed form), as svo_pg_set_edge_information takes it.
+ * For svo_pg_add_loop_closure_measured: source = the matched keyframe's cloud, target = the newest frame's, each in
+ * its own camera frame; T = X_newest^-1 X_matched is that call's meas7.                                            */
+int svo_icp_edge_information(const double *info36, const double *T16, double *info21);
+/* T16 -> tx ty tz qx qy qz qw by the quaternion formula stated at svo_closure_measure (host code) */
+int svo_icp_meas7(const double *T16, double *meas7);
+
 /* ---- data formats either side of the path (host code, no GPU work) -------------------------- */
 /* KITTI odometry pose files: one pose per line, 12 numbers = the 3x4 [R|t]
  * row-major, camera-to-world.  Rt12: capacity*12 doubles; *n = poses in the file.                */

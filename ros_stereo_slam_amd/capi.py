@@ -1928,3 +1928,168 @@ class PoseGraph:
             self.close()
         except Exception:
             pass
+
+
+# ---- point-to-plane ICP between clouds and the information of the edge it yields (csrc/cloud.hip) ------------------
+class IcpParams(C.Structure):
+    _fields_ = [("max_iteration", C.c_int), ("relative_fitness", C.c_double), ("relative_rmse", C.c_double)]
+
+
+def icp_params(**overrides) -> IcpParams:
+    p = IcpParams()
+    load().svo_icp_default_params(C.byref(p))
+    for k, v in overrides.items():
+        if not hasattr(p, k):
+            raise TypeError(f"svo_icp_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+def _cloud_arg(xyz):
+    """numpy array or device tensor (float32, n x 3) -> (array, n, mem)"""
+    if _is_device(xyz):
+        import torch
+
+        t = xyz.reshape(-1, 3).contiguous()
+        assert t.dtype == torch.float32
+        torch.cuda.synchronize(t.device)
+        return t, int(t.shape[0]), MEM_DEVICE
+    a = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    return a, int(a.shape[0]), MEM_HOST
+
+
+def _T16(T):
+    return np.ascontiguousarray(np.eye(4) if T is None else T, np.float64).reshape(16)
+
+
+class Cloud:
+    """A resident target cloud with its search index (``svo_cloud``): n x 3 float32 points, host array or device tensor."""
+
+    def __init__(self, ctx: Context, xyz):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        a, n, mem = _cloud_arg(xyz)
+        _check(ctx.lib.svo_cloud_create(ctx._h, _ptr(a), n, mem, C.byref(self._h)))
+        ctx._children.add(self)
+
+    def __len__(self) -> int:
+        return self.ctx.lib.svo_cloud_size(self._h)
+
+    @property
+    def has_normals(self) -> bool:
+        return bool(self.ctx.lib.svo_cloud_has_normals(self._h))
+
+    def set_normals(self, normals):
+        a = np.ascontiguousarray(normals, np.float64).reshape(-1, 3)
+        assert len(a) == len(self)
+        _check(self.ctx.lib.svo_cloud_set_normals(self._h, _ptr(a), MEM_HOST))
+
+    def normals(self) -> np.ndarray:
+        out = np.zeros((len(self), 3))
+        _check(self.ctx.lib.svo_cloud_get_normals(self._h, _ptr(out), MEM_HOST))
+        return out
+
+    def knn(self, k: int = 30) -> np.ndarray:
+        """[n, k] int32: the k nearest points of every point, itself included, by (d2, index); -1 past a short list"""
+        out = np.zeros((len(self), max(int(k), 1)), np.int32)
+        _check(self.ctx.lib.svo_cloud_knn(self._h, int(k), _ptr(out), MEM_HOST))
+        return out
+
+    def estimate_normals(self, knn: int = 30):
+        _check(self.ctx.lib.svo_cloud_estimate_normals(self._h, int(knn)))
+        return self
+
+    def close(self):
+        if self._h and self.ctx._h:
+            self.ctx.lib.svo_cloud_destroy(self._h)
+        self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+@_ctx_method
+def icp_correspondences(self, src, target: Cloud, max_dist, T=None):
+    """``svo_icp_correspondences`` -> (corr [n_src] int32, fitness, rmse)"""
+    a, n, mem = _cloud_arg(src)
+    if mem == MEM_DEVICE:
+        import torch
+
+        corr = torch.empty(max(n, 1), dtype=torch.int32, device=a.device)
+    else:
+        corr = np.zeros(max(n, 1), np.int32)
+    fit, rmse = C.c_double(), C.c_double()
+    _check(self.lib.svo_icp_correspondences(self._h, _ptr(a), n, target._h, C.c_double(max_dist), _ptr(_T16(T)), _ptr(corr),
+                                            C.byref(fit), C.byref(rmse), mem))
+    return corr[:n], fit.value, rmse.value
+
+
+@_ctx_method
+def icp_normal_equations(self, src, target: Cloud, max_dist, T=None):
+    """``svo_icp_normal_equations``: one point-to-plane step at T -> (JtJ21, Jtr6, n_corr)"""
+    a, n, mem = _cloud_arg(src)
+    A, b, nc = np.zeros(21), np.zeros(6), C.c_int()
+    _check(self.lib.svo_icp_normal_equations(self._h, _ptr(a), n, target._h, C.c_double(max_dist), _ptr(_T16(T)), _ptr(A),
+                                             _ptr(b), C.byref(nc), mem))
+    return A, b, nc.value
+
+
+@_ctx_method
+def icp_point_to_plane(self, src, target: Cloud, max_dist, T_init=None, want_corr=False, **params):
+    """``svo_icp_point_to_plane`` -> (T [4, 4], fitness, rmse, iterations[, corr])"""
+    a, n, mem = _cloud_arg(src)
+    prm = icp_params(**params)
+    T, fit, rmse, its = np.zeros(16), C.c_double(), C.c_double(), C.c_int()
+    corr = None
+    if want_corr:
+        if mem == MEM_DEVICE:
+            import torch
+
+            corr = torch.empty(max(n, 1), dtype=torch.int32, device=a.device)
+        else:
+            corr = np.zeros(max(n, 1), np.int32)
+    _check(self.lib.svo_icp_point_to_plane(self._h, _ptr(a), n, target._h, C.c_double(max_dist), _ptr(_T16(T_init)),
+                                           C.byref(prm), _ptr(T), C.byref(fit), C.byref(rmse), C.byref(its), _ptr(corr), mem))
+    res = (T.reshape(4, 4), fit.value, rmse.value, its.value)
+    return res + (corr[:n],) if want_corr else res
+
+
+@_ctx_method
+def icp_information(self, src, target: Cloud, max_dist, T=None):
+    """``svo_icp_information`` -> (Lambda [6, 6], n_corr)"""
+    a, n, mem = _cloud_arg(src)
+    L, nc = np.zeros(36), C.c_int()
+    _check(self.lib.svo_icp_information(self._h, _ptr(a), n, target._h, C.c_double(max_dist), _ptr(_T16(T)), _ptr(L),
+                                        C.byref(nc), mem))
+    return L.reshape(6, 6), nc.value
+
+
+@_ctx_method
+def icp_pairwise(self, src, target: Cloud, dist_coarse=15.0, dist_fine=1.5, **params):
+    """``svo_icp_pairwise`` (pairwiseRegistration) -> (T [4, 4], Lambda [6, 6], details); details: fitness / rmse /
+    iterations of the coarse and the fine pass, n_corr of the information"""
+    a, n, mem = _cloud_arg(src)
+    prm = icp_params(**params)
+    T, L, fit, rmse, its, nc = np.zeros(16), np.zeros(36), np.zeros(2), np.zeros(2), np.zeros(2, np.int32), C.c_int()
+    _check(self.lib.svo_icp_pairwise(self._h, _ptr(a), n, target._h, C.c_double(dist_coarse), C.c_double(dist_fine),
+                                     C.byref(prm), _ptr(T), _ptr(L), _ptr(fit), _ptr(rmse), _ptr(its), C.byref(nc), mem))
+    return T.reshape(4, 4), L.reshape(6, 6), dict(fitness=fit, rmse=rmse, iterations=its, n_corr=nc.value)
+
+
+def icp_edge_information(info, T) -> np.ndarray:
+    """``svo_icp_edge_information``: Lambda [6, 6] of a registration with result T -> the 21 numbers
+    ``PoseGraph.add_loop_closure`` / ``set_edge_information`` take for an edge whose measurement is T"""
+    L = np.ascontiguousarray(info, np.float64).reshape(36)
+    out = np.zeros(21)
+    _check(load().svo_icp_edge_information(_ptr(L), _ptr(_T16(T)), _ptr(out)))
+    return out
+
+
+def icp_meas7(T) -> np.ndarray:
+    """``svo_icp_meas7``: T [4, 4] -> tx ty tz qx qy qz qw (w >= 0)"""
+    out = np.zeros(7)
+    _check(load().svo_icp_meas7(_ptr(_T16(T)), _ptr(out)))
+    return out

@@ -211,7 +211,7 @@ int svo_ctx_destroy(svo_ctx *ctx)
     DevBuf *bufs[] = {&ctx->s_img, &ctx->s_a, &ctx->s_b, &ctx->s_c, &ctx->s_d, &ctx->s_e,
                       &ctx->s_f,   &ctx->s_g, &ctx->w_a, &ctx->w_b, &ctx->w_c, &ctx->w_d,
                       &ctx->w_e,   &ctx->orb_out, &ctx->orb_cv_out, &ctx->orb_cv_img, &ctx->orb_cv_ptrs,
-                      &ctx->sgbm_cost, &ctx->sgbm_misc, &ctx->sgbm_rp, &ctx->sor_grid, &ctx->ess,
+                      &ctx->sgbm_cost, &ctx->sgbm_misc, &ctx->sgbm_rp, &ctx->sor_grid, &ctx->icp_work, &ctx->ess,
                       &ctx->feat_img, &ctx->feat_sum, &ctx->sift_pyr, &ctx->sift_work, &ctx->sift_out,
                       &ctx->brief_work, &ctx->brief_pat, &ctx->surf_planes, &ctx->surf_work,
                       &ctx->wls_work, &ctx->wls_maps, &ctx->wls_lut};

@@ -149,6 +149,9 @@ struct svo_ctx {
     DevBuf sgbm_cost, sgbm_misc, sgbm_rp;
     // sor_grid.hip: the large-cloud outlier removal's keys, sorted points, boxes and radix histograms
     DevBuf sor_grid;
+    // cloud.hip: the staged source, the moved source in double, correspondences, partial sums and device states of one
+    // registration call
+    DevBuf icp_work;
     // essential.hip: normalised points, the RANSAC's per-iteration models / counts / state, recoverPose's candidate masks
     DevBuf ess;
     // sift.hip, brief.hip, surf.hip (feature_batch.hip.h, integral_scan.hip.h): the staged host images of a call (or surf.hip's
