@@ -557,6 +557,8 @@ enum { /* DLoopDetector::DetectionStatus, include/TemplatedLoopDetector.h:51-69 
     SVO_LC_NO_GEOMETRICAL_CONSISTENCY = 7
 };
 void svo_lc_default_params(svo_lc_params *p);
+/* SVO_ERR_ARG, with *out NULL: n_features outside 8..2048, max_entries < 2, dislocal < 0, k < 0, alpha outside 0..1 (or not a
+ * number), max_db_results outside 1..64.                                                                             */
 int svo_lc_create(svo_ctx *ctx, const svo_lc_params *params, int width, int height, int channels, svo_lc **out);
 int svo_lc_destroy(svo_lc *lc);
 int svo_lc_size(const svo_lc *lc);

@@ -6,6 +6,7 @@ gfx950 device is present.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 import pathlib
@@ -1551,11 +1552,30 @@ class LoopDetector:
             assert hasattr(self.prm, k), k
             setattr(self.prm, k, v)
         self._h = C.c_void_p()
+        # the images of submitted frames, oldest first: (entry of the submission's last frame, the images) -- the queued work
+        # reads them, so each stays referenced until collect / collect_batch / collect_ex has passed that entry
+        self._keep_images = collections.deque()
         _check(ctx.lib.svo_lc_create(ctx._h, C.byref(self.prm), w, h, c, C.byref(self._h)))
         ctx._children.add(self)
 
+    @staticmethod
+    def _image(image):
+        """a host image as the contiguous uint8 array whose pointer is taken; a device image as it is"""
+        return np.ascontiguousarray(image, np.uint8) if isinstance(image, np.ndarray) else image
+
+    def _hold(self, images):
+        self._keep_images.append((len(self) - 1, images))
+
+    def _release(self):
+        """drop the images of every submission whose last frame has been collected"""
+        if self._keep_images:
+            collected = len(self) - self.pending()
+            while self._keep_images and self._keep_images[0][0] < collected:
+                self._keep_images.popleft()
+
     def detect(self, image):
         """-> dict(status, query, match); a detection is status == 0 (LOOP_DETECTED)."""
+        image = self._image(image)
         mem = MEM_HOST if isinstance(image, np.ndarray) else MEM_DEVICE
         st, q, m = C.c_int(), C.c_int(), C.c_int()
         _check(self.ctx.lib.svo_lc_detect(self._h, _ptr(image), mem, C.byref(st), C.byref(q), C.byref(m)))
@@ -1563,23 +1583,27 @@ class LoopDetector:
 
     def submit(self, image):
         """Queue a frame (``svo_lc_submit``): nothing is waited for."""
+        image = self._image(image)
         mem = MEM_HOST if isinstance(image, np.ndarray) else MEM_DEVICE
         _check(self.ctx.lib.svo_lc_submit(self._h, _ptr(image), mem))
+        self._hold([image])
 
     def submit_batch(self, images):
         """Queue n frames at once (``svo_lc_submit_batch``): one set of launches per 16 frames."""
         n = len(images)
         if n == 0:
             return
+        images = [self._image(im) for im in images]
         mem = MEM_HOST if isinstance(images[0], np.ndarray) else MEM_DEVICE
         ptrs = (C.c_void_p * n)(*[_ptr(im).value for im in images])
-        self._keep_images = images      # the queued work reads them
         _check(self.ctx.lib.svo_lc_submit_batch(self._h, ptrs, n, mem))
+        self._hold(images)
 
     def collect(self):
         """The verdict of the oldest queued frame (``svo_lc_collect``) -> dict(status, query, match)."""
         st, q, m = C.c_int(), C.c_int(), C.c_int()
         _check(self.ctx.lib.svo_lc_collect(self._h, C.byref(st), C.byref(q), C.byref(m)))
+        self._release()
         return dict(status=st.value, query=q.value, match=m.value)
 
     def collect_batch(self, n: int):
@@ -1587,6 +1611,7 @@ class LoopDetector:
         n = int(n)
         st, q, m = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
         _check(self.ctx.lib.svo_lc_collect_batch(self._h, n, _ptr(st), _ptr(q), _ptr(m)))
+        self._release()
         return [dict(status=a, query=b, match=c) for a, b, c in zip(st.tolist(), q.tolist(), m.tolist())]
 
     def pending(self) -> int:
@@ -1626,6 +1651,7 @@ class LoopDetector:
         ids, sc = np.zeros(64, np.int32), np.zeros(64)
         _check(self.ctx.lib.svo_lc_collect_ex(self._h, C.byref(st), C.byref(q), C.byref(m), _ptr(ids), _ptr(sc), 64,
                                               C.byref(n), C.byref(ns)))
+        self._release()
         k = min(n.value, 64)
         return dict(status=st.value, query=q.value, match=m.value, cand_id=ids[:k].copy(), cand_score=sc[:k].copy(),
                     ns_factor=ns.value)
@@ -1635,8 +1661,9 @@ class LoopDetector:
 
     def close(self):
         if self._h and self.ctx._h:
-            self.ctx.lib.svo_lc_destroy(self._h)
+            self.ctx.lib.svo_lc_destroy(self._h)     # waits for the queued work
         self._h = C.c_void_p()
+        self._keep_images.clear()
 
     def __del__(self):
         try:

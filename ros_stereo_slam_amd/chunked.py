@@ -383,7 +383,8 @@ def gate_closures(matches, min_gap: int = 100, cooldown: int = 100):
 # ---- the loop detector sharded like the front-end (the detector off rank 0's serial path) ----------------
 DETECT_WARMUP = 8   # frames a rank queries BEFORE its share (verdicts discarded): they bring the temporal window into the
                     # state the sequential run has there -- the window forgets everything older than
-                    # max_distance_between_queries (2) frames and is only ever compared with k (1)
+                    # max_distance_between_queries (2) frames and is only ever compared with k (1); other settings:
+                    # detect_warmup and sharded_detect's ``params``
 
 
 def detect_shares(n_frames: int, world: int):
@@ -397,13 +398,39 @@ def detect_shares(n_frames: int, world: int):
     return out
 
 
-def sharded_detect(fill, submit, collect, first: int, end: int, warmup: int = DETECT_WARMUP, collect_many=None):
+def detect_warmup(k: int, max_distance_between_queries: int) -> int:
+    """The fewest warm-up frames after which a detector that starts with an EMPTY temporal window judges as one that has seen
+    the whole stream: ``k * max_distance_between_queries``.
+
+    The window's update rule (updateTemporalWindow, include/TemplatedLoopDetector.h:966-1003) makes ``nentries`` the length of
+    the current CHAIN of updates: an update at query q continues the chain iff the previous update was at most
+    max_distance_between_queries (D) queries back and its island fits, else the chain restarts at 1.  Frames that stop before the
+    islands (low scores, no groups ...) make no update.  A detector that starts empty at frame s holds the same chain cut to the
+    updates at frames >= s, and a verdict reads the length only as ``nentries > k``.  So a frame f is judged alike iff the cut
+    chain still has more than k links whenever the whole one has.  Links are at most D frames apart, so going back from the
+    link at f the j-th earlier one lies at f - j D or later: the frames s .. f hold at least floor((f - s) / D) + 1 links of a
+    chain that reaches back past s (and the whole chain otherwise).  That is more than k for every f >= first as soon as
+    first - s >= k D.  With D <= 0 every update restarts the chain and with k <= 0 its length is never short: no warm-up at all.
+    The bound is met with equality by a stream whose every D-th frame alone reaches the islands."""
+    return max(int(k), 0) * max(int(max_distance_between_queries), 0)
+
+
+def sharded_detect(fill, submit, collect, first: int, end: int, warmup: int = DETECT_WARMUP, collect_many=None, params=None):
     """One rank's part of the detection over a stream whose features every rank holds: the frames before the share enter
     the database WITHOUT being queries (``fill(a, b)``: frames a .. b - 1; svo_lc_fill_features_batch), then the share --
     preceded by ``warmup`` frames whose verdicts are discarded -- is queued (``submit(a, b)``) and collected
     (``collect()`` -> dict(status, query, match); ``collect_many(k)`` -> a list of k of them, if given).  Returns the verdicts of frames first .. end - 1, which are those of ONE
     detector run over the whole stream: a query's candidates, scores and normalisation score depend on the database alone,
-    the temporal window on the last few queries alone."""
+    the temporal window on the last few queries alone.
+
+    How few "the last few" are depends on the detector: ``params`` -- a mapping or an object with ``k`` and
+    ``max_distance_between_queries``, e.g. the detector's svo_lc_params -- lengthens the warm-up to :func:`detect_warmup` of
+    them where ``warmup`` is shorter.  Without ``params`` the warm-up is ``warmup`` as given, which is enough for the
+    reference's k 1 / max_distance_between_queries 2 (2 frames) and for every setting with k * max_distance_between_queries
+    <= 8."""
+    if params is not None:
+        get = params.__getitem__ if hasattr(params, "keys") else lambda name: getattr(params, name)
+        warmup = max(warmup, detect_warmup(get("k"), get("max_distance_between_queries")))
     start = max(0, first - warmup)
     fill(0, start)
     # queued a piece ahead of the collection: host arrays go through the detector's small ring of pinned slots, so a submit

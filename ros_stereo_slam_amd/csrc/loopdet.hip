@@ -429,6 +429,7 @@ void svo_lc_default_params(svo_lc_params *p)
 int svo_lc_create(svo_ctx *ctx, const svo_lc_params *params, int width, int height, int channels, svo_lc **out)
 {
     SVO_CHECK_ARG(ctx && out);
+    *out = nullptr;
     svo_lc *l = new svo_lc();
     l->ctx = ctx;
     if (params)
@@ -436,11 +437,13 @@ int svo_lc_create(svo_ctx *ctx, const svo_lc_params *params, int width, int heig
     else
         svo_lc_default_params(&l->prm);
     const svo_lc_params &p = l->prm;
+    // k < 0 would pass every frame that reaches the temporal check, an alpha outside [0, 1] (or a NaN, which fails both
+    // comparisons) cuts the candidates at no fraction of the normalisation score: refused, as a negative dislocal is
     if (p.n_features < 8 || p.n_features > 2048 || p.max_entries < 2 || p.dislocal < 0 || p.max_db_results < 1 ||
-        p.max_db_results > LC_MAX_CAND) {
+        p.max_db_results > LC_MAX_CAND || p.k < 0 || !(p.alpha >= 0.f && p.alpha <= 1.f)) {
         delete l;
-        svo_set_error("svo_lc_create: n_features in 8..2048, max_entries >= 2, max_db_results in 1..%d (the candidate list "
-                      "of a query is cut there BEFORE removeLowScores and the islands)", LC_MAX_CAND);
+        svo_set_error("svo_lc_create: n_features in 8..2048, max_entries >= 2, dislocal >= 0, k >= 0, alpha in 0..1, max_db_results "
+                      "in 1..%d (the candidate list of a query is cut there BEFORE removeLowScores and the islands)", LC_MAX_CAND);
         return SVO_ERR_ARG;
     }
     l->w = width;

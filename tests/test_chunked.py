@@ -244,7 +244,7 @@ def _loop_images_small(n):
     size, K4 = (320, 120), (180.0, 180.0, 160.0, 60.0)
     poses = synth.loop_trajectory(n, half_x=6, half_z=10, radius=4, step=0.5)
     sc = synth.Scene(wall_x=14, z_min=-18, z_max=18)
-    return [sc.stereo(R, t, K=K4, size=size)[0] for R, t in poses]
+    return [sc.render(R, t, K=K4, size=size)[0] for R, t in poses]      # the left views (stereo()[0]) without rendering the right ones
 
 
 def _closures_of(feats):
@@ -318,7 +318,7 @@ def test_detector_closures_from_features_gathered_over_gloo():
 # ---- the detector SHARDED like the front-end: every rank fills its database with the frames before its
 # share (entries that are not queries), queries its own frames after a short warm-up of the temporal window, rank 0 only
 # gates the gathered verdicts.  The verdicts must be those of ONE detector over the whole stream. ----
-def _sharded_detector_worker(rank, world, port, n, q):
+def _sharded_detector_worker(rank, world, port, n, q, lc=None):
     import torch.distributed as dist
 
     from oracle import orc
@@ -340,7 +340,7 @@ def _sharded_detector_worker(rank, world, port, n, q):
         an, axy, adesc = chunked.all_gather_frame_features(dist, fn, fxy, fdesc, counts=[e - s for s, e in shares])
         feats = [(axy[i, :an[i]], adesc[i, :an[i]]) for i in range(n)]
         voc = orc.Vocabulary.train([d for _, d in feats[::2]], k=9, L=4, seed=1)      # every rank: the same vocabulary
-        det = LoopDetector(Params(seed=5, n_features=200), voc=voc, di_levels=2)
+        det = LoopDetector(Params(seed=5, n_features=200, **(lc or {})), voc=voc, di_levels=2)
         queue = []
 
         def fill(a, b):
@@ -354,7 +354,7 @@ def _sharded_detector_worker(rank, world, port, n, q):
             i = queue.pop(0)
             return det.detect_features(*feats[i])
 
-        mine = chunked.sharded_detect(fill, submit, collect, lo, hi)
+        mine = chunked.sharded_detect(fill, submit, collect, lo, hi, params=det.p if lc else None)
         assert len(mine) == hi - lo and all(v["query"] == lo + k for k, v in enumerate(mine))
         allv = chunked.gather_verdicts(dist, mine, shares)
         if rank == 0:
@@ -395,6 +395,39 @@ def test_detector_sharded_over_gloo_gives_the_one_detector_verdicts(world):
     assert tag == "sharded detector"
     assert status == [v["status"] for v in want] and match == [v["match"] for v in want]
     assert closures == want_closures
+
+
+@pytest.mark.parametrize("k,world", [(3, 2), (3, 3), (9, 2), (9, 3)])
+def test_detector_sharded_over_gloo_at_larger_k(k, world):
+    """The same flow at k 3 and k 9, sharded_detect told the detector's parameters (alpha 0.01 lets nearly every frame reach
+    the window, which is then longer than k where the later ranks' shares begin: the case the fixed warm-up of 8 frames got
+    wrong at k 9)."""
+    import torch.multiprocessing as mp
+
+    from oracle import orc
+    from oracle.loop_detector import LoopDetector, Params
+
+    n, lc = 141, dict(alpha=float(np.float32(0.01)), k=k)
+    imgs = _loop_images_small(n)
+    feats = [(xy, desc) for xy, _, _, _, desc in (orc.orb_extract(im, 200, 20) for im in imgs)]
+    voc = orc.Vocabulary.train([d for _, d in feats[::2]], k=9, L=4, seed=1)
+    det = LoopDetector(Params(seed=5, n_features=200, **lc), voc=voc, di_levels=2)
+    want = [det.detect_features(xy, d) for xy, d in feats]
+    assert all(want[first]["status"] in (0, 7) for first, _ in chunked.detect_shares(n, world)[1:])   # the window is past k there
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        port = sk.getsockname()[1]
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_sharded_detector_worker, args=(r, world, port, n, q, lc)) for r in range(world)]
+    for p in procs:
+        p.start()
+    tag, closures, status, match = q.get(timeout=900)
+    for p in procs:
+        p.join(timeout=120)
+        assert p.exitcode == 0
+    assert tag == "sharded detector"
+    assert status == [v["status"] for v in want] and match == [v["match"] for v in want]
 
 
 def test_poses7_is_pose7_element_by_element():

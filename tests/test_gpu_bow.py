@@ -291,6 +291,38 @@ def test_detector_sharded_over_ranks_gives_the_one_detector_verdicts(ctx, loop_s
     assert [(v["status"], v["query"], v["match"]) for v in got] == [(v["status"], v["query"], v["match"]) for v in want]
 
 
+@pytest.mark.parametrize("world", [2, 3])
+@pytest.mark.parametrize("k", [3, 9])
+def test_detector_sharded_over_ranks_at_larger_k(ctx, loop_setup, k, world):
+    """The same rank-after-rank flow at k 3 and k 9 (alpha 0.01: the window is tens of entries long where the shares begin):
+    sharded_detect is told the detector's parameters and warms the window up for k * max_distance_between_queries frames --
+    with its fixed 8 the first frame of every later share waited for the window at k 9 (tests/test_loopdet_params.py)."""
+    from ros_stereo_slam_amd import chunked
+
+    poses, imgs, feats, gv, ov = loop_setup
+    n = len(feats)
+    fn = np.array([len(f[0]) for f in feats], np.int32)
+    fxy, fdesc = np.zeros((n, 500, 2), np.float32), np.zeros((n, 500, 8), np.uint32)
+    for i, f in enumerate(feats):
+        fxy[i, :fn[i]], fdesc[i, :fn[i]] = f[0], f[4]
+    one = capi.LoopDetector(ctx, SIZE[0], SIZE[1], 3, seed=5, alpha=0.01, k=k)
+    one.set_vocabulary(gv, 2)
+    one.submit_features_batch(fn, fxy, fdesc)
+    want = [one.collect() for _ in range(n)]
+    one.close()
+    shares = chunked.detect_shares(n, world)
+    assert all(want[first]["status"] in (0, 7) for first, _ in shares[1:])     # the window is past k where a share begins
+    got = []
+    for first, end in shares:
+        det = capi.LoopDetector(ctx, SIZE[0], SIZE[1], 3, seed=5, alpha=0.01, k=k)
+        det.set_vocabulary(gv, 2)
+        got += chunked.sharded_detect(lambda a, b: det.fill_features_batch(fn[a:b], fxy[a:b], fdesc[a:b]),
+                                      lambda a, b: det.submit_features_batch(fn[a:b], fxy[a:b], fdesc[a:b]), det.collect, first, end,
+                                      params=det.prm)
+        det.close()
+    assert [(v["status"], v["query"], v["match"]) for v in got] == [(v["status"], v["query"], v["match"]) for v in want]
+
+
 def test_more_than_8192_entries_and_the_wide_candidate_selection(ctx, loop_setup):
     """The candidate selection keeps 8 entries per thread up to 8192 database entries and 16 beyond (eight ranks' shares of the
     driver's bench run are 12 801 frames).  (a) The wide form on the small stream (SVO_BOW_TOPK_PER=16 in a child process) gives
