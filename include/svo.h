@@ -636,6 +636,44 @@ int svo_lc_collect_ex(svo_lc *lc, int *status, int *query, int *match, int *cand
 int svo_anms(svo_ctx *ctx, const float *xy, const float *response, int n, int num_to_keep, int *out_idx,
              int *count, int mem);
 
+/* ---- FAST: cv::FAST(image, kps, threshold, nonmaxSuppression), src/ANMS.cpp:76, and the FAST -> ANMS key-point source ----
+ * The algorithm is the one tests/fast_numpy.py states; TYPE_9_16 only.  Grey is the image itself (c = 1) or
+ * cvtColor's integer weights on B, G, R (c = 3).  A pixel (x, y), 3 <= x < w - 3 and 3 <= y < h - 3, is a corner when nine cyclically
+ * contiguous pixels of the radius-3 ring are all > centre + threshold or all < centre - threshold.  Its score is the largest
+ * threshold at which it is still one: over the 16 arcs of nine, the largest of min(ring - centre) and of min(centre - ring), minus
+ * one.  nonmax_suppression != 0 keeps a corner whose score is strictly above the scores of its eight neighbours (0 for a neighbour
+ * that is no corner or lies on the 3-pixel border; equal neighbours remove each other).  max_keypoints > 0 is
+ * KeyPointsFilter::retainBest: every key point whose response is at or above the max_keypoints-th largest stays, ties included, so an
+ * image can return more than max_keypoints.
+ *
+ * Output: key points in row-major order (y ascending, then x ascending); xy: the pixel as floats; response: the score with
+ * suppression, 0 without (what cv::FAST leaves); KeyPoint::size 7 and angle -1 are constants and are not returned.
+ *
+ * svo_fast_detect_batch: n_images (1 ... 16) images of one size, w x h x c bytes each; images: a host array of host or device pointers
+ * according to mem; xy / response hold n_images x cap entries, image i's at i * cap (response may be NULL); n: HOST ints in both
+ * modes -- the call waits once, for the counts; score (optional: NULL, or n_images x w x h bytes following mem): the score plane
+ * before suppression, 0 where no corner fires and on the border (diagnostics: it localises a parity failure).  An image with
+ * w < 7 or h < 7 is legal and has no key points.  SVO_ERR_ARG: null ctx / images / an image / prm / xy / n, xy, response or n not
+ * 4-byte aligned, c not 1 or 3, n_images outside 1 ... 16, cap < 1, w or h below 1 or above 16384, threshold outside 0 ... 255,
+ * max_keypoints < 0.  SVO_ERR_CAPACITY: an image has more than cap key points -- every n[i] holds the needed count and the first
+ * min(n[i], cap) key points of each image, in row-major order, are valid; nothing is written past cap.
+ *
+ * svo_fast_anms_batch: per image exactly what svo_fast_detect_batch, svo_anms(xy, response, n[i], num_to_keep) and a gather of xy /
+ * response by the returned indices give, in ANMS's response-sorted order; n[i] is the kept count.  The key points stay on the
+ * device in between (the host reads only the counts).  num_to_keep < 1: SVO_ERR_ARG.  When detection overflows cap the call returns
+ * SVO_ERR_CAPACITY with the detector's counts in n and runs no ANMS (xy / response are then unspecified).  svo_anms has no bound
+ * on n of its own: it is all-pairs, its time grows with n^2, and cap is the caller's limit.                                     */
+typedef struct svo_fast_params {
+    int threshold;          /* 10 (cv's default; the reference passes 1) */
+    int nonmax_suppression; /* 1 */
+    int max_keypoints;      /* 0 = all */
+} svo_fast_params;
+void svo_fast_default_params(svo_fast_params *p);
+int svo_fast_detect_batch(svo_ctx *ctx, const uint8_t *const *images, int n_images, int w, int h, int c,
+                          const svo_fast_params *prm, int cap, float *xy, float *response, uint8_t *score, int *n, int mem);
+int svo_fast_anms_batch(svo_ctx *ctx, const uint8_t *const *images, int n_images, int w, int h, int c,
+                        const svo_fast_params *prm, int num_to_keep, int cap, float *xy, float *response, int *n, int mem);
+
 /* ---- PnP-RANSAC: cv::solvePnPRansac(obj,img,K,0,rvec,tvec,false,its,thr,conf,inliers) --------- */
 /* replaces src/keyFrameManagement.cpp:84 (100, 1.0, 0.99) and :88 (100, 8.0, 0.98).
  * obj: n*3 floats (world), img: n*2 floats, K4 = {fx, fy, cx, cy} (HOST doubles), no

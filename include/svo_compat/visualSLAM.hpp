@@ -50,6 +50,13 @@ class visualSLAM {
     // in ORB's place
     bool SURF_FLAG = false;
     int surfHessian = 1200;
+    // with DENSE_FLAG == true: true = the reference points of stereoTriangulate come from fastKeypointExtractor (cv::FAST as the
+    // demo of src/ANMS.cpp:76 calls it, threshold 1) instead of the grid; fastKeep > 0 passes them through
+    // adaptiveNonMaximalSuppresion(kps, fastKeep) (src/ANMS.cpp:18-67) on the device.  Off: every method issues the calls it
+    // always issued.
+    bool FAST_FLAG = false;
+    int fastThreshold = 1;
+    int fastKeep = 0;
     double focal_x = 7.188560000000e+02, cx = 6.071928000000e+02;
     double focal_y = 7.188560000000e+02, cy = 1.852157000000e+02;
     int gridStep = 30;              // src/triangulation.cpp:89
@@ -103,6 +110,42 @@ class visualSLAM {
         return out;
     }
 
+    // ---- src/ANMS.cpp:69-82: cv::FAST(image, kps, fastThreshold) [-> adaptiveNonMaximalSuppresion(kps, fastKeep)] ----
+    // Key points carry their response (the corner score), size 7 and angle -1 as cv::FAST leaves them; row-major order with
+    // fastKeep == 0, ANMS's response-sorted order otherwise.
+    std::vector<KeyPoint> fastKeypointExtractor(Mat img)
+    {
+        std::vector<KeyPoint> out;
+        if (mat_data(img) == nullptr)
+            return out;
+        svo_fast_params prm;
+        svo_fast_default_params(&prm);
+        prm.threshold = fastThreshold;
+        const uint8_t *imgs[1] = {mat_data(img)};
+        const int w = mat_cols(img), h = mat_rows(img), c = mat_channels(img);
+        int cap = 4096, n = 0;
+        std::vector<float> xy, resp;
+        for (;;) {
+            xy.resize((size_t)cap * 2);
+            resp.resize((size_t)cap);
+            const int rc = fastKeep > 0 ? svo_fast_anms_batch(ctx_, imgs, 1, w, h, c, &prm, fastKeep, cap, xy.data(), resp.data(), &n,
+                                                              SVO_MEM_HOST)
+                                        : svo_fast_detect_batch(ctx_, imgs, 1, w, h, c, &prm, cap, xy.data(), resp.data(), nullptr, &n,
+                                                                SVO_MEM_HOST);
+            if (rc != SVO_ERR_CAPACITY)
+                check(rc);
+            if (rc == SVO_OK)
+                break;
+            cap = n;  // the needed count
+        }
+        out.reserve((size_t)n);
+        for (int i = 0; i < n; i++) {
+            out.emplace_back(xy[2 * (size_t)i], xy[2 * (size_t)i + 1], 7.f);
+            out.back().response = resp[(size_t)i];
+        }
+        return out;
+    }
+
     // ---- src/tracking.cpp:14-28 ----
     void denseLKtracking(const Mat &refImg, const Mat &curImg, std::vector<Point2f> &refPts,
                          std::vector<Point2f> &trackPts)
@@ -124,7 +167,7 @@ class visualSLAM {
         compact2(mask, refPts, trkPts);
     }
 
-    // ---- src/triangulation.cpp:73-166 (both branches of DENSE_FLAG) ----
+    // ---- src/triangulation.cpp:73-166 (both branches of DENSE_FLAG; FAST_FLAG swaps the dense branch's key-point source) ----
     void stereoTriangulate(const Mat &im1, const Mat &im2, std::vector<Point3f> &ref3dPts,
                            std::vector<Point2f> &ref2dPts)
     {
@@ -134,7 +177,7 @@ class visualSLAM {
         }
         std::vector<Point2f> refPts, trkPts;
         if (DENSE_FLAG) {
-            std::vector<KeyPoint> dkps = denseKeypointExtractor(im1, gridStep);
+            std::vector<KeyPoint> dkps = FAST_FLAG ? fastKeypointExtractor(im1) : denseKeypointExtractor(im1, gridStep);
             for (const KeyPoint &k : dkps)
                 refPts.emplace_back(k.pt);
             denseLKtracking(im1, im2, refPts, trkPts);

@@ -739,6 +739,77 @@ def sift_pyramid(self, image, params=None):
     return gauss, dog
 
 
+class FastParams(C.Structure):
+    """``svo_fast_params``: cv::FAST's arguments and retainBest's budget (max_keypoints 0 = all)."""
+    _fields_ = [("threshold", C.c_int), ("nonmax_suppression", C.c_int), ("max_keypoints", C.c_int)]
+
+
+def fast_params(**overrides) -> FastParams:
+    p = FastParams()
+    load().svo_fast_default_params(C.byref(p))
+    for k, v in overrides.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def _fast_call(self, images, prm, cap, keep, score):
+    """Both FAST entry points: per image (xy [n, 2], response [n][, score [h, w]]) as host arrays."""
+    nimg = len(images)
+    w, h, c = _image_shape(images[0])
+    if cap is None:
+        cap = max((w - 6) * (h - 6), 1)          # no image has more key points than interior pixels
+    n = (C.c_int * max(nimg, 1))()
+    e = nimg * cap
+    dev = _is_device(images[0])
+    if dev:
+        import torch
+
+        images = [im.contiguous() for im in images]
+        fb = torch.zeros(e * 3, dtype=torch.float32, device=images[0].device)
+        sb = torch.zeros((nimg, h, w), dtype=torch.uint8, device=images[0].device) if score else None
+        torch.cuda.synchronize(images[0].device)
+        args = [C.c_void_p(fb.data_ptr()), C.c_void_p(fb.data_ptr() + 8 * e)]
+    else:
+        images = [np.ascontiguousarray(im, np.uint8) for im in images]
+        xy, resp = np.zeros((nimg, cap, 2), np.float32), np.zeros((nimg, cap), np.float32)
+        sb = np.zeros((nimg, h, w), np.uint8) if score else None
+        args = [_ptr(xy), _ptr(resp)]
+    ptrs = (C.c_void_p * max(nimg, 1))(*[_ptr(im).value for im in images])
+    mem = MEM_DEVICE if dev else MEM_HOST
+    if keep is None:
+        rc = self.lib.svo_fast_detect_batch(self._h, ptrs, nimg, w, h, c, C.byref(prm), cap, *args, _ptr(sb), n, mem)
+    else:
+        rc = self.lib.svo_fast_anms_batch(self._h, ptrs, nimg, w, h, c, C.byref(prm), keep, cap, *args, n, mem)
+    if rc != SVO_OK:
+        err = SvoError(rc, self.lib.svo_last_error().decode(errors="replace"))
+        err.needed = list(n[:nimg])
+        raise err
+    if dev:
+        _check(self.lib.svo_ctx_sync(self._h))
+        hb = fb.cpu().numpy()
+        xy, resp = hb[:2 * e].reshape(nimg, cap, 2), hb[2 * e:].reshape(nimg, cap)
+        sb = sb.cpu().numpy() if score else None
+    return [(xy[i, :n[i]].copy(), resp[i, :n[i]].copy()) + ((sb[i].copy(),) if score else ()) for i in range(nimg)]
+
+
+@_ctx_method
+def fast_detect(self, images, threshold=10, nonmax=True, max_keypoints=0, cap=None, score=False):
+    """``svo_fast_detect_batch``: cv::FAST (TYPE_9_16) on 1 ... 16 images of one size (host arrays or device tensors) in one set
+    of launches -> per image (xy [n, 2], response [n] float32[, score [h, w] uint8]) in row-major order.  More than ``cap`` key
+    points in an image: SvoError(SVO_ERR_CAPACITY) whose ``needed`` lists the counts."""
+    prm = fast_params(threshold=threshold, nonmax_suppression=int(bool(nonmax)), max_keypoints=max_keypoints)
+    return _fast_call(self, images, prm, cap, None, score)
+
+
+@_ctx_method
+def fast_anms(self, images, num_to_keep, threshold=10, nonmax=True, max_keypoints=0, cap=None):
+    """``svo_fast_anms_batch``: FAST, then adaptive non-maximal suppression of each image's key points without leaving the
+    device -> per image (xy [k, 2], response [k]) in ANMS's response-sorted order."""
+    prm = fast_params(threshold=threshold, nonmax_suppression=int(bool(nonmax)), max_keypoints=max_keypoints)
+    return _fast_call(self, images, prm, cap, int(num_to_keep), False)
+
+
 def brief_default_pattern(bytes=32) -> np.ndarray:
     """``svo_brief_default_pattern``: the library's own test table of a descriptor length, [8 * bytes, 4] int8 rows of
     (y1, x1, y2, x2).  Host only."""

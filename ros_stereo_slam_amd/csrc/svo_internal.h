@@ -176,6 +176,9 @@ struct svo_ctx {
     std::vector<float> wls_lut_host;
     double wls_lut_sigma = 0;
     int wls_lut_c = 0;
+    // fast.hip: the grey, fired and score planes of a batch, the per-wavefront counts and offsets of the ordered compaction, the
+    // key-point lists of host calls and of the chained ANMS (layout: fast_plan.hip.h)
+    DevBuf fast_work;
 };
 
 // Low-latency host wait for everything queued on the context's stream: records an event and
