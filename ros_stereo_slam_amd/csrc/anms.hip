@@ -12,19 +12,9 @@
 #include <cfloat>
 
 #include "svo_internal.h"
+#include "wave_ops.hip.h"
 
 namespace {
-
-// exact wave-wide integer sum (per-lane values < 2^24)
-__device__ __forceinline__ int wave_sum_int(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false);   // quad_perm [2,3,0,1]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, false);  // row_half_mirror
-    v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, false);  // row_mirror
-    return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) +
-           __builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48);
-}
 
 // One WAVEFRONT per keypoint in every all-pairs pass: the 64 lanes stride over the other
 // keypoints (coalesced reads of a 17-50 KB array that stays in L2) and the per-lane partials
@@ -117,7 +107,7 @@ template <int KPW> __global__ __launch_bounds__(64) void anms_rank_kernel(AnmsBa
     }
 #pragma unroll
     for (int q = 0; q < KPW; q++) {
-        const int rank = wave_sum_int(cnt[q]);
+        const int rank = svo::wave_sum_dpp(cnt[q]);
         if (lane == 0 && i0 + q < n) {
             order[rank] = i0 + q;
             const float2 p = xy[i0 + q];
@@ -226,7 +216,7 @@ template <int KPW> __global__ __launch_bounds__(64) void anms_decide_kernel(Anms
     }
 #pragma unroll
     for (int q = 0; q < KPW; q++) {
-        const int g = wave_sum_int(gt[q]), e = wave_sum_int(ge[q]);
+        const int g = svo::wave_sum_dpp(gt[q]), e = svo::wave_sum_dpp(ge[q]);
         // radiiSorted[keep] (descending, 0-based) == ri  <=>  gt <= keep < ge
         if (lane == 0 && s0 + q < n && g <= keep && keep < e)
             *decision = ri[q];  // every keypoint that qualifies writes the same value

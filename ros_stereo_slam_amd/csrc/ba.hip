@@ -19,7 +19,9 @@
 // every thread carries redundantly (no broadcast, no extra barrier).
 // Bound: f64 VALU latency of one workgroup (the problem is 4096 x ~1 kflop per pass); HBM traffic
 // is the points once (20 B each) + 48 B per point per pass of L2-resident estimates.
+#include "small_solve.hip.h"
 #include "svo_internal.h"
+#include "wave_ops.hip.h"
 
 namespace {
 
@@ -102,77 +104,6 @@ __device__ __forceinline__ void ba_sym3_inv(const double *Hll, double lambda, do
     Vi[5] = (a * d - b * b) * id;
 }
 
-// K per-thread partials -> K totals in every thread, fixed order: balanced tree inside each
-// wavefront (xor butterfly, commutative additions: every lane holds the same bits), then the four
-// wave totals ((w0 + w1) + w2) + w3 through LDS.
-template <int K> __device__ __forceinline__ void block_sum(double (&v)[K], double *s_red /* [4][K] */)
-{
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-        double x = v[k];
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1)
-            x = x + __shfl_xor(x, m, 64);
-        v[k] = x;
-    }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();  // the previous reduction's readers are done with s_red
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < K; k++)
-            s_red[wave * K + k] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; k++)
-        v[k] = ((s_red[k] + s_red[K + k]) + s_red[2 * K + k]) + s_red[3 * K + k];
-}
-
-__device__ __forceinline__ double block_max(double x, double *s_red)
-{
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1)
-        x = fmax(x, __shfl_xor(x, m, 64));
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();
-    if (lane == 0)
-        s_red[wave] = x;
-    __syncthreads();
-    return fmax(fmax(s_red[0], s_red[1]), fmax(s_red[2], s_red[3]));
-}
-
-__device__ bool ba_chol6_solve(const double *Ain, const double *b, double *x)
-{
-    double L[36];
-    for (int k = 0; k < 36; k++)
-        L[k] = 0;
-    for (int i = 0; i < 6; i++)
-        for (int j = 0; j <= i; j++) {
-            double s = Ain[6 * i + j];
-            for (int k = 0; k < j; k++)
-                s -= L[6 * i + k] * L[6 * j + k];
-            if (i == j) {
-                if (!(s > 0))
-                    return false;
-                L[6 * i + i] = sqrt(s);
-            } else
-                L[6 * i + j] = s / L[6 * j + j];
-        }
-    double y[6];
-    for (int i = 0; i < 6; i++) {
-        double s = b[i];
-        for (int k = 0; k < i; k++)
-            s -= L[6 * i + k] * y[k];
-        y[i] = s / L[6 * i + i];
-    }
-    for (int i = 5; i >= 0; i--) {
-        double s = y[i];
-        for (int k = i + 1; k < 6; k++)
-            s -= L[6 * k + i] * x[k];
-        x[i] = s / L[6 * i + i];
-    }
-    return true;
-}
-
 // SE3Quat::exp([omega; upsilon]) * (R, t)
 __device__ void ba_se3_exp_mul(const double *d, const double *R, const double *t, double *Rn, double *tn)
 {
@@ -246,7 +177,7 @@ __global__ __launch_bounds__(BA_T) void ba_3d2d_kernel(BaArgs a)
             ba_error(R, t, X + 3 * i, z[i].x, z[i].y, f, cx, cy, e);
             c1[0] += e[0] * e[0] + e[1] * e[1];
         }
-        block_sum<1>(c1, s_red);
+        svo::block_sum<1>(c1, s_red);
         const double chi = c1[0];
         if (it == 0)
             chi_first = chi_last = chi;
@@ -271,7 +202,7 @@ __global__ __launch_bounds__(BA_T) void ba_3d2d_kernel(BaArgs a)
                          h2 = L.A[2] * L.A[2] + L.A[5] * L.A[5];
             md = fmax(md, fmax(h0, fmax(h1, h2)));
         }
-        block_sum<27>(acc, s_red);
+        svo::block_sum<27>(acc, s_red);
         double Hpp[36], bp[6];
         {
             int k = 0;
@@ -287,7 +218,7 @@ __global__ __launch_bounds__(BA_T) void ba_3d2d_kernel(BaArgs a)
                 bp[r] = acc[21 + r];
         }
         if (it == 0) {  // computeLambdaInit: tau * max |diag H|
-            double maxdiag = block_max(md, s_red);
+            double maxdiag = svo::block_max(md, s_red);
             for (int r = 0; r < 6; r++)
                 maxdiag = fmax(maxdiag, fabs(Hpp[7 * r]));
             lambda = 1e-5 * maxdiag;
@@ -324,7 +255,7 @@ __global__ __launch_bounds__(BA_T) void ba_3d2d_kernel(BaArgs a)
                 for (int r = 0; r < 6; r++)
                     acc[21 + r] += Y[3 * r] * bl[0] + Y[3 * r + 1] * bl[1] + Y[3 * r + 2] * bl[2];
             }
-            block_sum<27>(acc, s_red);
+            svo::block_sum<27>(acc, s_red);
             double S[36], bs[6], dp[6];
             {
                 int k = 0;
@@ -340,7 +271,7 @@ __global__ __launch_bounds__(BA_T) void ba_3d2d_kernel(BaArgs a)
                 for (int r = 0; r < 6; r++)
                     bs[r] = bp[r] - acc[21 + r];
             }
-            const bool ok2 = ba_chol6_solve(S, bs, dp);  // wave-uniform
+            const bool ok2 = svo::chol6_solve(S, bs, dp);  // wave-uniform
             double Rn[9], tn[3], tempChi, scale = 0;
             if (ok2) {
                 ba_se3_exp_mul(dp, R, t, Rn, tn);
@@ -372,7 +303,7 @@ __global__ __launch_bounds__(BA_T) void ba_3d2d_kernel(BaArgs a)
                     ba_error(Rn, tn, xn, z[i].x, z[i].y, f, cx, cy, e);
                     c2[1] += e[0] * e[0] + e[1] * e[1];
                 }
-                block_sum<2>(c2, s_red);
+                svo::block_sum<2>(c2, s_red);
                 scale = c2[0];
                 tempChi = c2[1];
                 for (int r = 0; r < 6; r++)

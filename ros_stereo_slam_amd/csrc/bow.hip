@@ -56,9 +56,7 @@ struct ClusterOut {
 
 __device__ __forceinline__ long long block_sum_ll(long long v, long long *s_red, int t)
 {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        v += __shfl_xor(v, o, 64);
+    v = svo::wave_sum(v);
     __syncthreads();
     if ((t & 63) == 0)
         s_red[t >> 6] = v;
@@ -940,10 +938,7 @@ __device__ __forceinline__ void di_nearest_body(const uint32_t *__restrict__ A, 
         }
     }
     // the second smallest of the multiset
-    int s2 = (bj == wj && b1 == w1) ? b2 : b1;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-        s2 = min(s2, __shfl_xor(s2, off, 64));
+    const int s2 = svo::wave_min((bj == wj && b1 == w1) ? b2 : b1);
     if (lane == 0) {
         best_j[i] = w1 < 1000000000 ? wj : -1;
         d1[i] = w1;

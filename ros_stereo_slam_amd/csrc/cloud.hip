@@ -98,21 +98,13 @@ __device__ __forceinline__ bool box_excluded(double mind2, double thr)
     return mind2 * (1.0 - 1e-6) - 1e-300 >= thr;
 }
 
-__device__ __forceinline__ double wave_min_double(double v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-        v = fmin(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
 // the live child with the smallest bound among those that cannot be excluded, or -1
 __device__ __forceinline__ int pick_child(bool live, double md, double thr)
 {
     const bool cand = live && !box_excluded(md, thr);
     if (__ballot(cand) == 0)
         return -1;
-    const double m = wave_min_double(cand ? md : INF_D);
+    const double m = svo::wave_min(cand ? md : INF_D);
     const unsigned long long at_min = __ballot(cand && md == m);
     return __builtin_ctzll(at_min ? at_min : __ballot(cand));  // (no lane at the minimum: bounds that do not compare)
 }

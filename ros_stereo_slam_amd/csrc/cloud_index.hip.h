@@ -4,6 +4,7 @@
 // of a point to a box.  Every kernel here has internal linkage: each of the two translation units carries its own copy.
 #pragma once
 #include "svo_internal.h"
+#include "wave_ops.hip.h"
 
 namespace {
 
@@ -236,22 +237,6 @@ __global__ __launch_bounds__(256) void sorg_gather_kernel(const float *__restric
     pts[3 * i + 2] = xyz[3 * j + 2];
 }
 
-__device__ __forceinline__ float wave_min(float v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-        v = fminf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-        v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
 // number of elements at a level of the hierarchy: 0 = points, 1..3 = boxes
 __device__ __forceinline__ int level_count(int m, int level)
 {
@@ -289,8 +274,8 @@ __global__ __launch_bounds__(256) void sorg_box_kernel(const float *__restrict__
     }
 #pragma unroll
     for (int a = 0; a < 3; a++) {
-        lo[a] = wave_min(lo[a]);
-        hi[a] = wave_max(hi[a]);
+        lo[a] = svo::wave_min(lo[a]);
+        hi[a] = svo::wave_max(hi[a]);
     }
     if (lane == 0)
 #pragma unroll

@@ -111,14 +111,6 @@ template <int DA, int DB> __device__ __forceinline__ void polymul(const double *
             out[i + j] += a[i] * b[j];
 }
 
-__device__ __forceinline__ double em_wave_max(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 // LDS of one five-point solve
 struct EmLds {
     double A[45];          // 5 x 9 system after elimination
@@ -300,7 +292,7 @@ __device__ int em_solve_wave(const double2 *__restrict__ q1, const double2 *__re
 #pragma unroll 1
     for (int k = 0; k < MP; k++) {
         const double v = (valid && li >= k && lj >= k) ? fabs(a) : -1.;
-        const double best = em_wave_max(v);
+        const double best = wave_max(v);
         if (!(best >= 1e-12))
             return 0;  // degenerate sample (wave-uniform)
         const int pl = __ffsll((unsigned long long)__ballot(v == best)) - 1;
@@ -860,7 +852,7 @@ __global__ __launch_bounds__(256) void em_iter_kernel(EmBatch b, uint64_t seed, 
                     const double2 u = q1[i], w = q2[i];
                     c += em_error(E, u.x, u.y, w.x, w.y) <= job.thr ? 1 : 0;
                 }
-                c = wave_sum_small(c);
+                c = wave_sum_dpp(c);
                 if (lane == 0)
                     s_cnt[wave][k] = c;
             }

@@ -150,14 +150,6 @@ __device__ bool collinear_last(const float *__restrict__ p, const int (&idx)[M])
     return bad;
 }
 
-__device__ __forceinline__ double wave_max_f64(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 // One RANSAC iteration's models, by one WAVE: up to three unit-norm F (row-major) into Fk_out[27] (LDS, written
 // by lane 0); returns their number (valid in lane 0), -1 when no sample could be drawn (the sequential loop
 // stops there).  The sample is drawn by every lane alike; the 7x9 Gauss-Jordan elimination with full pivoting
@@ -229,7 +221,7 @@ __device__ int fr_solve_wave(const float *__restrict__ p1, const float *__restri
     for (int k = 0; k < M; k++) {
         // the first entry (row-major) of the largest magnitude in rows >= k, columns >= k
         const double v = (valid && li >= k && lj >= k) ? fabs(a) : -1.;
-        const double best = wave_max_f64(v);
+        const double best = wave_max(v);
         if (best < 1e-12) {
             singular = true;
             break;
@@ -258,9 +250,7 @@ __device__ int fr_solve_wave(const float *__restrict__ p1, const float *__restri
         sA[lane] = a;
     if (lane < 9)
         sPerm[lane] = permv;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_fence();
     if (lane != 0)
         return 0;  // the tail is lane 0's
     if (singular)
@@ -607,9 +597,9 @@ __global__ __launch_bounds__(LEAN ? 64 : 256, LEAN ? 5 : 4) void fr_ransac_kerne
                 }
                 cur = nxt;
             }
-            c0 = wave_sum_small(c0);
-            c1 = nm > 1 ? wave_sum_small(c1) : 0;
-            c2 = nm > 2 ? wave_sum_small(c2) : 0;
+            c0 = wave_sum_dpp(c0);
+            c1 = nm > 1 ? wave_sum_dpp(c1) : 0;
+            c2 = nm > 2 ? wave_sum_dpp(c2) : 0;
         }
         if (NW > 1) {
             if (lane == 0) {

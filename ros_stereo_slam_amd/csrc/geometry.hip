@@ -13,6 +13,7 @@
 
 #include "dlt.hip.h"
 #include "svo_internal.h"
+#include "wave_ops.hip.h"
 
 using svo::smallest_right_singular_vector4;
 
@@ -236,14 +237,6 @@ template <int NJ> struct CompactBatchN {  // blockIdx.y picks the job; NJ = 1: a
 };
 using CompactBatch = CompactBatchN<SVO_LK_MAX_JOBS>;
 
-__device__ __forceinline__ int wave_sum_int(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        v += __shfl_xor(v, o);
-    return v;
-}
-
 // number of bytes equal to 1 in a dword
 __device__ __forceinline__ int count_ones_bytes(uint32_t x)
 {
@@ -285,7 +278,7 @@ template <int NJ> __global__ __launch_bounds__(64) void compact_kernel(CompactBa
         for (int i = lane; i < first; i += 64)
             part += mask[i] == 1 ? 1 : 0;
     }
-    int pos0 = __builtin_amdgcn_readfirstlane(wave_sum_int(part));
+    int pos0 = __builtin_amdgcn_readfirstlane(svo::wave_sum(part));
     for (int start = first; start < last; start += 64) {
         const int i = start + lane;
         const bool keep = i < last && mask[i] == 1;

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "svo_internal.h"
+#include "wave_ops.hip.h"
 
 namespace {
 
@@ -58,9 +59,7 @@ __global__ __launch_bounds__(256) void lc_score_kernel(const uint32_t *__restric
         }
         c += best <= thr ? 1 : 0;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-        c += __shfl_xor(c, off, 64);
+    c = svo::wave_sum(c);
     if ((t & 63) == 0)
         s_red[t >> 6] = c;
     __syncthreads();

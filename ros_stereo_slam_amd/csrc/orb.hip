@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "svo_internal.h"
+#include "wave_ops.hip.h"
 
 namespace {
 
@@ -370,14 +371,6 @@ __global__ __launch_bounds__(1024) void select_kernel(OrbLevels L, const int *__
         *d_nsel = s_base;
 }
 
-__device__ __forceinline__ int wave_sum_int(int v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-        v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // one wavefront per selected keypoint: orientation + descriptor, appended at out_base
 __global__ __launch_bounds__(256) void describe_kernel(OrbLevels L, const uint8_t *__restrict__ blur_all,
                                                        const int *__restrict__ sel_idx_all,
@@ -418,8 +411,8 @@ __global__ __launch_bounds__(256) void describe_kernel(OrbLevels L, const uint8_
             m01 += v * p;
         }
     }
-    m10 = wave_sum_int(m10);
-    m01 = wave_sum_int(m01);
+    m10 = svo::wave_sum(m10);
+    m01 = svo::wave_sum(m01);
     const float f10 = (float)m10, f01 = (float)m01;
     const float nrm = sqrtf(f10 * f10 + f01 * f01);
     const float cs = nrm > 0.f ? f10 / nrm : 1.f, sn = nrm > 0.f ? f01 / nrm : 0.f;

@@ -27,6 +27,7 @@
 
 #include "svo_internal.h"
 #include "fast_atan2.hip.h"
+#include "wave_ops.hip.h"
 
 namespace {
 
@@ -677,14 +678,6 @@ __global__ __launch_bounds__(CV_SEL_T) void cv_select_kernel(CvLevels L, const u
         *d_nsel = kept;
 }
 
-__device__ __forceinline__ int wave_sum(int v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-        v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // one wavefront per selected key point; grid (ceil(max want / 4), n_lev, batch)
 __global__ __launch_bounds__(256) void cv_describe_kernel(CvLevels L, const uint8_t *__restrict__ levels,
                                                           const uint8_t *__restrict__ blur_all, const int *__restrict__ sel_idx_all,
@@ -736,8 +729,8 @@ __global__ __launch_bounds__(256) void cv_describe_kernel(CvLevels L, const uint
             m01 += v * p;
         }
     }
-    m10 = wave_sum(m10);
-    m01 = wave_sum(m01);
+    m10 = svo::wave_sum(m10);
+    m01 = svo::wave_sum(m01);
     const float ang = fast_atan2_deg((float)m01, (float)m10);
     const float rad = ang * (float)(3.14159265358979323846 / 180.f);
     const float a = (float)svo_cos((double)rad), b = (float)svo_sin((double)rad);

@@ -20,6 +20,7 @@
 #include <cfloat>
 
 #include "ransac_common.hip.h"
+#include "small_solve.hip.h"
 #include "svo_internal.h"
 
 using namespace svo;
@@ -783,7 +784,7 @@ __device__ __forceinline__ void pnp_hypothesis(const PnpJob &job, int it, int n,
         const float2 u = img2[i];
         cnt += reproj_err_sq(P, K, obj[3 * i], obj[3 * i + 1], obj[3 * i + 2], u.x, u.y) <= thr ? 1 : 0;
     }
-    cnt = wave_sum_small(cnt);
+    cnt = wave_sum_dpp(cnt);
     if (lane == 0)
         counts[it] = cnt;
 }
@@ -911,39 +912,6 @@ __device__ void rodrigues_inv_dev(const double *R, double *r)
     }
 }
 
-__device__ bool chol6_solve(const double *Ain, const double *b, double *x)
-{
-    double L[36];
-    for (int i = 0; i < 36; i++)
-        L[i] = 0;
-    for (int i = 0; i < 6; i++)
-        for (int j = 0; j <= i; j++) {
-            double s = Ain[6 * i + j];
-            for (int k = 0; k < j; k++)
-                s -= L[6 * i + k] * L[6 * j + k];
-            if (i == j) {
-                if (!(s > 0))
-                    return false;
-                L[6 * i + i] = sqrt(s);
-            } else
-                L[6 * i + j] = s / L[6 * j + j];
-        }
-    double y[6];
-    for (int i = 0; i < 6; i++) {
-        double s = b[i];
-        for (int k = 0; k < i; k++)
-            s -= L[6 * i + k] * y[k];
-        y[i] = s / L[6 * i + i];
-    }
-    for (int i = 5; i >= 0; i--) {
-        double s = y[i];
-        for (int k = i + 1; k < 6; k++)
-            s -= L[6 * k + i] * x[k];
-        x[i] = s / L[6 * i + i];
-    }
-    return true;
-}
-
 constexpr int NACC = 28;  // [0] squared error, [1..21] upper-triangular J^T J, [22..27] J^T r
 
 // Fixed-order block reduction of the first NV of a thread's accumulators (256 threads):
@@ -1036,28 +1004,6 @@ struct DltArgs {
     int *status;
 };
 
-template <int KN> __device__ __forceinline__ void block_sum_fixed(double (&v)[KN], double *s_red /* [4][KN] */)
-{
-#pragma unroll
-    for (int k = 0; k < KN; k++) {
-        double x = v[k];
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1)
-            x = x + __shfl_xor(x, m, 64);  // balanced tree; commutative adds: every lane holds the same bits
-        v[k] = x;
-    }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < KN; k++)
-            s_red[wave * KN + k] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < KN; k++)
-        v[k] = ((s_red[k] + s_red[KN + k]) + s_red[2 * KN + k]) + s_red[3 * KN + k];
-}
-
 __global__ __launch_bounds__(256) void pnp_dlt_kernel(DltArgs a)
 {
     __shared__ double s_red[4 * 40], s_A[144], s_V[144], s_cs[16];
@@ -1088,7 +1034,7 @@ __global__ __launch_bounds__(256) void pnp_dlt_kernel(DltArgs a)
                 k++;
             }
     }
-    block_sum_fixed<40>(acc, s_red);
+    block_sum<40>(acc, s_red);
     if (tid >= 64)
         return;  // wave 0 goes on alone: no workgroup barrier below
     int status = 0;

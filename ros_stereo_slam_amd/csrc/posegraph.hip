@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "svo_internal.h"
+#include "wave_ops.hip.h"
 
 namespace {
 
@@ -331,14 +332,6 @@ constexpr int PG_MAX_SEG_CHORDS = 8;  // closure endpoints a segment takes insid
 constexpr int SEG_L = 104;  // regular separator spacing (rows): a segment and its 13 right-hand sides live in LDS
 constexpr int TB = 48;      // tile of the dense reduced solve (8 block rows)
 
-// hand-off of LDS data between the lanes of the ONE wave a workgroup consists of
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // A workgroup barrier that orders LDS traffic only.  __syncthreads() on gfx9 also waits for every global load and store of
 // the wave (one counter for both, and a release fence has to wait for the stores): loads asked for early would be drained
 // at the next barrier.  The kernels below exchange data between their waves through LDS alone.
@@ -463,7 +456,7 @@ __device__ inline bool wave_chol6_inv(double *sS, double *sL, double *sLi, int l
         for (int r = 0; r < 6; r++)
             sLi[6 * r + lane] = x[r];
     }
-    wave_sync();
+    svo::wave_lds_fence();
     return ok;
 }
 
@@ -712,7 +705,7 @@ __global__ __launch_bounds__(BCR_WAVES * 64) void pg_segment_kernel(int nb, int 
                 out[r] = acc;
                 dsts[r] = dst;
             }
-            wave_sync();  // F_q and B_q have been read by every lane
+            svo::wave_lds_fence();  // F_q and B_q have been read by every lane
 #pragma unroll
             for (int r = 0; r < 3; r++)
                 if (dsts[r] >= 0)
@@ -821,7 +814,7 @@ __global__ __launch_bounds__(BCR_WAVES * 64) void pg_segment_kernel(int nb, int 
             for (int k2 = 0; k2 < 2; k2++)
                 if (lane + 64 * k2 < 78)
                     Q[BCR_B + lane + 64 * k2] = v[k2];  // a lane's own entries
-            wave_sync();
+            svo::wave_lds_fence();
 #pragma unroll
             for (int k2 = 0; k2 < 2; k2++) {
                 const int e = lane + 64 * k2;
@@ -834,7 +827,7 @@ __global__ __launch_bounds__(BCR_WAVES * 64) void pg_segment_kernel(int nb, int 
                 }
                 v[k2] = acc;
             }
-            wave_sync();
+            svo::wave_lds_fence();
 #pragma unroll
             for (int k2 = 0; k2 < 2; k2++) {
                 const int e = lane + 64 * k2;
@@ -895,10 +888,10 @@ __global__ __launch_bounds__(BCR_WAVES * 64) void pg_segment_kernel(int nb, int 
                     for (int u = 0; u < 6; u++)
                         acc = fma(Q[6 * i + u], Q[BCR_B + 13 * u + c], acc);
                 }
-                wave_sync();
+                svo::wave_lds_fence();
                 if (lane < 36)
                     Q[BCR_B + 13 * i + c] = acc;
-                wave_sync();
+                svo::wave_lds_fence();
                 int keep = 0;
                 for (int f = 0; f < nf; f++)
                     if (flagged[f] != q)
@@ -923,7 +916,7 @@ __global__ __launch_bounds__(BCR_WAVES * 64) void pg_segment_kernel(int nb, int 
                     if (!known && nf < 4)
                         flagged[nf++] = p;
                 }
-                wave_sync();
+                svo::wave_lds_fence();
             }
         }
         lds_barrier();
@@ -960,7 +953,7 @@ __global__ __launch_bounds__(BCR_WAVES * 64) void pg_segment_kernel(int nb, int 
                     }
                     v[k2] = acc;
                 }
-                wave_sync();
+                svo::wave_lds_fence();
 #pragma unroll
                 for (int k2 = 0; k2 < 2; k2++) {
                     double acc = 0.;
@@ -971,7 +964,7 @@ __global__ __launch_bounds__(BCR_WAVES * 64) void pg_segment_kernel(int nb, int 
                     }
                     v[k2] = acc;
                 }
-                wave_sync();
+                svo::wave_lds_fence();
 #pragma unroll
                 for (int k2 = 0; k2 < 2; k2++) {
                     const int e = lane + 64 * k2;
@@ -1115,7 +1108,7 @@ __device__ __forceinline__ int pg_potf2_lds(bool dbg, double *sL, double *sX, do
             }
             sS6[tid] = v;
         }
-        wave_sync();
+        svo::wave_lds_fence();
         if (!wave_chol6_regs(sS6, tid, fa, fr) && tid == 0 && *s_bad == 0)
             *s_bad = 1 + o2;
         if (tid < 6) {

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "../../include/svo_math.h"  // sin / cos / acos / cbrt / log shared with the oracle, bit for bit
+#include "wave_ops.hip.h"            // wave_sum_dpp (the inlier counts), wave_lds_fence
 
 namespace svo {
 
@@ -51,17 +52,6 @@ struct RansacState {
     int iters_run;
     int pad;
 };
-
-// exact wave-wide integer sum (values small enough that no carry handling is needed)
-__device__ __forceinline__ int wave_sum_small(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false);   // quad_perm [2,3,0,1]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, false);  // row_half_mirror
-    v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, false);  // row_mirror
-    return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) +
-           __builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48);
-}
 
 // Replays the SEQUENTIAL RANSAC loop over iterations [st->next_iter, it_end) (called by one
 // thread: the last wave of fr_ransac_kernel / of pnp_solve_kernel's first phase, thread 0 of pnp_finish_kernel): first-best-wins,
@@ -119,15 +109,6 @@ __device__ inline RansacState ransac_replay(const RansacState *st_in, int first,
     s.next_iter = it;
     s.iters_run = it;
     return s;
-}
-
-// hand-off of LDS data between lanes of ONE wave (LDS ops of a wave execute in order; this
-// only pins the compiler)
-__device__ __forceinline__ void wave_lds_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 }  // namespace svo

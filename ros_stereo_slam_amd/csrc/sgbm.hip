@@ -19,6 +19,7 @@
 //                       invalidate components of <= window pixels (the partition is unique: the result does not depend
 //                       on the order threads run in)
 #include "svo_internal.h"
+#include "wave_ops.hip.h"
 
 #include <climits>
 
@@ -140,14 +141,6 @@ __global__ __launch_bounds__(256) void sgbm_vsum_kernel(SgbmGeom g, const int16_
     }
 }
 
-__device__ __forceinline__ int wave_min(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        v = min(v, __shfl_xor(v, o));
-    return v;
-}
-
 // one step of R6 for the PER disparities of this lane; Lp / minLp: the stored int16 values of the previous step
 template <int PER>
 __device__ __forceinline__ void path_step(const int (&Cv)[PER], int (&Lp)[PER], int &minLp, int (&L)[PER], bool last_lane,
@@ -231,7 +224,7 @@ __global__ __launch_bounds__(256) void sgbm_path_kernel(SgbmGeom g, const int16_
             mn = min(mn, L[k]);
             Lp[k] = (int16_t)L[k];
         }
-        minLp = (int16_t)wave_min(active ? mn : INT_MAX);
+        minLp = (int16_t)svo::wave_min(active ? mn : INT_MAX);
         off += step;
     }
 }
@@ -295,8 +288,8 @@ __global__ __launch_bounds__(64) void sgbm_wta_kernel(SgbmGeom g, const int16_t 
                 key = min(key, s * 512 + lane * PER + k);   // the first d of the smallest S
             }
         }
-        minLp = (int16_t)wave_min(active ? mn : INT_MAX);
-        key = wave_min(key);
+        minLp = (int16_t)svo::wave_min(active ? mn : INT_MAX);
+        key = svo::wave_min(key);
         int minS = key >> 9, best = key & 511;
         if (minS >= SHORT_MAX_)   // strict < from SHRT_MAX: nothing below it -> d = -1 (R7)
             minS = SHORT_MAX_, best = -1;

@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void sor_knn_kernel(const float *__restrict__ 
 #pragma unroll
         for (int t = 0; t < T; t++)
             c += key[t] < test ? 1 : 0;
-        if (svo::wave_sum_small(c) < kk)
+        if (svo::wave_sum_dpp(c) < kk)
             kth = test;
     }
     int c_less = 0;
@@ -73,8 +73,8 @@ __global__ __launch_bounds__(256) void sor_knn_kernel(const float *__restrict__ 
             c_less++;
             s_less += (double)sqrtf(__uint_as_float(key[t]));
         }
-    c_less = svo::wave_sum_small(c_less);
-    const double total = wave_sum_double(s_less) + (double)(kk - c_less) * (double)sqrtf(__uint_as_float(kth));
+    c_less = svo::wave_sum_dpp(c_less);
+    const double total = svo::wave_sum(s_less) + (double)(kk - c_less) * (double)sqrtf(__uint_as_float(kth));
     if (lane == 0)
         dist[a] = (float)(total / kk);
 }

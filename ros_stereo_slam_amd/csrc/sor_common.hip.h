@@ -1,5 +1,5 @@
 // sor_common.hip.h -- device code shared by the two statistical outlier removal paths (sor.hip: brute force,
-// sor_grid.hip: the Morton-ordered kNN): the wave-wide double sum of the mean distances and the cloud statistics.
+// sor_grid.hip: the Morton-ordered kNN): the cloud statistics.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -7,14 +7,6 @@
 #include <cstdint>
 
 namespace {
-
-__device__ __forceinline__ double wave_sum_double(double v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-        v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // mean / stddev of the distances in point order by one thread (PCL's own loop), then the keep mask.  The summing
 // thread reads the distances from LDS: the other waves stage them SOR_STAGE at a time, one chunk ahead (two buffers),

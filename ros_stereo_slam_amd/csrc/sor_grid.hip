@@ -67,7 +67,7 @@ __device__ unsigned knn_kth(const KnnWave &w)
         int c = 0;
         for (int t = w.lane; t < w.nb; t += 64)
             c += w.buf[t] < test ? 1 : 0;
-        if (svo::wave_sum_small(c) < w.kk)
+        if (svo::wave_sum_dpp(c) < w.kk)
             kth = test;
     }
     return kth;
@@ -201,8 +201,8 @@ __global__ __launch_bounds__(256) void sorg_knn_kernel(const float *__restrict__
             s_less += (double)sqrtf(__uint_as_float(v));
         }
     }
-    c_less = svo::wave_sum_small(c_less);
-    const double total = wave_sum_double(s_less) + (double)(kk - c_less) * (double)sqrtf(__uint_as_float(kth));
+    c_less = svo::wave_sum_dpp(c_less);
+    const double total = svo::wave_sum(s_less) + (double)(kk - c_less) * (double)sqrtf(__uint_as_float(kth));
     if (lane == 0)
         dist[idx[i]] = (float)(total / kk);
 }
