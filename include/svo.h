@@ -173,6 +173,43 @@ int svo_transform_points(svo_ctx *ctx, const double *Rt, const float *in_xyz, in
 /* getColors, include/monoUtils.h:180-193: B,G,R of level 0 at (int(y), int(x)) as floats.      */
 int svo_get_colors(svo_ctx *ctx, const svo_pyramid *pyr, const float *xy, int n, float *out_bgr, int mem);
 
+/* ---- duplicate-aware replenishment of a tracked set: removeDuplicate and the top-up of trackSequence, src/ROSslam.py:156-169,
+ * 262-271, and removeDuplicates, include/monoUtils.h:195-213 ----------------------------------------------
+ * svo_dedup_points: keep[i] = 1 when new point i has no reference point near it, else 0.  xy arrays hold 2 floats per point.
+ *   SVO_DEDUP_BOX   the prototype: i is a duplicate when some reference point has rx > qx - r && rx < qx + r && ry > qy - r &&
+ *                   ry < qy + r, every operand promoted to double first (the prototype's query points are float64), all four
+ *                   comparisons strict: |dx| == r is no duplicate.  The prototype marks a duplicate by zeroing the point and returns
+ *                   "x != 0", so a new point whose own x is exactly 0 is dropped whether or not it has a neighbour; that artefact is
+ *                   reproduced (keep = 0 for qx == 0, also with n_ref == 0).
+ *   SVO_DEDUP_DISC  the C++ side: i is a duplicate when sqrt((double)dx * dx + (double)dy * dy) < radius, dx and dy the FLOAT
+ *                   differences ref - new (Point2f::operator-), the sum of the two double products formed without contraction, the
+ *                   double square root compared with <.  Squares are not compared: sqrt(s) < r and s < r * r differ when s is one
+ *                   ulp below r * r.
+ * ref_idx is the reference's `mask`: only the n_idx listed reference points take part, in any order, repeats allowed; an entry
+ * outside [0, n_ref) is skipped and nothing is read through it.  ref_idx == NULL (n_idx must then be 0) means all n_ref points; a
+ * non-null ref_idx with n_idx == 0 means none.  A NaN coordinate makes every comparison false: such a new point is kept, such a
+ * reference point drops nobody.  n_keep (optional): the number of ones, a host or a device int following `mem`.  n_new == 0 and
+ * n_ref == 0 are legal.  SVO_ERR_ARG, with nothing written: null ctx, a negative count, a radius that is negative or NaN, an unknown
+ * mode or mem, n_idx != 0 with a null ref_idx, a null array whose count is not 0, a count above 2^28.
+ *
+ * svo_replenish: the loop body of src/ROSslam.py:262-271 without a host round trip.  The n_new new points are tested against
+ * ref_xy[0 .. n_ref) as above; each survivor's 3-D point is moved with Rt (3 x 4 row-major HOST doubles; the arithmetic of
+ * svo_transform_points: double products of the float input in the order x, y, z, t, rounded to float at the store) and kept when the z
+ * of the STORED float is > 0; the kept points are appended in input order to ref_xy (2 floats a row) and ref_xyz (3 floats a row)
+ * from row n_ref on.  Rows [0, n_ref) and rows past the new count are left as they were.  n_out = the new size, n_dup = points dropped
+ * as duplicates, n_behind = points dropped for z <= 0 (a NaN z included): optional, host or device ints following `mem`;
+ * n_dup + n_behind + (n_out - n_ref) == n_new.  cap = rows ref_xy / ref_xyz can hold; cap < n_ref + n_new is refused with
+ * SVO_ERR_CAPACITY before anything is launched (the worst case is checked, so the device never overflows).  The result is, bit for
+ * bit, svo_dedup_points -> svo_compact -> svo_transform_points -> a host z > 0 mask -> svo_compact -> concatenation.  In device
+ * memory nothing waits for the device; the new arrays must not overlap the reference arrays.  The prototype keeps float64 points
+ * (cv2.triangulatePoints on double input); these are float, as on the C++ path.                                                    */
+#define SVO_DEDUP_BOX  0 /* src/ROSslam.py:156-169 */
+#define SVO_DEDUP_DISC 1 /* include/monoUtils.h:195-213 */
+int svo_dedup_points(svo_ctx *ctx, const float *ref_xy, int n_ref, const int *ref_idx, int n_idx, const float *new_xy,
+                     int n_new, double radius, int mode, uint8_t *keep, int *n_keep, int mem);
+int svo_replenish(svo_ctx *ctx, float *ref_xy, float *ref_xyz, int n_ref, int cap, const float *new_xy, const float *new_xyz,
+                  int n_new, double radius, int mode, const double *Rt, int *n_out, int *n_dup, int *n_behind, int mem);
+
 /* ---- map clean-up: visualSLAM::SORcloud(ref3d, colorMap), src/rosFuncs.cpp:9-39 ------------- */
 /* Drops points with -z > z_limit (500 upstream, :12; <= 0 disables), then the statistical
  * outlier removal PCL applies at :19-23 (mean_k 200, stddev_mul 0.01): mean distance to the

@@ -89,6 +89,14 @@ class visualOdometry {
         ftrPts = new2d;
     }
 
+    // src/bundleAdjust.cpp:359, the copy of include/monoUtils.h:195-213: the indices of newref2dFeatures with no listed base point
+    // within `radius`.  A negative radius keeps everything upstream (no norm is below it); it is passed on as 0, which does too.
+    std::vector<int> removeDuplicates(std::vector<Point2f> &baseref2dFeatures, std::vector<Point2f> &newref2dFeatures,
+                                      std::vector<int> &mask, int radius = 10)
+    {
+        return remove_duplicates(ctx_, baseref2dFeatures, newref2dFeatures, mask, radius < 0 ? 0 : radius);
+    }
+
   private:
     svo_ctx *ctx_;
 };

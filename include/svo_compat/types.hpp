@@ -314,6 +314,25 @@ inline void ratio_match_points(svo_ctx *ctx, int norm, const void *desc1, const 
     pt2.resize((size_t)cnt);
 }
 
+// removeDuplicates (include/monoUtils.h:195-213), the body both classes carry: the indices of `fresh`, ascending, that have no point
+// of `base` listed in `mask` within `radius` (norm(p1 - p2) < radius).  The list goes through as it is, repeats and order included;
+// an EMPTY list means no reference point and everything is kept, as upstream's empty loop does -- so the call never gets a null
+// list, which would mean every point of `base`.
+inline std::vector<int> remove_duplicates(svo_ctx *ctx, const std::vector<Point2f> &base, const std::vector<Point2f> &fresh,
+                                          const std::vector<int> &mask, int radius)
+{
+    const int none = 0;
+    std::vector<uint8_t> keep(fresh.size());
+    check(svo_dedup_points(ctx, reinterpret_cast<const float *>(base.data()), (int)base.size(), mask.empty() ? &none : mask.data(),
+                           (int)mask.size(), reinterpret_cast<const float *>(fresh.data()), (int)fresh.size(), (double)radius,
+                           SVO_DEDUP_DISC, keep.data(), nullptr, SVO_MEM_HOST));
+    std::vector<int> res;
+    for (size_t i = 0; i < keep.size(); i++)
+        if (keep[i])
+            res.push_back((int)i);
+    return res;
+}
+
 // one context per device, shared by the adaptors of a process
 inline svo_ctx *shared_context(int device = 0)
 {

@@ -146,6 +146,15 @@ class visualSLAM {
         return out;
     }
 
+    // ---- include/monoUtils.h:195-213 (declared at include/visualSLAM.h:162) ----
+    // The indices of newref2dFeatures, ascending, with no base point listed in `mask` within `radius`: svo_dedup_points in DISC mode.
+    // A negative radius keeps everything upstream (no norm is below it); it is passed on as 0, which does too.
+    std::vector<int> removeDuplicates(std::vector<Point2f> &baseref2dFeatures, std::vector<Point2f> &newref2dFeatures,
+                                      std::vector<int> &mask, int radius = 10)
+    {
+        return remove_duplicates(ctx_, baseref2dFeatures, newref2dFeatures, mask, radius < 0 ? 0 : radius);
+    }
+
     // ---- src/tracking.cpp:14-28 ----
     void denseLKtracking(const Mat &refImg, const Mat &curImg, std::vector<Point2f> &refPts,
                          std::vector<Point2f> &trackPts)

@@ -287,6 +287,82 @@ def get_colors(self, pyr, xy):
     return out
 
 
+# ---- duplicate-aware replenishment: removeDuplicate / the top-up of trackSequence (src/ROSslam.py:156-169, 262-271) ----
+DEDUP_BOX, DEDUP_DISC = 0, 1
+
+
+@_ctx_method
+def dedup_points(self, ref_xy, new_xy, radius, mode=DEDUP_BOX, ref_idx=None, wait=True):
+    """``svo_dedup_points``: keep [n_new] uint8, 1 where a new point has no reference point near it (BOX: the prototype's strict
+    box with its x == 0 artefact; DISC: the C++ side's norm(ref - new) < radius).  ref_idx: the reference points that take part
+    (any order, repeats allowed, entries outside the array are skipped; an empty list means none), None for all.  numpy arrays, or
+    device tensors, which give a device tensor back (wait=False: without waiting for the context's stream; the caller orders
+    its reads after it)."""
+    if _is_device(new_xy):
+        import torch
+
+        ref = ref_xy.to(torch.float32).reshape(-1, 2).contiguous()
+        new = new_xy.to(torch.float32).reshape(-1, 2).contiguous()
+        idx = None if ref_idx is None else torch.as_tensor(ref_idx, dtype=torch.int32, device=new.device).reshape(-1).contiguous()
+        keep = torch.zeros(max(len(new), 1), dtype=torch.uint8, device=new.device)
+        dummy = torch.zeros(1, dtype=torch.int32, device=new.device)      # an empty list is still a list: a non-null pointer
+        torch.cuda.synchronize(new.device)
+        _check(self.lib.svo_dedup_points(self._h, _ptr(ref), len(ref), _ptr(dummy if idx is not None and len(idx) == 0 else idx),
+                                         0 if idx is None else len(idx), _ptr(new), len(new), C.c_double(radius), int(mode),
+                                         _ptr(keep), None, MEM_DEVICE))
+        if wait:
+            _check(self.lib.svo_ctx_sync(self._h))
+        return keep[:len(new)]
+    ref = np.ascontiguousarray(ref_xy, np.float32).reshape(-1, 2)
+    new = np.ascontiguousarray(new_xy, np.float32).reshape(-1, 2)
+    idx = None if ref_idx is None else np.ascontiguousarray(ref_idx, np.int32).reshape(-1)
+    keep = np.zeros(len(new), np.uint8)
+    cnt = C.c_int()
+    p_idx = None if idx is None else (C.c_int * max(len(idx), 1))(*idx.tolist())    # never null, also when the list is empty
+    _check(self.lib.svo_dedup_points(self._h, _ptr(ref), len(ref), p_idx, 0 if idx is None else len(idx), _ptr(new), len(new),
+                                     C.c_double(radius), int(mode), _ptr(keep), C.byref(cnt), MEM_HOST))
+    assert cnt.value == int(keep.sum())
+    return keep
+
+
+@_ctx_method
+def replenish(self, ref_xy, ref_xyz, new_xy, new_xyz, radius, Rt, mode=DEDUP_BOX, n_ref=None, counts=None, wait=True):
+    """``svo_replenish``: the new points that duplicate no held point, moved with ``Rt`` (3 x 4) and in front of the camera, appended
+    to the held set.  Host form (numpy arrays): -> (xy [n_out, 2], xyz [n_out, 3], n_dup, n_behind), new arrays.  Device form
+    (tensors): ref_xy / ref_xyz are [cap, 2] / [cap, 3] tensors whose first ``n_ref`` rows are held; the rows behind them are
+    written in place, ``counts`` (optional int32 tensor of 3: n_out, n_dup, n_behind) is filled on the device; wait=False: the call returns
+    without waiting for the context's stream, as the C entry point does."""
+    Rt = np.ascontiguousarray(np.asarray(Rt, np.float64).reshape(3, 4))
+    if _is_device(ref_xy):
+        import torch
+
+        assert ref_xy.dtype == torch.float32 and ref_xyz.dtype == torch.float32 and ref_xy.is_contiguous() and ref_xyz.is_contiguous()
+        assert n_ref is not None and ref_xy.shape[0] == ref_xyz.shape[0]
+        new = new_xy.to(torch.float32).reshape(-1, 2).contiguous()
+        new3 = new_xyz.to(torch.float32).reshape(-1, 3).contiguous()
+        assert len(new) == len(new3)
+        base = counts.data_ptr() if counts is not None else 0
+        torch.cuda.synchronize(new.device)
+        _check(self.lib.svo_replenish(self._h, _ptr(ref_xy), _ptr(ref_xyz), int(n_ref), int(ref_xy.shape[0]), _ptr(new), _ptr(new3),
+                                      len(new), C.c_double(radius), int(mode), _ptr(Rt), C.c_void_p(base),
+                                      C.c_void_p(base + 4 if base else 0), C.c_void_p(base + 8 if base else 0), MEM_DEVICE))
+        if wait:
+            _check(self.lib.svo_ctx_sync(self._h))
+        return ref_xy, ref_xyz
+    ref = np.ascontiguousarray(ref_xy, np.float32).reshape(-1, 2)
+    ref3 = np.ascontiguousarray(ref_xyz, np.float32).reshape(-1, 3)
+    new = np.ascontiguousarray(new_xy, np.float32).reshape(-1, 2)
+    new3 = np.ascontiguousarray(new_xyz, np.float32).reshape(-1, 3)
+    assert len(ref) == len(ref3) and len(new) == len(new3)
+    n, cap = len(ref), len(ref) + len(new)
+    xy, xyz = np.zeros((max(cap, 1), 2), np.float32), np.zeros((max(cap, 1), 3), np.float32)
+    xy[:n], xyz[:n] = ref, ref3
+    n_out, n_dup, n_behind = C.c_int(), C.c_int(), C.c_int()
+    _check(self.lib.svo_replenish(self._h, _ptr(xy), _ptr(xyz), n, cap, _ptr(new), _ptr(new3), len(new), C.c_double(radius), int(mode),
+                                  _ptr(Rt), C.byref(n_out), C.byref(n_dup), C.byref(n_behind), MEM_HOST))
+    return xy[:n_out.value].copy(), xyz[:n_out.value].copy(), n_dup.value, n_behind.value
+
+
 @_ctx_method
 def anms(self, xy, response, num_to_keep):
     xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
