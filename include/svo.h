@@ -973,6 +973,44 @@ int svo_pg_get_edge_information(const svo_posegraph *pg, int e, double *info21);
  * any other count is SVO_ERR_ARG with the line number.  svo_pg_write_g2o writes stored information as %.17g and, for an
  * edge that stores none, the integers 1 / 0 of the identity.                                                         */
 int svo_pg_read_g2o_info(svo_posegraph *pg, const char *path);
+/* ---- robust kernels on edges, and pruning ------------------------------------------------------
+ * An edge that carries a kernel enters a Gauss-Newton iteration as w Om instead of Om, in H and in b alike, with
+ * w = rho'(c) at c = chi2 = e^T Om e of the edge at that iteration's estimates: iteratively re-weighted least squares, g2o's
+ * robustInformation without the second-order term (commented out upstream).  The kinds and their weights are g2o's
+ * robust_kernel_impl.h (src/bundleAdjust.cpp:19 includes it) and Open3D's line process -- FROM MEMORY, VERIFY:
+ *   HUBER(d):          c <= d^2: rho = c, w = 1;  else rho = 2 d sqrt(c) - d^2, w = d / sqrt(c)
+ *   CAUCHY(d):         rho = d^2 log(1 + c / d^2), w = 1 / (1 + c / d^2)
+ *   DCS(phi):          s = 2 phi / (phi + c);  s >= 1: rho = c, w = 1;  else rho = s^2 c, w = s^2 -- g2o's weight here is NOT the
+ *                      derivative of its rho; it is reproduced as it stands
+ *   GEMAN_MCCLURE(mu): rho = mu c / (mu + c), w = l = (mu / (mu + c))^2 -- the line-process weight of Open3D's global
+ *                      optimisation for an `uncertain` edge (src/ROSslam.py:57 adds every closure as one)
+ * chi2[] of svo_pg_optimize stays the unweighted sum of e^T Om e (g2o's activeChi2).  A graph that stores no kernel is
+ * optimised by the same kernels, to the same bits, as before these calls existed; so is one whose weights are all 1.   */
+#define SVO_PG_ROBUST_NONE          0
+#define SVO_PG_ROBUST_HUBER         1
+#define SVO_PG_ROBUST_CAUCHY        2
+#define SVO_PG_ROBUST_DCS           3
+#define SVO_PG_ROBUST_GEMAN_MCCLURE 4
+/* SVO_ERR_ARG, the graph unchanged: e outside the edges, an unknown kind, a delta that is not finite and positive (NONE takes
+ * any).  The getter gives NONE and 0 for an edge that carries none; either output may be NULL.                       */
+int svo_pg_set_robust_kernel(svo_posegraph *pg, int e, int kind, double delta);
+int svo_pg_get_robust_kernel(const svo_posegraph *pg, int e, int *kind, double *delta);
+/* The kernel of every edge svo_pg_add_loop_closure, svo_pg_add_loop_closure_measured and svo_pg_augment_nodes add AFTER this
+ * call (NONE when the graph is created, and again after svo_pg_initialize and the .g2o readers).  Odometry edges never get one. */
+int svo_pg_set_loop_closure_kernel(svo_posegraph *pg, int kind, double delta);
+/* Per edge at the current estimates: chi2 = e^T Om e, the weight w and rho of its kernel (1 and chi2 without one); ne HOST
+ * doubles each, any of the three may be NULL.  No blocks are formed; the call waits once.                             */
+int svo_pg_edge_residuals(svo_posegraph *pg, double *chi2, double *weight, double *rho);
+/* The weights the LAST linearisation of the last svo_pg_optimize stored in its per-edge records (ne HOST doubles), i.e. at
+ * the estimates that call returned.  SVO_ERR_STATE when that solve used no kernel or the graph has changed since.      */
+int svo_pg_linearization_weights(svo_posegraph *pg, double *weight);
+/* Evaluates w at the current estimates and removes every edge that carries a kernel, does not join consecutive vertices
+ * and has w < threshold (strict).  The other edges keep their order; measurements, information matrices and kernels move
+ * with them.  removed (cap HOST ints, may be NULL with cap 0): the former indices, ascending; *n_removed (optional): their
+ * count, also when the call refuses.  SVO_ERR_CAPACITY: cap is below the count; SVO_ERR_STATE: a vertex would no longer be
+ * reachable from vertex 0; SVO_ERR_ARG: a NaN threshold -- nothing is removed in any of these.  After a removal the next
+ * svo_pg_optimize uploads the graph and builds the elimination structure again.                                        */
+int svo_pg_prune_edges(svo_posegraph *pg, double threshold, int *removed, int cap, int *n_removed);
 
 /* ---- the measurement of a loop closure: getLCMeasurement, dump.cpp:331-348 -------------------- */
 typedef struct svo_closure_params {

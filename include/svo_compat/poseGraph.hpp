@@ -91,6 +91,19 @@ class globalPoseGraph {
             out.push_back(pose7_to_iso(&p[7 * i]));
         return out;
     }
+    // Not in the reference, off by default: the robust kernel (SVO_PG_ROBUST_*, include/svo.h) of every loop closure that
+    // addLoopClosure adds from now on; SVO_PG_ROBUST_NONE brings the reference's behaviour back.
+    void setLoopClosureKernel(int kind, double delta) { check(svo_pg_set_loop_closure_kernel(pg_, kind, delta)); }
+    // Not in the reference: removes the closures whose robust weight at the current estimates is below `threshold`
+    // (svo_pg_prune_edges) and returns their former edge indices, ascending.
+    std::vector<int> pruneLoopClosures(double threshold)
+    {
+        std::vector<int> removed((size_t)svo_pg_num_edges(pg_) + 1);
+        int n = 0;
+        check(svo_pg_prune_edges(pg_, threshold, removed.data(), (int)removed.size(), &n));
+        removed.resize((size_t)n);
+        return removed;
+    }
     // :140-179
     void saveStructure() { check(svo_pg_write_g2o(pg_, outFileName.c_str())); }
     int numVertices() const { return svo_pg_num_vertices(pg_); }

@@ -28,6 +28,7 @@ SVO_ERR_TRACKING_LOST = -5
 SVO_ERR_STATE = -6
 MEM_HOST, MEM_DEVICE = 0, 1
 K_PYRAMID, K_LK, K_FRANSAC, K_TRIANGULATE, K_PNP, K_POSEGRAPH, K_ANMS, K_BRIEF_INTEGRAL, K_BRIEF_DESCRIBE = range(9)
+PG_ROBUST_NONE, PG_ROBUST_HUBER, PG_ROBUST_CAUCHY, PG_ROBUST_DCS, PG_ROBUST_GEMAN_MCCLURE = range(5)
 
 
 class SvoError(RuntimeError):
@@ -2046,6 +2047,39 @@ class PoseGraph:
         out = np.zeros(21)
         _check(self.ctx.lib.svo_pg_get_edge_information(self._h, int(e), _ptr(out)))
         return out
+
+    def set_robust_kernel(self, e: int, kind: int, delta: float = 0.0):
+        """``svo_pg_set_robust_kernel``: kind = PG_ROBUST_NONE / HUBER / CAUCHY / DCS / GEMAN_MCCLURE and its parameter."""
+        _check(self.ctx.lib.svo_pg_set_robust_kernel(self._h, int(e), int(kind), C.c_double(delta)))
+
+    def robust_kernel(self, e: int):
+        """-> (kind, delta) of edge e; (PG_ROBUST_NONE, 0.0) when it carries none."""
+        kind, delta = C.c_int(), C.c_double()
+        _check(self.ctx.lib.svo_pg_get_robust_kernel(self._h, int(e), C.byref(kind), C.byref(delta)))
+        return kind.value, delta.value
+
+    def set_loop_closure_kernel(self, kind: int, delta: float = 0.0):
+        """``svo_pg_set_loop_closure_kernel``: the kernel of every loop closure added from now on."""
+        _check(self.ctx.lib.svo_pg_set_loop_closure_kernel(self._h, int(kind), C.c_double(delta)))
+
+    def edge_residuals(self):
+        """``svo_pg_edge_residuals`` -> (chi2, weight, rho), one double per edge, at the current estimates."""
+        out = np.zeros((3, self.num_edges))
+        _check(self.ctx.lib.svo_pg_edge_residuals(self._h, _ptr(out[0]), _ptr(out[1]), _ptr(out[2])))
+        return out[0], out[1], out[2]
+
+    def linearization_weights(self) -> np.ndarray:
+        """``svo_pg_linearization_weights``: the weights the last optimize's final linearisation stored."""
+        out = np.zeros(self.num_edges)
+        _check(self.ctx.lib.svo_pg_linearization_weights(self._h, _ptr(out)))
+        return out
+
+    def prune_edges(self, threshold: float = 0.25, cap: int | None = None) -> np.ndarray:
+        """``svo_pg_prune_edges`` -> the former indices of the removed edges, ascending (cap: slots offered, default every edge)."""
+        cap = self.num_edges if cap is None else int(cap)
+        removed, n = np.zeros(max(cap, 1), np.int32), C.c_int()
+        _check(self.ctx.lib.svo_pg_prune_edges(self._h, C.c_double(threshold), _ptr(removed), cap, C.byref(n)))
+        return removed[:n.value].copy()
 
     def augment_nodes(self, poses7, closure_from=None):
         """``svo_pg_augment_nodes``: poses7 [n, 7]; closure_from [n] int32 (-1: none): the closure edge staged before node i."""

@@ -25,6 +25,7 @@
 #include <utility>
 #include <vector>
 
+#include "pg_prune_plan.hip.h"
 #include "svo_internal.h"
 #include "wave_ops.hip.h"
 
@@ -92,7 +93,39 @@ __device__ inline void q_to_R(const double *q, double *R)
 }
 
 // per-edge outputs: 3 blocks + 2 gradients + chi2, one record of EO_FIELDS doubles per edge
-enum { EO_HII = 0, EO_HIJ = 36, EO_HJJ = 72, EO_BI = 108, EO_BJ = 114, EO_CHI2 = 120, EO_FIELDS = 122 };
+// (EO_W: the robust weight of the edge, written by the robust instantiations only)
+enum { EO_HII = 0, EO_HIJ = 36, EO_HJJ = 72, EO_BI = 108, EO_BJ = 114, EO_CHI2 = 120, EO_W = 121, EO_FIELDS = 122 };
+
+// The robust kernels at c = chi2 of an edge: the weight w = rho'(c) that scales the edge's information, and rho itself.  g2o's
+// robust_kernel_impl.h and Open3D's line process, from memory -- verify (include/svo.h has the table).  DCS: g2o's weight s^2 is not
+// the derivative of its rho = s^2 c (s depends on c); it is reproduced as it stands.  delta is finite and positive (checked on entry).
+__device__ inline double pg_robust_weight(int kind, double delta, double c, double *rho)
+{
+    double w = 1., r = c;
+    if (kind == SVO_PG_ROBUST_HUBER) {
+        if (c > delta * delta) {
+            const double sq = sqrt(c);
+            w = delta / sq;
+            r = 2. * delta * sq - delta * delta;
+        }
+    } else if (kind == SVO_PG_ROBUST_CAUCHY) {
+        const double d2 = delta * delta, aux = 1. + c / d2;
+        w = 1. / aux;
+        r = d2 * svo_log(aux);
+    } else if (kind == SVO_PG_ROBUST_DCS) {
+        const double sc = 2. * delta / (delta + c);
+        if (sc < 1.) {
+            w = sc * sc;
+            r = w * c;
+        }
+    } else if (kind == SVO_PG_ROBUST_GEMAN_MCCLURE) {
+        const double l = delta / (delta + c);
+        w = l * l;
+        r = delta * c / (delta + c);
+    }
+    *rho = r;
+    return w;
+}
 
 // Index of entry (i, j), i <= j, of a symmetric 6 x 6 matrix stored as its upper triangle, row-major (g2o's order)
 __host__ __device__ constexpr int pg_tri(int i, int j)
@@ -105,12 +138,17 @@ __host__ __device__ constexpr int pg_tri(int i, int j)
 // WEIGHTED = true: a second instantiation, launched only for a graph with at least one stored information matrix:
 // `info` holds 21 doubles per edge (pg_tri), chi2 = e^T (Om e), b = J^T (Om e), H = J^T (Om J).  Om J is never held as a
 // whole: per output column q the six values w = Om J[:, q] are formed and dotted with the columns of Ji and Jj.
-template <bool WEIGHTED>
+// ROBUST = true: two more instantiations, launched only for a graph that stores at least one robust kernel: (rkind, rdelta) per
+// edge, w = rho'(chi) scales the FINISHED blocks and gradients as they are stored (w == 1: times 1.0, the other instantiation's
+// bits; a diagonal block's two mirrored entries are the same product) and goes to EO_W.  chi2 stays the unweighted e^T Om e.
+template <bool WEIGHTED, bool ROBUST>
 __global__ __launch_bounds__(128) void pg_linearize_kernel(const double *__restrict__ pose, const int *__restrict__ efrom,
                                                            const int *__restrict__ eto, const double *__restrict__ meas,
                                                            int ne, double *__restrict__ out, double *__restrict__ part,
                                                            unsigned *__restrict__ ticket, double *__restrict__ chi2_out,
-                                                           const double *__restrict__ info)
+                                                           const double *__restrict__ info,
+                                                           const int *__restrict__ rkind,
+                                                           const double *__restrict__ rdelta)
 {
     __shared__ double s_chi[128];
     __shared__ bool s_last;
@@ -232,6 +270,12 @@ __global__ __launch_bounds__(128) void pg_linearize_kernel(const double *__restr
     if (live) {
         double *o = out + (size_t)e * EO_FIELDS;
         o[EO_CHI2] = chi;
+        double rw = 1.;  // (read by the robust instantiations only)
+        if constexpr (ROBUST) {
+            double rho;
+            rw = pg_robust_weight(rkind[e], rdelta[e], chi, &rho);
+            o[EO_W] = rw;
+        }
         if constexpr (WEIGHTED) {
 #pragma unroll
             for (int p = 0; p < 6; p++) {
@@ -241,8 +285,8 @@ __global__ __launch_bounds__(128) void pg_linearize_kernel(const double *__restr
                     si += Ji[6 * k + p] * we[k];
                     sj += Jj[6 * k + p] * we[k];
                 }
-                o[EO_BI + p] = si;
-                o[EO_BJ + p] = sj;
+                o[EO_BI + p] = ROBUST ? si * rw : si;
+                o[EO_BJ + p] = ROBUST ? sj * rw : sj;
             }
 #pragma unroll
             for (int q = 0; q < 6; q++) {
@@ -267,14 +311,14 @@ __global__ __launch_bounds__(128) void pg_linearize_kernel(const double *__restr
                         b += Ji[6 * k + p] * wj[k];
                         c += Jj[6 * k + p] * wj[k];
                     }
-                    o[EO_HIJ + 6 * p + q] = b;
+                    o[EO_HIJ + 6 * p + q] = ROBUST ? b * rw : b;
                     // the diagonal blocks are symmetric: the upper triangle is computed, the lower mirrors it bit for bit
                     if (p <= q) {
-                        o[EO_HII + 6 * p + q] = a;
-                        o[EO_HJJ + 6 * p + q] = c;
+                        o[EO_HII + 6 * p + q] = ROBUST ? a * rw : a;
+                        o[EO_HJJ + 6 * p + q] = ROBUST ? c * rw : c;
                         if (p < q) {
-                            o[EO_HII + 6 * q + p] = a;
-                            o[EO_HJJ + 6 * q + p] = c;
+                            o[EO_HII + 6 * q + p] = ROBUST ? a * rw : a;
+                            o[EO_HJJ + 6 * q + p] = ROBUST ? c * rw : c;
                         }
                     }
                 }
@@ -288,8 +332,8 @@ __global__ __launch_bounds__(128) void pg_linearize_kernel(const double *__restr
                 si += Ji[6 * k + p] * err[k];
                 sj += Jj[6 * k + p] * err[k];
             }
-            o[EO_BI + p] = si;
-            o[EO_BJ + p] = sj;
+            o[EO_BI + p] = ROBUST ? si * rw : si;
+            o[EO_BJ + p] = ROBUST ? sj * rw : sj;
 #pragma unroll
             for (int q = 0; q < 6; q++) {
                 double a = 0, b = 0, c = 0;
@@ -299,12 +343,59 @@ __global__ __launch_bounds__(128) void pg_linearize_kernel(const double *__restr
                     b += Ji[6 * k + p] * Jj[6 * k + q];
                     c += Jj[6 * k + p] * Jj[6 * k + q];
                 }
-                o[EO_HII + 6 * p + q] = a;
-                o[EO_HIJ + 6 * p + q] = b;
-                o[EO_HJJ + 6 * p + q] = c;
+                o[EO_HII + 6 * p + q] = ROBUST ? a * rw : a;
+                o[EO_HIJ + 6 * p + q] = ROBUST ? b * rw : b;
+                o[EO_HJJ + 6 * p + q] = ROBUST ? c * rw : c;
             }
         }
     }
+}
+
+// chi2, w and rho of every edge at the current estimates, no blocks: one thread per edge, the error and chi2 by the operations of
+// pg_linearize_kernel in its order (so chi2 and w are that kernel's bits).  For svo_pg_edge_residuals and svo_pg_prune_edges.
+// rkind == nullptr: no edge carries a kernel.  res: chi2 [ne] | w [ne] | rho [ne].
+template <bool WEIGHTED>
+__global__ __launch_bounds__(128) void pg_edge_eval_kernel(const double *__restrict__ pose, const int *__restrict__ efrom,
+                                                           const int *__restrict__ eto, const double *__restrict__ meas,
+                                                           int ne, const double *__restrict__ info,
+                                                           const int *__restrict__ rkind, const double *__restrict__ rdelta,
+                                                           double *__restrict__ res)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= ne)
+        return;
+    const double *Xi = pose + 7 * efrom[e], *Xj = pose + 7 * eto[e], *Z = meas + 7 * e;
+    double A[7], Xi_inv[7], B[7], E[7];
+    se3_inv(Z, A);
+    se3_inv(Xi, Xi_inv);
+    se3_mul(Xi_inv, Xj, B);
+    se3_mul(A, B, E);
+    const double s = E[6] < 0 ? -1. : 1.;
+    const double err[6] = {E[0], E[1], E[2], s * E[3], s * E[4], s * E[5]};
+    double chi = 0;
+    if constexpr (WEIGHTED) {
+        double we[6];
+#pragma unroll
+        for (int r = 0; r < 6; r++) {
+            double acc = 0;
+#pragma unroll
+            for (int k = 0; k < 6; k++)
+                acc += info[21 * (size_t)e + pg_tri(r, k)] * err[k];
+            we[r] = acc;
+        }
+#pragma unroll
+        for (int k = 0; k < 6; k++)
+            chi += err[k] * we[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 6; k++)
+            chi += err[k] * err[k];
+    }
+    double rho = chi;
+    const double w = rkind ? pg_robust_weight(rkind[e], rdelta[e], chi, &rho) : 1.;
+    res[e] = chi;
+    res[(size_t)ne + e] = w;
+    res[2 * (size_t)ne + e] = rho;
 }
 
 // ---- the linear solve  H dx = -b --------------------------------------------------------------
@@ -1740,6 +1831,16 @@ struct svo_posegraph {
     std::vector<double> info;
     std::vector<char> has_info;
     int n_info = 0;
+    // Robust kernels, lazily like the information: EMPTY while no edge carries one (the two non-robust linearisations run); else a
+    // kind and its parameter per edge.  n_robust: edges whose kind is not NONE.  lc_kind / lc_delta: what a new closure gets.
+    std::vector<int> rkind;
+    std::vector<double> rdelta;
+    int n_robust = 0;
+    int lc_kind = SVO_PG_ROBUST_NONE;
+    double lc_delta = 0;
+    // the edges of the last solve when its final linearisation was a robust one and nothing has changed since (EO_W of d_eo
+    // holds the weights at the current estimates), else -1
+    int eo_w_ne = -1;
     int prev = -1;
     // What the device already holds.  The graph only grows between two solves (augmentNode /
     // addLoopClosure append), and after a solve the device poses ARE the host poses, so the next
@@ -1758,6 +1859,7 @@ struct svo_posegraph {
     size_t s_wc_blocks = 0;
     size_t o_seg_start = 0, o_seg_len = 0, o_sepidx = 0, o_lsep = 0, o_rsep = 0, o_rb_row = 0, o_rb_col = 0, o_rptr = 0,
            o_rsrc = 0, o_rowseg = 0, o_cptr = 0, o_clrow = 0, o_cedge = 0, o_ctr = 0, o_cwbase = 0, o_csep = 0, o_terms = 0;
+    DevBuf d_rkind, d_rdelta, d_eval;
     DevBuf d_pose, d_from, d_to, d_meas, d_info, d_eo, d_incptr, d_inc, d_struct, d_Dg, d_Cc, d_rneg, d_Y,
         d_Wl, d_Wr, d_Wc, d_R, d_Lo, d_Tinv, d_rR, d_xR, d_misc, d_dx, d_res;
     int refine = 0;  // iterative-refinement passes per Gauss-Newton iteration (svo_pg_set_refinement)
@@ -1832,6 +1934,116 @@ static void pg_append_info(svo_posegraph *g, const double *info21)
     pg_store_info(g, g->ne() - 1, info21);
 }
 
+static void pg_drop_robust(svo_posegraph *g)
+{
+    g->rkind.clear();
+    g->rdelta.clear();
+    g->n_robust = 0;
+}
+
+// Stores the (checked) kernel of edge e; NONE = none.  The edge must exist.
+static void pg_store_robust(svo_posegraph *g, int e, int kind, double delta)
+{
+    const bool none = kind == SVO_PG_ROBUST_NONE;
+    g->eo_w_ne = -1;
+    if (g->rkind.empty()) {
+        if (none)
+            return;
+        g->rkind.assign(g->ne(), SVO_PG_ROBUST_NONE);
+        g->rdelta.assign(g->ne(), 0.);
+    }
+    g->n_robust += (none ? 0 : 1) - (g->rkind[e] != SVO_PG_ROBUST_NONE ? 1 : 0);
+    g->rkind[e] = kind;
+    g->rdelta[e] = none ? 0. : delta;
+    if (g->n_robust == 0)
+        pg_drop_robust(g);  // no kernel left: back to the non-robust linearisations
+}
+
+// a new edge was appended to efrom / eto / meas: the kernel vectors, where they exist, follow
+static void pg_append_robust(svo_posegraph *g, int kind, double delta)
+{
+    if (!g->rkind.empty()) {
+        g->rkind.push_back(SVO_PG_ROBUST_NONE);
+        g->rdelta.push_back(0.);
+    }
+    pg_store_robust(g, g->ne() - 1, kind, delta);
+}
+
+// The graph itself on the device: grown buffers keep what the device already holds, only the tail is uploaded (poses, edges,
+// measurements; with `weighted` the information; the robust kernels, where the graph stores any, whole: 12 bytes an edge).
+// Queued on `st` from vectors that live in *g, so the copies need no sync.  The CALLER sets dev_nv / dev_ne / dev_ninfo to 0 until
+// its work on the device has succeeded, and to nv / ne / (weighted ? ne : 0) then.
+static int pg_upload_graph(svo_posegraph *g, const bool weighted, hipStream_t st)
+{
+    const int nv = g->nv(), ne = g->ne();
+    int rc;
+    if (g->dev_nv > nv || g->dev_ne > ne)
+        g->dev_nv = g->dev_ne = 0;
+    if ((rc = ensure_keep(g->d_pose, (size_t)nv * 56, (size_t)g->dev_nv * 56, st)) ||
+        (rc = ensure_keep(g->d_from, (size_t)ne * 4, (size_t)g->dev_ne * 4, st)) ||
+        (rc = ensure_keep(g->d_to, (size_t)ne * 4, (size_t)g->dev_ne * 4, st)) ||
+        (rc = ensure_keep(g->d_meas, (size_t)ne * 56, (size_t)g->dev_ne * 56, st)))
+        return rc;
+    if (!weighted || g->dev_ninfo > ne || g->dev_ninfo > g->dev_ne)
+        g->dev_ninfo = 0;
+    if (weighted && (rc = ensure_keep(g->d_info, (size_t)ne * 168, (size_t)g->dev_ninfo * 168, st)))
+        return rc;
+    const bool robust = g->n_robust > 0;
+    if (robust && ((rc = g->d_rkind.ensure((size_t)ne * 4)) || (rc = g->d_rdelta.ensure((size_t)ne * 8))))
+        return rc;
+    if (nv > g->dev_nv)
+        SVO_HIP(hipMemcpyAsync(g->d_pose.as<double>() + 7 * (size_t)g->dev_nv, g->pose.data() + 7 * (size_t)g->dev_nv,
+                               (size_t)(nv - g->dev_nv) * 56, hipMemcpyHostToDevice, st));
+    if (ne > g->dev_ne) {
+        const size_t e0 = (size_t)g->dev_ne, cnt = (size_t)(ne - g->dev_ne);
+        SVO_HIP(hipMemcpyAsync(g->d_from.as<int>() + e0, g->efrom.data() + e0, cnt * 4, hipMemcpyHostToDevice, st));
+        SVO_HIP(hipMemcpyAsync(g->d_to.as<int>() + e0, g->eto.data() + e0, cnt * 4, hipMemcpyHostToDevice, st));
+        SVO_HIP(hipMemcpyAsync(g->d_meas.as<double>() + 7 * e0, g->meas.data() + 7 * e0, cnt * 56, hipMemcpyHostToDevice, st));
+    }
+    if (weighted && ne > g->dev_ninfo)
+        SVO_HIP(hipMemcpyAsync(g->d_info.as<double>() + 21 * (size_t)g->dev_ninfo, g->info.data() + 21 * (size_t)g->dev_ninfo,
+                               (size_t)(ne - g->dev_ninfo) * 168, hipMemcpyHostToDevice, st));
+    if (robust) {
+        SVO_HIP(hipMemcpyAsync(g->d_rkind.p, g->rkind.data(), (size_t)ne * 4, hipMemcpyHostToDevice, st));
+        SVO_HIP(hipMemcpyAsync(g->d_rdelta.p, g->rdelta.data(), (size_t)ne * 8, hipMemcpyHostToDevice, st));
+    }
+    return SVO_OK;
+}
+
+// chi2 | w | rho of every edge at the current estimates -> res (3 ne doubles); one wait
+static int pg_edge_eval(svo_posegraph *g, std::vector<double> &res)
+{
+    svo_ctx *ctx = g->ctx;
+    SVO_HIP(hipSetDevice(ctx->device));
+    const int nv = g->nv(), ne = g->ne();
+    res.assign(3 * (size_t)ne, 0.);
+    if (ne == 0)
+        return SVO_OK;
+    hipStream_t st = ctx->stream;
+    const bool weighted = g->n_info > 0, robust = g->n_robust > 0;
+    int rc;
+    if ((rc = pg_upload_graph(g, weighted, st)) || (rc = g->d_eval.ensure(3 * (size_t)ne * 8)))
+        return rc;
+    g->dev_nv = g->dev_ne = g->dev_ninfo = 0;  // until the wait below has succeeded the device copy is not to be trusted
+    const int *rk = robust ? g->d_rkind.as<int>() : nullptr;
+    const double *rd = robust ? g->d_rdelta.as<double>() : nullptr;
+    if (weighted)
+        hipLaunchKernelGGL(pg_edge_eval_kernel<true>, dim3((ne + 127) / 128), dim3(128), 0, st, g->d_pose.as<double>(),
+                           g->d_from.as<int>(), g->d_to.as<int>(), g->d_meas.as<double>(), ne, g->d_info.as<double>(), rk, rd,
+                           g->d_eval.as<double>());
+    else
+        hipLaunchKernelGGL(pg_edge_eval_kernel<false>, dim3((ne + 127) / 128), dim3(128), 0, st, g->d_pose.as<double>(),
+                           g->d_from.as<int>(), g->d_to.as<int>(), g->d_meas.as<double>(), ne, static_cast<const double *>(nullptr),
+                           rk, rd, g->d_eval.as<double>());
+    SVO_HIP(hipGetLastError());
+    SVO_HIP(hipMemcpyAsync(res.data(), g->d_eval.p, 3 * (size_t)ne * 8, hipMemcpyDeviceToHost, st));
+    SVO_HIP(hipStreamSynchronize(st));
+    g->dev_nv = nv;
+    g->dev_ne = ne;
+    g->dev_ninfo = weighted ? ne : 0;
+    return SVO_OK;
+}
+
 extern "C" {
 
 int svo_pg_create(svo_ctx *ctx, svo_posegraph **out)
@@ -1851,7 +2063,7 @@ int svo_pg_destroy(svo_posegraph *g)
         return SVO_OK;
     (void)hipSetDevice(g->ctx->device);
     (void)hipStreamSynchronize(g->ctx->stream);
-    DevBuf *bufs[] = {&g->d_pose, &g->d_from, &g->d_to, &g->d_meas, &g->d_info, &g->d_eo,  &g->d_incptr, &g->d_inc, &g->d_struct,
+    DevBuf *bufs[] = {&g->d_rkind, &g->d_rdelta, &g->d_eval, &g->d_pose, &g->d_from, &g->d_to, &g->d_meas, &g->d_info, &g->d_eo,  &g->d_incptr, &g->d_inc, &g->d_struct,
                       &g->d_Dg,   &g->d_Cc,   &g->d_rneg, &g->d_Y,     &g->d_Wl,
                       &g->d_Wr,   &g->d_Wc,   &g->d_R,    &g->d_Lo, &g->d_Tinv, &g->d_rR,  &g->d_xR,  &g->d_misc, &g->d_dx, &g->d_res};
     for (DevBuf *b : bufs)
@@ -1868,6 +2080,10 @@ int svo_pg_initialize(svo_posegraph *g)
     g->eto.clear();
     g->meas.clear();
     pg_drop_info(g);
+    pg_drop_robust(g);
+    g->lc_kind = SVO_PG_ROBUST_NONE;
+    g->lc_delta = 0;
+    g->eo_w_ne = -1;
     g->prev = 0;
     g->dev_nv = g->dev_ne = 0;
     g->built_nv = g->built_ne = -1;
@@ -1891,6 +2107,7 @@ int svo_pg_augment_node(svo_posegraph *g, const double *pose7)
     g->eto.push_back(cur);
     g->meas.insert(g->meas.end(), z, z + 7);
     pg_append_info(g, nullptr);
+    pg_append_robust(g, SVO_PG_ROBUST_NONE, 0.);  // an odometry edge never gets a kernel
     g->prev = cur;
     return SVO_OK;
 }
@@ -1903,6 +2120,7 @@ int svo_pg_add_loop_closure(svo_posegraph *g, int from_id)
     g->eto.push_back(from_id);
     g->meas.insert(g->meas.end(), id, id + 7);
     pg_append_info(g, nullptr);
+    pg_append_robust(g, g->lc_kind, g->lc_delta);
     return SVO_OK;
 }
 
@@ -1933,6 +2151,7 @@ int svo_pg_add_loop_closure_measured(svo_posegraph *g, int from_id, const double
     g->eto.push_back(from_id);
     g->meas.insert(g->meas.end(), z, z + 7);
     pg_append_info(g, info21);
+    pg_append_robust(g, g->lc_kind, g->lc_delta);
     return SVO_OK;
 }
 
@@ -1943,6 +2162,7 @@ int svo_pg_set_edge_information(svo_posegraph *g, int e, const double *info21)
     if (info21 && (rc = pg_check_info(info21, "edge", e)))
         return rc;
     pg_store_info(g, e, info21);
+    g->eo_w_ne = -1;
     return SVO_OK;
 }
 
@@ -2268,20 +2488,10 @@ int svo_pg_optimize(svo_posegraph *g, int iters, double *chi2)
     const size_t o_rowseg = g->o_rowseg, o_cptr = g->o_cptr, o_terms = g->o_terms;
     hipStream_t st = ctx->stream;
     int rc;
-    // the graph itself: grown buffers keep what the device already holds, only the tail is uploaded
-    if (g->dev_nv > nv || g->dev_ne > ne)
-        g->dev_nv = g->dev_ne = 0;
-    if ((rc = ensure_keep(g->d_pose, (size_t)nv * 56, (size_t)g->dev_nv * 56, st)) ||
-        (rc = ensure_keep(g->d_from, (size_t)ne * 4, (size_t)g->dev_ne * 4, st)) ||
-        (rc = ensure_keep(g->d_to, (size_t)ne * 4, (size_t)g->dev_ne * 4, st)) ||
-        (rc = ensure_keep(g->d_meas, (size_t)ne * 56, (size_t)g->dev_ne * 56, st)))
-        return rc;
-    // the weighted linearisation runs only for a graph that stores at least one non-identity information matrix
-    const bool weighted = g->n_info > 0;
-    if (!weighted || g->dev_ninfo > ne || g->dev_ninfo > g->dev_ne)
-        g->dev_ninfo = 0;
-    if (weighted && (rc = ensure_keep(g->d_info, (size_t)ne * 168, (size_t)g->dev_ninfo * 168, st)))
-        return rc;
+    // the weighted linearisation runs only for a graph that stores at least one non-identity information matrix, the robust
+    // ones only for a graph that stores at least one kernel
+    const bool weighted = g->n_info > 0, robust = g->n_robust > 0;
+    g->eo_w_ne = -1;
     if ((rc = g->d_eo.ensure((size_t)ne * EO_FIELDS * 8)) || (rc = g->d_incptr.ensure((size_t)(nv + 1) * 4)) ||
         (rc = g->d_inc.ensure((size_t)2 * ne * 4)) || (rc = g->d_struct.ensure(g->h_struct.size() * 4 + 16)) ||
         (rc = g->d_Dg.ensure((size_t)nb * 288)) || (rc = g->d_Cc.ensure((size_t)nb * 288)) ||
@@ -2292,19 +2502,9 @@ int svo_pg_optimize(svo_posegraph *g, int iters, double *chi2)
         (rc = g->d_rR.ensure((size_t)ldr * 8 + 64)) || (rc = g->d_xR.ensure((size_t)ldr * 8 + 64)) ||
         (rc = g->d_misc.ensure(((size_t)iters + 6 + (ne + 127) / 128) * 8 + 64)))
         return rc;
-    // (g->pose / efrom / eto / meas and the structure vectors live in *g: the copies below need no sync)
-    if (nv > g->dev_nv)
-        SVO_HIP(hipMemcpyAsync(g->d_pose.as<double>() + 7 * (size_t)g->dev_nv, g->pose.data() + 7 * (size_t)g->dev_nv,
-                               (size_t)(nv - g->dev_nv) * 56, hipMemcpyHostToDevice, st));
-    if (ne > g->dev_ne) {
-        const size_t e0 = (size_t)g->dev_ne, cnt = (size_t)(ne - g->dev_ne);
-        SVO_HIP(hipMemcpyAsync(g->d_from.as<int>() + e0, g->efrom.data() + e0, cnt * 4, hipMemcpyHostToDevice, st));
-        SVO_HIP(hipMemcpyAsync(g->d_to.as<int>() + e0, g->eto.data() + e0, cnt * 4, hipMemcpyHostToDevice, st));
-        SVO_HIP(hipMemcpyAsync(g->d_meas.as<double>() + 7 * e0, g->meas.data() + 7 * e0, cnt * 56, hipMemcpyHostToDevice, st));
-    }
-    if (weighted && ne > g->dev_ninfo)
-        SVO_HIP(hipMemcpyAsync(g->d_info.as<double>() + 21 * (size_t)g->dev_ninfo, g->info.data() + 21 * (size_t)g->dev_ninfo,
-                               (size_t)(ne - g->dev_ninfo) * 168, hipMemcpyHostToDevice, st));
+    // (g->pose / efrom / eto / meas and the structure vectors live in *g: the copies need no sync)
+    if ((rc = pg_upload_graph(g, weighted, st)))
+        return rc;
     if (rebuild) {
         SVO_HIP(hipMemcpyAsync(g->d_incptr.p, g->h_incptr.data(), (size_t)(nv + 1) * 4, hipMemcpyHostToDevice, st));
         SVO_HIP(hipMemcpyAsync(g->d_inc.p, g->h_inc.data(), (size_t)2 * ne * 4, hipMemcpyHostToDevice, st));
@@ -2345,14 +2545,17 @@ int svo_pg_optimize(svo_posegraph *g, int iters, double *chi2)
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)seg_lds));
     ScopedKernelTime tm(ctx, SVO_K_POSEGRAPH);
     for (int it = 0; it <= iters; it++) {
-        if (weighted)
-            hipLaunchKernelGGL(pg_linearize_kernel<true>, dim3((ne + 127) / 128), dim3(128), 0, st, g->d_pose.as<double>(),
-                               g->d_from.as<int>(), g->d_to.as<int>(), g->d_meas.as<double>(), ne, eo, d_part, d_ticket,
-                               d_chi + it, g->d_info.as<double>());
+        auto linearize = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3((ne + 127) / 128), dim3(128), 0, st, g->d_pose.as<double>(), g->d_from.as<int>(),
+                               g->d_to.as<int>(), g->d_meas.as<double>(), ne, eo, d_part, d_ticket, d_chi + it,
+                               weighted ? g->d_info.as<double>() : static_cast<const double *>(nullptr),
+                               robust ? g->d_rkind.as<int>() : static_cast<const int *>(nullptr),
+                               robust ? g->d_rdelta.as<double>() : static_cast<const double *>(nullptr));
+        };
+        if (robust)
+            weighted ? linearize(pg_linearize_kernel<true, true>) : linearize(pg_linearize_kernel<false, true>);
         else
-            hipLaunchKernelGGL(pg_linearize_kernel<false>, dim3((ne + 127) / 128), dim3(128), 0, st, g->d_pose.as<double>(),
-                               g->d_from.as<int>(), g->d_to.as<int>(), g->d_meas.as<double>(), ne, eo, d_part, d_ticket,
-                               d_chi + it, static_cast<const double *>(nullptr));
+            weighted ? linearize(pg_linearize_kernel<true, false>) : linearize(pg_linearize_kernel<false, false>);
         if (it == iters)
             break;
         hipLaunchKernelGGL(pg_assemble_kernel, dim3((nb + PG_ASM_ROWS - 1) / PG_ASM_ROWS), dim3(PG_ASM_ROWS * 78), 0, st, nb,
@@ -2438,6 +2641,7 @@ int svo_pg_optimize(svo_posegraph *g, int iters, double *chi2)
     g->dev_nv = nv;  // device poses == host poses, edges unchanged: the next solve uploads what is appended
     g->dev_ne = ne;
     g->dev_ninfo = weighted ? ne : 0;
+    g->eo_w_ne = robust ? ne : -1;
     return SVO_OK;
 }
 
@@ -2586,6 +2790,10 @@ static int pg_read_g2o(svo_posegraph *g, const char *path, const bool keep_info)
     g->eto = et;
     g->meas = em;
     pg_drop_info(g);
+    pg_drop_robust(g);  // (the format has no field for kernels)
+    g->lc_kind = SVO_PG_ROBUST_NONE;
+    g->lc_delta = 0;
+    g->eo_w_ne = -1;
     for (size_t e = 0; e < ehas.size(); e++)
         if (ehas[e])
             pg_store_info(g, (int)e, &einfo[21 * e]);
@@ -2597,5 +2805,127 @@ static int pg_read_g2o(svo_posegraph *g, const char *path, const bool keep_info)
 
 int svo_pg_read_g2o(svo_posegraph *g, const char *path) { return pg_read_g2o(g, path, false); }
 int svo_pg_read_g2o_info(svo_posegraph *g, const char *path) { return pg_read_g2o(g, path, true); }
+
+// ---- robust kernels and pruning ----------------------------------------------------------------
+int svo_pg_set_robust_kernel(svo_posegraph *g, int e, int kind, double delta)
+{
+    SVO_CHECK_ARG(g && e >= 0 && e < g->ne());
+    if (const char *why = pg_prune_plan::check_kernel(kind, delta)) {
+        svo_set_error("svo_pg_set_robust_kernel: edge %d: %s (kind %d, parameter %g)", e, why, kind, delta);
+        return SVO_ERR_ARG;
+    }
+    pg_store_robust(g, e, kind, delta);
+    return SVO_OK;
+}
+
+int svo_pg_get_robust_kernel(const svo_posegraph *g, int e, int *kind, double *delta)
+{
+    SVO_CHECK_ARG(g && e >= 0 && e < g->ne());
+    if (kind)
+        *kind = g->rkind.empty() ? SVO_PG_ROBUST_NONE : g->rkind[e];
+    if (delta)
+        *delta = g->rdelta.empty() ? 0. : g->rdelta[e];
+    return SVO_OK;
+}
+
+int svo_pg_set_loop_closure_kernel(svo_posegraph *g, int kind, double delta)
+{
+    SVO_CHECK_ARG(g);
+    if (const char *why = pg_prune_plan::check_kernel(kind, delta)) {
+        svo_set_error("svo_pg_set_loop_closure_kernel: %s (kind %d, parameter %g)", why, kind, delta);
+        return SVO_ERR_ARG;
+    }
+    g->lc_kind = kind;
+    g->lc_delta = kind == SVO_PG_ROBUST_NONE ? 0. : delta;
+    return SVO_OK;
+}
+
+int svo_pg_edge_residuals(svo_posegraph *g, double *chi2, double *weight, double *rho)
+{
+    SVO_CHECK_ARG(g);
+    std::vector<double> res;
+    int rc;
+    if ((rc = pg_edge_eval(g, res)))
+        return rc;
+    const size_t ne = (size_t)g->ne();
+    double *outs[3] = {chi2, weight, rho};
+    for (int k = 0; k < 3; k++)
+        if (outs[k] && ne)
+            memcpy(outs[k], res.data() + k * ne, ne * sizeof(double));
+    return SVO_OK;
+}
+
+int svo_pg_linearization_weights(svo_posegraph *g, double *weight)
+{
+    SVO_CHECK_ARG(g && weight);
+    const int ne = g->ne();
+    if (g->eo_w_ne != ne || ne == 0 || g->dev_ne != ne || g->dev_nv != g->nv()) {
+        svo_set_error("svo_pg_linearization_weights: the last svo_pg_optimize used no robust kernel, or the graph has changed since");
+        return SVO_ERR_STATE;
+    }
+    SVO_HIP(hipSetDevice(g->ctx->device));
+    SVO_HIP(hipMemcpy2DAsync(weight, sizeof(double), g->d_eo.as<double>() + EO_W, EO_FIELDS * sizeof(double), sizeof(double),
+                             (size_t)ne, hipMemcpyDeviceToHost, g->ctx->stream));
+    SVO_HIP(hipStreamSynchronize(g->ctx->stream));
+    return SVO_OK;
+}
+
+int svo_pg_prune_edges(svo_posegraph *g, double threshold, int *removed, int cap, int *n_removed)
+{
+    SVO_CHECK_ARG(g && cap >= 0 && (removed || cap == 0));
+    if (n_removed)
+        *n_removed = 0;
+    if (std::isnan(threshold)) {
+        svo_set_error("svo_pg_prune_edges: the threshold is NaN");
+        return SVO_ERR_ARG;
+    }
+    if (g->n_robust == 0)
+        return SVO_OK;  // no edge carries a kernel: nothing can go, and nothing is evaluated
+    std::vector<double> res;
+    int rc;
+    if ((rc = pg_edge_eval(g, res)))
+        return rc;
+    const int ne = g->ne();
+    pg_prune_plan::Plan plan;
+    const int verdict = pg_prune_plan::plan(g->nv(), ne, g->efrom.data(), g->eto.data(), g->rkind.data(), res.data() + ne, threshold,
+                                            cap, plan);
+    if (n_removed)
+        *n_removed = (int)plan.removed.size();
+    if (verdict == pg_prune_plan::PRUNE_CAPACITY) {
+        svo_set_error("svo_pg_prune_edges: %zu edges are below the threshold, `removed` holds %d", plan.removed.size(), cap);
+        return SVO_ERR_CAPACITY;
+    }
+    if (verdict == pg_prune_plan::PRUNE_DISCONNECTS) {
+        svo_set_error("svo_pg_prune_edges: without the %zu edges below the threshold vertex %d cannot be reached from vertex 0",
+                      plan.removed.size(), plan.orphan);
+        return SVO_ERR_STATE;
+    }
+    if (plan.removed.empty())
+        return SVO_OK;
+    memcpy(removed, plan.removed.data(), plan.removed.size() * sizeof(int));
+    pg_prune_plan::compact(g->efrom, 1, plan.remap);
+    pg_prune_plan::compact(g->eto, 1, plan.remap);
+    pg_prune_plan::compact(g->meas, 7, plan.remap);
+    if (!g->info.empty()) {
+        pg_prune_plan::compact(g->info, 21, plan.remap);
+        pg_prune_plan::compact(g->has_info, 1, plan.remap);
+        g->n_info = 0;
+        for (char h : g->has_info)
+            g->n_info += h ? 1 : 0;
+        if (g->n_info == 0)
+            pg_drop_info(g);
+    }
+    pg_prune_plan::compact(g->rkind, 1, plan.remap);
+    pg_prune_plan::compact(g->rdelta, 1, plan.remap);
+    g->n_robust -= (int)plan.removed.size();  // every removed edge carried a kernel
+    if (g->n_robust == 0)
+        pg_drop_robust(g);
+    // the device copies of the edges and the elimination structure are those of the graph before: the next solve uploads and
+    // rebuilds (the poses did not change, but dev_nv and dev_ne go together)
+    g->dev_nv = g->dev_ne = g->dev_ninfo = 0;
+    g->built_nv = g->built_ne = -1;
+    g->eo_w_ne = -1;
+    return SVO_OK;
+}
 
 }  // extern "C"
