@@ -385,6 +385,8 @@ extern "C" int svo_anms(svo_ctx *ctx, const float *xy, const float *response, in
     if (n == 0) {
         if (count && mem == SVO_MEM_HOST)
             *count = 0;
+        else if (count)  // as svo_compact: a device count is written for an empty input too
+            SVO_HIP(hipMemsetAsync(count, 0, sizeof(int), ctx->stream));
         return SVO_OK;
     }
     SVO_CHECK_ARG(xy && response && out_idx && count);

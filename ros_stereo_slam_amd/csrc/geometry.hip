@@ -584,6 +584,8 @@ int svo_compact(svo_ctx *ctx, const uint8_t *mask, int n, const float *in_a, int
     if (n == 0) {
         if (count && mem == SVO_MEM_HOST)
             *count = 0;
+        else if (count)  // a device count is an output like the host one: an empty input has zero rows, not the last call's
+            SVO_HIP(hipMemsetAsync(count, 0, sizeof(int), ctx->stream));
         return SVO_OK;
     }
     SVO_CHECK_ARG(mask);

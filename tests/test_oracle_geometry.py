@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 from scipy.spatial.transform import Rotation as Rot
 
+from core_numpy import triangulate as numpy_dlt
 from geom_fixtures import BASELINE, K, K4, project, scene_points, two_view
 
 
@@ -81,13 +82,10 @@ def test_triangulate_known_answer_and_numpy_dlt(orc):
     rng = np.random.default_rng(0)
     b2 = (b + rng.normal(0, 0.5, b.shape)).astype(np.float32)
     xyz2, h2 = orc.triangulate(P1, P2, a, b2)
-    for i in range(0, 300, 17):
-        A = np.array([a[i, 0] * P1[2] - P1[0], a[i, 1] * P1[2] - P1[1], b2[i, 0] * P2[2] - P2[0],
-                      b2[i, 1] * P2[2] - P2[1]], np.float64)
-        v = np.linalg.svd(A)[2][-1]
-        v32 = v.astype(np.float32)
-        ref = v32[:3] / v32[3]
-        assert np.allclose(xyz2[i], ref, rtol=2e-4, atol=1e-4)
+    pick = np.arange(0, 300, 17)
+    ref, vs = numpy_dlt(P1, P2, a[pick], b2[pick])      # the float64 SVD DLT of tests/core_numpy.py
+    for i, r, v in zip(pick, ref, vs):
+        assert np.allclose(xyz2[i], r, rtol=2e-4, atol=1e-4)
         assert abs(abs(np.dot(h2[i].astype(np.float64), v)) - 1) < 1e-5  # same direction, sign free
 
 

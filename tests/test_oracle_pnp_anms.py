@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 from scipy.spatial.transform import Rotation as Rot
 
+from core_numpy import anms as _np_anms          # the brute-force restatement of src/ANMS.cpp:18-67, shared with the seam tests
 from geom_fixtures import K4, project, scene_points
 
 
@@ -85,26 +86,6 @@ def test_pnp_degenerate_inputs(orc):
     R, t = _pose()
     cnt, *_ = orc.pnp_ransac(X, project(X, R, t), K4)
     assert cnt == 0
-
-
-def _np_anms(xy, resp, keep):
-    """Brute-force restatement of src/ANMS.cpp:18-67 (stable sort, clamped index)."""
-    n = len(xy)
-    order = sorted(range(n), key=lambda i: (-resp[i], i))
-    if n <= keep:
-        return np.array(order, np.int32)
-    radii = []
-    for s, i in enumerate(order):
-        r = np.float32(resp[i]) * np.float32(1.11)
-        best = np.finfo(np.float64).max
-        for j in order[:s]:
-            if not (resp[j] > r):
-                break
-            d = xy[i] - xy[j]
-            best = min(best, np.sqrt(float(d[0]) ** 2 + float(d[1]) ** 2))
-        radii.append(best)
-    dec = sorted(radii, reverse=True)[keep]
-    return np.array([i for i, r in zip(order, radii) if r >= dec], np.int32)
 
 
 @pytest.mark.parametrize("n,keep", [(300, 100), (300, 299), (50, 50), (50, 80), (200, 0)])
