@@ -115,6 +115,21 @@ int svo_pyramid_is_mono(svo_ctx *ctx, const svo_pyramid *pyr, int *out);
 /* copy one level out (tests).  out holds w*h*c bytes. */
 int svo_pyramid_get_level(svo_ctx *ctx, const svo_pyramid *pyr, int level, uint8_t *out,
                           int mem, int *w, int *h);
+/* svo_pyramid_create with the choice of derivative levels: want_deriv == 0 makes a pyramid that carries none (a right
+ * image, never the first image of a tracking pass).  svo_lk_track derives them on demand when such a pyramid does become
+ * its first image, and again after every later build. */
+int svo_pyramid_create2(svo_ctx *ctx, int width, int height, int channels, int levels, int want_deriv,
+                        svo_pyramid **out);
+/* copy one level out AS STORED, with its reflect-101 border of 32 pixels on every side (tests): rows are packed,
+ * out holds (h + 64) * (w + 64) * c bytes; *pw and *ph receive the padded sizes.  out == NULL: the sizes only. */
+int svo_pyramid_get_padded_level(svo_ctx *ctx, const svo_pyramid *pyr, int level, uint8_t *out, int mem,
+                                 int *pw, int *ph);
+/* copy one Scharr derivative level out as stored (tests): one int32 word (4 dx & 0xffff) | (4 dy << 16) per pixel and
+ * channel, with its zero border of 32 pixels; rows are packed, out holds (h + 64) * (w + 64) * c words.  out == NULL: the
+ * sizes only.  SVO_ERR_STATE when the pyramid holds no derivative levels at present (4 channels, created without them and
+ * not yet a tracking pass's first image, or never built). */
+int svo_pyramid_get_derivative_level(svo_ctx *ctx, const svo_pyramid *pyr, int level, int32_t *out, int mem,
+                                     int *pw, int *ph);
 
 /* ---- dense grid sampler: visualSLAM::denseKeypointExtractor, src/tracking.cpp:4-12 ------- */
 int svo_grid_keypoints(svo_ctx *ctx, int rows, int cols, int step, float *out_xy, int cap,
@@ -137,6 +152,11 @@ int svo_lk_track_jobs(svo_ctx *ctx, int n_jobs, svo_pyramid *const *prev, const 
 /* svo_pyramid_build of a device image behind a gate, as the chain runner queues it: with *d_gate == 0 (a device int) the
  * pyramid is left as it was.  d_gate may be NULL.  Asynchronous on the context's stream. */
 int svo_pyramid_build_gated(svo_ctx *ctx, svo_pyramid *pyr, const uint8_t *d_image, const int *d_gate);
+/* k pyramids of ONE geometry (width, height, channels, levels) from k device images in one set of launches, as the
+ * lock-step front-ends queue them: 1 <= k <= 32.  d_gates may be NULL; otherwise it holds k device int pointers, each of
+ * which may be NULL, and pyramid a is left as it was when *d_gates[a] == 0.  Asynchronous on the context's stream. */
+int svo_pyramid_build_many(svo_ctx *ctx, int k, svo_pyramid *const *pyrs, const uint8_t *const *d_images,
+                           const int *const *d_gates);
 
 /* ---- order-preserving compaction by a byte mask -------------------------------------------- */
 /* replaces the push_back filters of src/tracking.cpp:20-27 (status), :35-42 and :66-84 (mask).

@@ -84,10 +84,12 @@ def _ptr(a):
 
 
 class Pyramid:
-    def __init__(self, ctx: "Context", w: int, h: int, c: int, levels: int = 4):
+    def __init__(self, ctx: "Context", w: int, h: int, c: int, levels: int = 4, want_deriv: bool = True):
+        """``want_deriv=False``: a pyramid without Scharr derivative levels (``svo_pyramid_create2``), as the front-end keeps
+        for its right images; the tracker derives them when such a pyramid becomes its first image after all."""
         self.ctx, self.w, self.h, self.c, self.levels = ctx, w, h, c, levels
         self._h = C.c_void_p()
-        _check(ctx.lib.svo_pyramid_create(ctx._h, w, h, c, levels, C.byref(self._h)))
+        _check(ctx.lib.svo_pyramid_create2(ctx._h, w, h, c, levels, int(bool(want_deriv)), C.byref(self._h)))
         ctx._children.add(self)
 
     def build(self, image, mem: int = MEM_HOST):
@@ -114,6 +116,24 @@ class Pyramid:
         out = np.empty((h.value, w.value, self.c), np.uint8)
         _check(self.ctx.lib.svo_pyramid_get_level(self.ctx._h, self._h, l, _ptr(out), MEM_HOST,
                                                   C.byref(w), C.byref(h)))
+        return out
+
+    def padded_level(self, l: int) -> np.ndarray:
+        """Level ``l`` as stored, with its reflect-101 border: ``(h + 64, w + 64, c)`` uint8."""
+        w, h = C.c_int(), C.c_int()
+        _check(self.ctx.lib.svo_pyramid_get_padded_level(self.ctx._h, self._h, l, None, MEM_HOST, C.byref(w), C.byref(h)))
+        out = np.empty((h.value, w.value, self.c), np.uint8)
+        _check(self.ctx.lib.svo_pyramid_get_padded_level(self.ctx._h, self._h, l, _ptr(out), MEM_HOST, C.byref(w), C.byref(h)))
+        return out
+
+    def derivative_level(self, l: int) -> np.ndarray:
+        """The packed Scharr words ``(4 dx & 0xffff) | (4 dy << 16)`` of level ``l`` with their zero border:
+        ``(h + 64, w + 64, c)`` int32.  Raises ``SvoError`` (``SVO_ERR_STATE``) when the pyramid holds none."""
+        w, h = C.c_int(), C.c_int()
+        _check(self.ctx.lib.svo_pyramid_get_derivative_level(self.ctx._h, self._h, l, None, MEM_HOST, C.byref(w), C.byref(h)))
+        out = np.empty((h.value, w.value, self.c), np.int32)
+        _check(self.ctx.lib.svo_pyramid_get_derivative_level(self.ctx._h, self._h, l, _ptr(out), MEM_HOST, C.byref(w),
+                                                             C.byref(h)))
         return out
 
     def close(self):
@@ -170,8 +190,19 @@ class Context:
         return ms.value, n.value
 
     # ---- hot-path entry points (host-array convenience forms) ----
-    def pyramid(self, w, h, c, levels=4) -> Pyramid:
-        return Pyramid(self, w, h, c, levels)
+    def pyramid(self, w, h, c, levels=4, want_deriv=True) -> Pyramid:
+        return Pyramid(self, w, h, c, levels, want_deriv)
+
+    def build_pyramids(self, pyrs, d_images, d_gates=None):
+        """``svo_pyramid_build_many``: up to 32 pyramids of one geometry from as many device images in one set of launches.
+        ``d_gates``: None, or one entry per pyramid, each None or a device int (0 leaves that pyramid as it was).
+        Asynchronous on the ctx stream."""
+        k = len(pyrs)
+        assert len(d_images) == k and (d_gates is None or len(d_gates) == k)
+        P = C.c_void_p * max(k, 1)
+        gates = None if d_gates is None else P(*[_ptr(g).value for g in d_gates])
+        _check(self.lib.svo_pyramid_build_many(self._h, k, P(*[p._h.value for p in pyrs]),
+                                               P(*[_ptr(i).value for i in d_images]), gates))
 
     def grid_keypoints(self, rows: int, cols: int, step: int) -> np.ndarray:
         cnt = C.c_int()

@@ -460,6 +460,31 @@ template <int C, int NJ> __global__ __launch_bounds__(PB) void pyr_finish_kernel
 
 }  // namespace
 
+// The derivative levels of a 1- or 3-channel pyramid: one allocation, zeroed once (the Scharr role writes the interiors
+// only, the zero border is never written again).  At creation for a pyramid that wants them; on demand for one that was
+// created without and becomes a tracking pass's first image after all (svo_build_derivatives).
+static int alloc_derivative_levels(svo_ctx *ctx, svo_pyramid *p)
+{
+    size_t ints = 0;
+    for (int l = 0; l < p->levels; l++) {
+        p->dpitch[l] = (((p->dev.w[l] + 2 * SVO_DERIV_PAD) * p->c * 4 + 15) / 16) * 16;
+        const size_t lvl_ints = (size_t)(p->dpitch[l] / 4) * (p->dev.h[l] + 2 * SVO_DERIV_PAD);
+        p->doff[l] = ints + (size_t)SVO_DERIV_PAD * (p->dpitch[l] / 4) + (size_t)SVO_DERIV_PAD * p->c;
+        ints += (lvl_ints + 63) & ~(size_t)63;  // levels start 256-byte aligned
+    }
+    const size_t dbytes = ints * 4 + 1024;  // slack: 16-byte tile loads run a few vectors past a row
+    hipError_t e = hipMalloc((void **)&p->dbase, dbytes);
+    if (e == hipSuccess)
+        e = hipMemsetAsync(p->dbase, 0, dbytes, ctx->stream);  // the zero border is never written again
+    if (e != hipSuccess) {
+        (void)hipFree(p->dbase);
+        p->dbase = nullptr;
+        svo_set_error("hipMalloc derivative levels -> %s", hipGetErrorString(e));
+        return SVO_ERR_HIP;
+    }
+    return SVO_OK;
+}
+
 static void fill_build(PyrBuild &b, int k, svo_pyramid *const *pyrs, const uint8_t *const *d_images, bool deriv_only,
                        const int *const *gates = nullptr)
 {
@@ -537,9 +562,18 @@ int svo_build_derivatives(svo_ctx *ctx, int k, svo_pyramid *const *pyrs)
         return SVO_ERR_ARG;
     }
     for (int a = 0; a < k; a++)
-        if (!pyrs[a]->dbase || (pyrs[a]->c != 1 && pyrs[a]->c != 3)) {
-            svo_set_error("pyramid: created without derivative levels");
+        if (pyrs[a]->c != 1 && pyrs[a]->c != 3) {
+            svo_set_error("pyramid: %d channels carry no derivative levels", pyrs[a]->c);
             return SVO_ERR_STATE;
+        }
+    // a pyramid created without derivative levels (want_deriv == 0) gets its buffer the first time it needs one; it keeps
+    // want_deriv == 0, so its builds go on skipping the Scharr role and clear has_deriv again
+    for (int a = 0; a < k; a++)
+        if (!pyrs[a]->dbase) {
+            SVO_HIP(hipSetDevice(ctx->device));
+            const int rc = alloc_derivative_levels(ctx, pyrs[a]);
+            if (rc)
+                return rc;
         }
     PyrBuild b;
     fill_build(b, k, pyrs, nullptr, true);
@@ -681,23 +715,11 @@ int svo_pyramid_create_ex(svo_ctx *ctx, int width, int height, int channels, int
         p->dev.lvl[l] = l < levels ? p->origin(l) : nullptr;
     p->want_deriv = want_deriv && (channels == 1 || channels == 3);
     if (p->want_deriv) {
-        size_t ints = 0;
-        for (int l = 0; l < levels; l++) {
-            p->dpitch[l] = (((p->dev.w[l] + 2 * SVO_DERIV_PAD) * channels * 4 + 15) / 16) * 16;
-            const size_t lvl_ints = (size_t)(p->dpitch[l] / 4) * (p->dev.h[l] + 2 * SVO_DERIV_PAD);
-            p->doff[l] = ints + (size_t)SVO_DERIV_PAD * (p->dpitch[l] / 4) + (size_t)SVO_DERIV_PAD * channels;
-            ints += (lvl_ints + 63) & ~(size_t)63;  // levels start 256-byte aligned
-        }
-        const size_t dbytes = ints * 4 + 1024;  // slack: 16-byte tile loads run a few vectors past a row
-        e = hipMalloc((void **)&p->dbase, dbytes);
-        if (e == hipSuccess)
-            e = hipMemsetAsync(p->dbase, 0, dbytes, ctx->stream);  // the zero border is never written again
-        if (e != hipSuccess) {
-            (void)hipFree(p->dbase);
+        const int rc = alloc_derivative_levels(ctx, p);
+        if (rc) {
             (void)hipFree(p->base);
             delete p;
-            svo_set_error("hipMalloc derivative levels -> %s", hipGetErrorString(e));
-            return SVO_ERR_HIP;
+            return rc;
         }
     }
     *out = p;
@@ -772,6 +794,65 @@ int svo_pyramid_get_level(svo_ctx *ctx, const svo_pyramid *pyr, int level, uint8
             SVO_HIP(hipStreamSynchronize(ctx->stream));
     }
     return SVO_OK;
+}
+
+int svo_pyramid_create2(svo_ctx *ctx, int width, int height, int channels, int levels, int want_deriv, svo_pyramid **out)
+{
+    return svo_pyramid_create_ex(ctx, width, height, channels, levels, want_deriv != 0, out);
+}
+
+int svo_pyramid_get_padded_level(svo_ctx *ctx, const svo_pyramid *pyr, int level, uint8_t *out, int mem, int *pw, int *ph)
+{
+    SVO_CHECK_ARG(ctx && pyr && level >= 0 && level < pyr->levels);
+    SVO_CHECK_ARG(mem == SVO_MEM_HOST || mem == SVO_MEM_DEVICE);
+    const int W = pyr->dev.w[level] + 2 * SVO_PYR_PAD, H = pyr->dev.h[level] + 2 * SVO_PYR_PAD;
+    if (pw)
+        *pw = W;
+    if (ph)
+        *ph = H;
+    if (out) {
+        const size_t rowb = (size_t)W * pyr->c;  // the pitch's slack is dropped
+        SVO_HIP(hipMemcpy2DAsync(out, rowb, pyr->base + pyr->off[level], pyr->dev.pitch[level], rowb, H,
+                                 mem == SVO_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
+        if (mem == SVO_MEM_HOST)
+            SVO_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return SVO_OK;
+}
+
+int svo_pyramid_get_derivative_level(svo_ctx *ctx, const svo_pyramid *pyr, int level, int32_t *out, int mem, int *pw, int *ph)
+{
+    SVO_CHECK_ARG(ctx && pyr && level >= 0 && level < pyr->levels);
+    SVO_CHECK_ARG(mem == SVO_MEM_HOST || mem == SVO_MEM_DEVICE);
+    if (!pyr->dbase || !pyr->has_deriv || (pyr->c != 1 && pyr->c != 3)) {
+        svo_set_error("pyramid: holds no derivative levels");
+        return SVO_ERR_STATE;
+    }
+    const int W = pyr->dev.w[level] + 2 * SVO_DERIV_PAD, H = pyr->dev.h[level] + 2 * SVO_DERIV_PAD;
+    if (pw)
+        *pw = W;
+    if (ph)
+        *ph = H;
+    if (out) {
+        const size_t rowb = (size_t)W * pyr->c * sizeof(int32_t);
+        // doff names element (0, 0): the padded level starts SVO_DERIV_PAD rows and pixels in front of it
+        const int *first = pyr->dbase + pyr->doff[level] - (size_t)SVO_DERIV_PAD * (pyr->dpitch[level] / 4) -
+                           (size_t)SVO_DERIV_PAD * pyr->c;
+        SVO_HIP(hipMemcpy2DAsync(out, rowb, first, pyr->dpitch[level], rowb, H,
+                                 mem == SVO_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
+        if (mem == SVO_MEM_HOST)
+            SVO_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    return SVO_OK;
+}
+
+int svo_pyramid_build_many(svo_ctx *ctx, int k, svo_pyramid *const *pyrs, const uint8_t *const *d_images,
+                           const int *const *d_gates)
+{
+    SVO_CHECK_ARG(ctx && k >= 1 && k <= PYR_JOBS && pyrs && d_images);
+    for (int a = 0; a < k; a++)
+        SVO_CHECK_ARG(pyrs[a] && d_images[a]);
+    return svo_build_pyramids_from_device(ctx, k, pyrs, d_images, d_gates);
 }
 
 }  // extern "C"
