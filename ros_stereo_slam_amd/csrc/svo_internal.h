@@ -139,7 +139,7 @@ struct svo_ctx {
     int8_t orb_pattern[1024];
     int has_pattern = 0;
     DevBuf orb_cv_out, orb_cv_img, orb_cv_ptrs;
-    // host images in a lock-step group (frontend.hip, chain_enqueue): a copy stream of its own and a ring of three device
+    // host images in a lock-step group (frontend_chain.hip, chain_enqueue_lockstep): a copy stream of its own and a ring of three device
     // slots, each holding one step's left and right images of every chunk of the group -- step f + 2 is uploaded while
     // step f computes; up_ev: a slot's upload has landed, use_ev: its pyramids have been built
     hipStream_t up_stream = nullptr;
@@ -196,7 +196,7 @@ struct ScopedKernelTime {
 };
 int svo_resolve_timers(svo_ctx *ctx);
 
-// ---- the front-end's device-resident frame state (frontend.hip: the chain runner) --------------------------------
+// ---- the front-end's device-resident frame state (frontend_chain.hip: the chain runner) --------------------------------
 // A chunk of frames is queued WITHOUT the host in the loop: the decisions the reference's host policy takes per
 // frame -- keyframe iff fewer than 200 PnP inliers (src/VisualSLAM.cpp:120), retry / shutdown below 10
 // (src/keyFrameManagement.cpp:85-92) -- are taken by pnp_finish_kernel and left here; the keyframe path's kernels are

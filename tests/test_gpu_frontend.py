@@ -233,17 +233,23 @@ def test_run_chunks_side_by_side_equals_one_by_one(ctx):
         c.close()
 
 
-@pytest.mark.parametrize("lengths", [(4, 4, 4), (5, 3, 2, 4), (3, 2) * 8])  # the last: a full group of 16
-def test_chunks_sharing_a_context_run_in_lock_step_with_one_lk_launch(ctx, lengths):
+_SPARSE = dict(grid_step=30, keyframe_min_inliers=200)
+_ANMS = dict(grid_step=10, anms_keep=4096, keyframe_min_inliers=2000)
+
+
+@pytest.mark.parametrize("lengths,kw", [((4, 4, 4), _SPARSE), ((5, 3, 2, 4), _SPARSE), ((3, 2) * 8, _SPARSE),  # a full group of 16
+                                        ((5, 3, 2, 4), _ANMS)],
+                         ids=["lengths0", "lengths1", "lengths2", "lengths1-anms"])
+def test_chunks_sharing_a_context_run_in_lock_step_with_one_lk_launch(ctx, lengths, kw):
     """Jobs whose front-ends share ONE context form a group: one host thread, one pyramidal-LK
     launch per frame for all of them (blockIdx.y = job).  Chunks of different lengths, keyframes
-    falling on different frames: every chunk must still get exactly its stand-alone result."""
+    falling on different frames: every chunk must still get exactly its stand-alone result -- also
+    with ANMS on, whose launch then carries the group's jobs too."""
     import torch
     total = sum(lengths)
     poses, frames = _frames(total)
     dev = [(torch.from_numpy(l).cuda(), torch.from_numpy(r).cuda()) for l, r in frames]
     torch.cuda.synchronize()
-    kw = dict(grid_step=30, keyframe_min_inliers=200)
     bounds, s0 = [], 0
     for n in lengths:
         bounds.append((s0, s0 + n))
@@ -450,8 +456,10 @@ def test_run_chunk_reports_tracking_lost_in_the_middle_of_a_chunk(ctx, pipeline)
     b.close()
 
 
-def test_run_chunk_takes_host_images(ctx):
-    """Host images go through the front-end's staging buffer, in order: the same results as device images."""
+@pytest.mark.parametrize("host_pipeline", [False, True])
+def test_run_chunk_takes_host_images(ctx, host_pipeline):
+    """Host images go through the serial runner's upload ring, in order: the same results as device images.  Asking for
+    the pipeline with host images falls back to the serial runner: the same results as pipeline=False."""
     import torch
     poses, frames = _frames(6)
     dev = [(torch.from_numpy(l).cuda(), torch.from_numpy(r).cuda()) for l, r in frames]
@@ -462,10 +470,18 @@ def test_run_chunk_takes_host_images(ctx):
     a.init(*dev[0])
     b.init(*frames[0])
     ra = a.run_chunk([d[0] for d in dev[1:]], [d[1] for d in dev[1:]], pipeline=True)
-    rb = b.run_chunk([f[0] for f in frames[1:]], [f[1] for f in frames[1:]], pipeline=False)
+    rb = b.run_chunk([f[0] for f in frames[1:]], [f[1] for f in frames[1:]], pipeline=host_pipeline)
     assert ra[0] == rb[0] == 0 and ra[1] == rb[1] == 5
     for x, y in zip(ra[2:], rb[2:]):
         assert np.array_equal(x, y)
+    if host_pipeline:
+        c = capi.VisualOdometry(ctx, 1241, 376, 3, **kw)
+        c.init(*frames[0])
+        rc = c.run_chunk([f[0] for f in frames[1:]], [f[1] for f in frames[1:]], pipeline=False)
+        assert rc[0] == 0 and rc[1] == 5
+        for x, y in zip(rb[2:], rc[2:]):
+            assert np.array_equal(x, y)
+        c.close()
     a.close()
     b.close()
 

@@ -61,7 +61,8 @@ def test_the_solvers_call_no_libm_transcendentals():
 
     root = pathlib.Path(__file__).resolve().parents[1]
     files = [root / "ros_stereo_slam_amd" / "csrc" / f for f in
-             ("fransac.hip", "pnp.hip", "ba.hip", "geometry.hip", "posegraph.hip", "ransac_common.hip.h", "frontend.hip")]
+             ("fransac.hip", "pnp.hip", "ba.hip", "geometry.hip", "posegraph.hip", "ransac_common.hip.h", "frontend.hip",
+              "frontend_chain.hip", "frontend_state.hip.h")]
     files += [root / "oracle" / f for f in ("geometry.c", "pnp.c", "ba.c", "posegraph.c", "vo.c")]
     pat = re.compile(r"(?<![\w.])(sin|cos|acos|asin|atan2?|cbrt|pow|log|exp|sincos)\s*\(")
     for f in files:
