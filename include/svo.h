@@ -731,6 +731,53 @@ int svo_fast_detect_batch(svo_ctx *ctx, const uint8_t *const *images, int n_imag
 int svo_fast_anms_batch(svo_ctx *ctx, const uint8_t *const *images, int n_images, int w, int h, int c,
                         const svo_fast_params *prm, int num_to_keep, int cap, float *xy, float *response, int *n, int mem);
 
+/* ---- Star (CenSurE): xfeatures2d::StarDetector::create()->detect, the detector of the commented pair above
+ * visualSLAM::stereoTriangulate (src/triangulation.cpp:79-80), with BriefDescriptorExtractor as its descriptor --------------------
+ * The algorithm is the one tests/star_numpy.py states.  Grey is the image itself (c = 1) or cvtColor's
+ * integer weights on B, G, R (c = 3).  For the size indices i of sizes0 = {1, 2, 3, 4, 6, 8, 11, 12, 16, 22, 23, 32, 45, 46, 64, 90,
+ * 128}, r = sizes0[i] and t = r + r / 2, the star sum of a pixel is grey over the square |dx|, |dy| <= r plus grey over the diamond
+ * |dx| + |dy| <= t (int32, exact).  svo_star_layout gives the number of (outer, inner) patterns in use, the largest size index and
+ * the border = its t: the pattern count grows while the outer size is below max_size and the next outer star fits min(w, h), and
+ * stops at the 12 patterns there are.  Inside the border a pixel's response is, over the patterns in order, the
+ * float(inner) * (1.f / innerArea) - float(outer) * (1.f / outerArea) of the strictly largest magnitude (float32: two multiplies and
+ * a subtraction) and its size the outer size of that pattern; outside, both are 0.  Suppression works on tiles of
+ * (suppress_nonmax_size / 2 + 1)^2 pixels anchored at (border, border): a tile's strict maximum above response_threshold and its strict
+ * minimum below -response_threshold are candidates; a candidate falls when another pixel within suppress_nonmax_size / 2 of it
+ * (clipped to the image) is >= (<=) it, when its size is below 4, or when the line test fires on the response plane
+ * (line_threshold_projected) or on the plane of pixels of its own size (line_threshold_binarized).
+ *
+ * Output: a tile's maximum before its minimum, tiles in row-major order; xy: the pixel as floats; size: the outer size; response:
+ * the extremum, negative for minima; KeyPoint::angle -1 and octave 0 are constants and are not returned.
+ *
+ * svo_star_detect_batch: n_images (1 ... 16) images of one size, w x h x c bytes each; images: a host array of host or device pointers
+ * according to mem; xy / size / response hold n_images x cap entries, image i's at i * cap (size and response may be NULL); n: HOST
+ * ints in both modes -- the call waits once, for the counts.  A batch returns the bits of one call per image, host memory the bits
+ * of device memory.  An image with no pixel inside the border is legal and has no key points.  SVO_ERR_ARG, nothing written: null ctx
+ * / images / an image / prm / xy / n, xy, size, response or n not 4-byte aligned, c not 1 or 3, n_images outside 1 ... 16, cap < 1, w
+ * or h below 1 or above 16384, max_size outside 3 ... 128, response_threshold < 0, a line threshold < 0, suppress_nonmax_size outside
+ * 1 ... 31.  SVO_ERR_CAPACITY: 255 w h > 2^31 - 1 (the int32 tables could overflow; decided before any allocation, nothing
+ * written), or an image has more than cap key points -- every n[i] then holds the needed count and the first min(n[i], cap) key
+ * points of each image are valid; nothing is written past cap.
+ *
+ * svo_star_responses (diagnostics: it localises a parity failure): the response (w x h floats) and size (w x h int16) planes of one
+ * image following mem, and the border as a HOST int.  Refusals as above; response 4-byte, size 2-byte aligned.
+ *
+ * svo_star_layout: host only, no context.  SVO_ERR_ARG for w or h outside 1 ... 16384 or max_size outside 3 ... 128; the outputs
+ * may be NULL.  The defaults give 9 patterns, index 13 and border 69.                                                            */
+typedef struct svo_star_params {
+    int max_size;                 /* 45 */
+    int response_threshold;       /* 30 */
+    int line_threshold_projected; /* 10 */
+    int line_threshold_binarized; /* 8 */
+    int suppress_nonmax_size;     /* 5 */
+} svo_star_params;
+void svo_star_default_params(svo_star_params *p);
+int svo_star_detect_batch(svo_ctx *ctx, const uint8_t *const *images, int n_images, int w, int h, int c,
+                          const svo_star_params *prm, int cap, float *xy, float *size, float *response, int *n, int mem);
+int svo_star_responses(svo_ctx *ctx, const uint8_t *image, int w, int h, int c, const svo_star_params *prm,
+                       float *response, int16_t *size, int *border, int mem);
+int svo_star_layout(int w, int h, int max_size, int *npatterns, int *max_idx, int *border);
+
 /* ---- PnP-RANSAC: cv::solvePnPRansac(obj,img,K,0,rvec,tvec,false,its,thr,conf,inliers) --------- */
 /* replaces src/keyFrameManagement.cpp:84 (100, 1.0, 0.99) and :88 (100, 8.0, 0.98).
  * obj: n*3 floats (world), img: n*2 floats, K4 = {fx, fy, cx, cy} (HOST doubles), no

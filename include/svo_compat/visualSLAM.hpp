@@ -57,6 +57,12 @@ class visualSLAM {
     bool FAST_FLAG = false;
     int fastThreshold = 1;
     int fastKeep = 0;
+    // with DENSE_FLAG == false and SURF_FLAG == false: true = the sparse branch with the commented detector / descriptor pair of
+    // src/triangulation.cpp:79-80, StarDetector::create() (starMaxSize, starResponseThreshold; the other arguments at their
+    // defaults) + BriefDescriptorExtractor::create(), in ORB's place.  Off: every method issues the calls it always issued.
+    bool STAR_FLAG = false;
+    int starMaxSize = 45;
+    int starResponseThreshold = 30;
     double focal_x = 7.188560000000e+02, cx = 6.071928000000e+02;
     double focal_y = 7.188560000000e+02, cy = 1.852157000000e+02;
     int gridStep = 30;              // src/triangulation.cpp:89
@@ -146,6 +152,19 @@ class visualSLAM {
         return out;
     }
 
+    // ---- src/triangulation.cpp:79: StarDetector::create(starMaxSize, starResponseThreshold)->detect(img, kps) ----
+    // Key points carry their size (the outer size of the winning pattern) and response (negative for dark blobs), angle -1 and
+    // octave 0 as the detector leaves them; a tile's maximum before its minimum, tiles in row-major order.
+    std::vector<KeyPoint> starKeypointExtractor(Mat img)
+    {
+        std::vector<KeyPoint> out[1];
+        if (mat_data(img) == nullptr)
+            return out[0];
+        const Mat *imgs[1] = {&img};
+        starKeypointsBatch(imgs, 1, out);
+        return out[0];
+    }
+
     // ---- include/monoUtils.h:195-213 (declared at include/visualSLAM.h:162) ----
     // The indices of newref2dFeatures, ascending, with no base point listed in `mask` within `radius`: svo_dedup_points in DISC mode.
     // A negative radius keeps everything upstream (no norm is below it); it is passed on as 0, which does too.
@@ -195,6 +214,8 @@ class visualSLAM {
             if (mat_cols(im1) != mat_cols(im2) || mat_rows(im1) != mat_rows(im2) || mat_channels(im1) != mat_channels(im2))
                 throw SvoError(SVO_ERR_ARG, "stereoTriangulate: the two images differ in size");
             surf_ratio_pairs(ctx_, im1, im2, (double)surfHessian, refPts, trkPts);
+        } else if (STAR_FLAG) {
+            starBriefRatioPairs(im1, im2, refPts, trkPts);  // no FmatThresholding, as the ORB branch beside it
         } else {
             orbRatioPairs(im1, im2, refPts, trkPts);  // no FmatThresholding in this branch, as upstream
         }
@@ -597,6 +618,83 @@ class visualSLAM {
         check(svo_orb_extract_batch(ctx_, imgs, 2, mat_cols(im1), mat_rows(im1), mat_channels(im1), &prm, f(kp), nullptr, nullptr,
                                     nullptr, desc.data(), n, SVO_MEM_HOST));
         ratio_match_points(ctx_, SVO_MATCH_L2_U8, desc.data(), desc.data() + nf * 8, 32, n[0], n[1], f(kp), f(kp) + 2 * nf, pt1, pt2);
+    }
+    // n (1 ... 16) images of one size through one svo_star_detect_batch call.  The capacity grows to what the library asks for, so a
+    // call never loses key points.
+    void starKeypointsBatch(const Mat *const *imgs, int n, std::vector<KeyPoint> *kps)
+    {
+        const uint8_t *ptrs[16];
+        same_size_ptrs(imgs, n, "starKeypointExtractor", ptrs);
+        const Mat &first = *imgs[0];
+        svo_star_params prm;
+        svo_star_default_params(&prm);
+        prm.max_size = starMaxSize;
+        prm.response_threshold = starResponseThreshold;
+        size_t cap = 4096;
+        std::vector<float> xy, size, resp;
+        std::vector<int> cnt((size_t)n);
+        for (;;) {
+            const size_t e = cap * (size_t)n;
+            xy.resize(2 * e);
+            size.resize(e);
+            resp.resize(e);
+            const int rc = svo_star_detect_batch(ctx_, ptrs, n, mat_cols(first), mat_rows(first), mat_channels(first), &prm, (int)cap,
+                                                 xy.data(), size.data(), resp.data(), cnt.data(), SVO_MEM_HOST);
+            size_t need = 0;
+            for (int i = 0; i < n; i++)
+                need = (size_t)cnt[(size_t)i] > need ? (size_t)cnt[(size_t)i] : need;
+            if (rc == SVO_ERR_CAPACITY && need > cap) {
+                cap = need;  // every count is the needed one
+                continue;
+            }
+            check(rc);
+            break;
+        }
+        for (int i = 0; i < n; i++) {
+            const size_t b = cap * (size_t)i, m = (size_t)cnt[(size_t)i];
+            kps[i].clear();
+            kps[i].reserve(m);
+            for (size_t j = 0; j < m; j++) {
+                kps[i].emplace_back(xy[2 * (b + j)], xy[2 * (b + j) + 1], size[b + j]);
+                kps[i].back().angle = -1.f;
+                kps[i].back().response = resp[b + j];
+                kps[i].back().octave = 0;
+            }
+        }
+    }
+    // src/triangulation.cpp:79-80 in the place of :105-133: Star on both images (one set of launches), brief->compute on both (one
+    // svo_brief_describe_batch call, 32 bytes; the key points runByImageBorder(28) removes are dropped, as cv erases them),
+    // desc.convertTo(CV_32F) + BFMatcher().knnMatch(desc1, desc2, matches, 2), m.distance < 0.8 * n.distance
+    void starBriefRatioPairs(const Mat &im1, const Mat &im2, std::vector<Point2f> &pt1, std::vector<Point2f> &pt2)
+    {
+        const Mat *imgs[2] = {&im1, &im2};
+        const uint8_t *ptrs[2];
+        same_size_ptrs(imgs, 2, "stereoTriangulate", ptrs);
+        std::vector<KeyPoint> kps[2];
+        starKeypointsBatch(imgs, 2, kps);
+        const size_t cap = std::max<size_t>(std::max(kps[0].size(), kps[1].size()), 1);
+        std::vector<float> xy(2 * 2 * cap, 0.f);
+        int n_in[2], n_out[2] = {0, 0};
+        for (int i = 0; i < 2; i++) {
+            n_in[i] = (int)kps[i].size();
+            for (size_t j = 0; j < kps[i].size(); j++) {
+                xy[2 * (cap * (size_t)i + j)] = kps[i][j].pt.x;
+                xy[2 * (cap * (size_t)i + j) + 1] = kps[i][j].pt.y;
+            }
+        }
+        std::vector<int> kept(2 * cap);
+        std::vector<uint8_t> desc(2 * cap * 32);
+        check(svo_brief_describe_batch(ctx_, ptrs, 2, mat_cols(im1), mat_rows(im1), mat_channels(im1), 32, xy.data(), n_in, (int)cap,
+                                       kept.data(), desc.data(), n_out, SVO_MEM_HOST));
+        std::vector<float> kxy(2 * 2 * cap, 0.f);
+        for (int i = 0; i < 2; i++)
+            for (int j = 0; j < n_out[i]; j++) {
+                const size_t src = cap * (size_t)i + (size_t)kept[cap * (size_t)i + (size_t)j], dst = cap * (size_t)i + (size_t)j;
+                kxy[2 * dst] = xy[2 * src];
+                kxy[2 * dst + 1] = xy[2 * src + 1];
+            }
+        ratio_match_points(ctx_, SVO_MATCH_L2_U8, desc.data(), desc.data() + cap * 32, 32, n_out[0], n_out[1], kxy.data(),
+                           kxy.data() + 2 * cap, pt1, pt2);
     }
     void compact2(const std::vector<uint8_t> &mask, std::vector<Point2f> &a, std::vector<Point2f> &b)
     {

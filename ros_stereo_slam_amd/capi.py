@@ -918,6 +918,104 @@ def fast_anms(self, images, num_to_keep, threshold=10, nonmax=True, max_keypoint
     return _fast_call(self, images, prm, cap, int(num_to_keep), False)
 
 
+class StarParams(C.Structure):
+    """``svo_star_params``: xfeatures2d::StarDetector::create's arguments."""
+    _fields_ = [("max_size", C.c_int), ("response_threshold", C.c_int), ("line_threshold_projected", C.c_int),
+                ("line_threshold_binarized", C.c_int), ("suppress_nonmax_size", C.c_int)]
+
+
+def star_params(**overrides) -> StarParams:
+    p = StarParams()
+    load().svo_star_default_params(C.byref(p))
+    for k, v in overrides.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def _star_prm(params) -> StarParams:
+    return params if isinstance(params, StarParams) else star_params(**(params or {}))
+
+
+def star_layout(w, h, max_size=45):
+    """``svo_star_layout`` -> (npatterns, max_idx, border).  Host only."""
+    out = [C.c_int() for _ in range(3)]
+    _check(load().svo_star_layout(int(w), int(h), int(max_size), *[C.byref(o) for o in out]))
+    return tuple(o.value for o in out)
+
+
+def _star_images(images, mem):
+    """The images where ``mem`` wants them (None: where they are) -> (images, is_device)."""
+    dev = _is_device(images[0]) if mem is None else mem == MEM_DEVICE
+    if dev:
+        import torch
+
+        images = [(im if _is_device(im) else torch.from_numpy(np.ascontiguousarray(im, np.uint8)).cuda()).contiguous() for im in images]
+        torch.cuda.synchronize(images[0].device)
+    else:
+        images = [np.ascontiguousarray(im.cpu().numpy() if _is_device(im) else im, np.uint8) for im in images]
+    return images, dev
+
+
+@_ctx_method
+def star_detect(self, images, prm=None, cap=None, mem=None):
+    """``svo_star_detect_batch``: the Star (CenSurE) detector on 1 ... 16 images of one size (host arrays or device tensors; ``mem``
+    moves them first) in one set of launches -> per image (xy [n, 2], size [n], response [n]) float32 host arrays, a tile's
+    maximum before its minimum, tiles in row-major order.  More than ``cap`` key points in an image:
+    SvoError(SVO_ERR_CAPACITY) whose ``needed`` lists the counts."""
+    prm = _star_prm(prm)
+    nimg = len(images)
+    w, h, c = _image_shape(images[0])
+    if cap is None:
+        cap = max(2 * w * h, 1)                  # a pixel is at most a maximum and a minimum
+    n = (C.c_int * max(nimg, 1))()
+    e = nimg * cap
+    images, dev = _star_images(images, mem)
+    if dev:
+        import torch
+
+        fb = torch.zeros(e * 4, dtype=torch.float32, device=images[0].device)
+        torch.cuda.synchronize(images[0].device)
+        args = [C.c_void_p(fb.data_ptr() + 4 * k * e) for k in (0, 2, 3)]
+    else:
+        xy, size, resp = np.zeros((nimg, cap, 2), np.float32), np.zeros((nimg, cap), np.float32), np.zeros((nimg, cap), np.float32)
+        args = [_ptr(xy), _ptr(size), _ptr(resp)]
+    ptrs = (C.c_void_p * max(nimg, 1))(*[_ptr(im).value for im in images])
+    rc = self.lib.svo_star_detect_batch(self._h, ptrs, nimg, w, h, c, C.byref(prm), cap, *args, n, MEM_DEVICE if dev else MEM_HOST)
+    if rc != SVO_OK:
+        err = SvoError(rc, self.lib.svo_last_error().decode(errors="replace"))
+        err.needed = list(n[:nimg])
+        raise err
+    if dev:
+        _check(self.lib.svo_ctx_sync(self._h))
+        hb = fb.cpu().numpy()
+        xy, size, resp = hb[:2 * e].reshape(nimg, cap, 2), hb[2 * e:3 * e].reshape(nimg, cap), hb[3 * e:].reshape(nimg, cap)
+    return [(xy[i, :n[i]].copy(), size[i, :n[i]].copy(), resp[i, :n[i]].copy()) for i in range(nimg)]
+
+
+@_ctx_method
+def star_responses(self, image, prm=None, mem=None):
+    """``svo_star_responses`` (diagnostics) -> (response [h, w] float32, size [h, w] int16, border) as host values."""
+    prm = _star_prm(prm)
+    w, h, c = _image_shape(image)
+    (img,), dev = _star_images([image], mem)
+    border = C.c_int(-1)
+    if dev:
+        import torch
+
+        resp = torch.zeros((h, w), dtype=torch.float32, device=img.device)
+        size = torch.zeros((h, w), dtype=torch.int16, device=img.device)
+        torch.cuda.synchronize(img.device)
+    else:
+        resp, size = np.zeros((h, w), np.float32), np.zeros((h, w), np.int16)
+    _check(self.lib.svo_star_responses(self._h, _ptr(img), w, h, c, C.byref(prm), _ptr(resp), _ptr(size), C.byref(border),
+                                       MEM_DEVICE if dev else MEM_HOST))
+    if dev:
+        _check(self.lib.svo_ctx_sync(self._h))
+        resp, size = resp.cpu().numpy(), size.cpu().numpy()
+    return resp, size, border.value
+
+
 def brief_default_pattern(bytes=32) -> np.ndarray:
     """``svo_brief_default_pattern``: the library's own test table of a descriptor length, [8 * bytes, 4] int8 rows of
     (y1, x1, y2, x2).  Host only."""

@@ -1,0 +1,433 @@
+"""svo_star_detect_batch and svo_star_responses (csrc/star.hip) against the numpy restatement (tests/star_numpy.py), bit for bit:
+counts, key points, sizes, responses and both planes on every fixture; the smallest shapes where the kernels can go wrong; grey and
+BGR; host and device memory behind guard bands; batches; capacity; every refusal; determinism; the neighbours on the same context;
+the Star + BRIEF composition; the adaptor's smoke program.  Every comparison is exact."""
+import ctypes as C
+import pathlib
+import subprocess
+
+import numpy as np
+import pytest
+
+import star_fixtures as sf
+import star_numpy as sn
+from ros_stereo_slam_amd import capi
+
+pytestmark = pytest.mark.gpu
+
+ROOT = pathlib.Path(__file__).resolve().parents[1]
+
+
+def noise(w, h, seed, channels=1):
+    shape = (h, w) if channels == 1 else (h, w, channels)
+    return np.random.default_rng(seed).integers(0, 256, shape, dtype=np.uint8)
+
+
+def smooth(w, h, seed, channels=1):
+    """Noise averaged over 5 x 5: blobs of a few pixels, so that sizes of 4 and more win and key points survive."""
+    rng = np.random.default_rng(seed)
+    shape = (h + 4, w + 4) if channels == 1 else (h + 4, w + 4, channels)
+    a = rng.integers(0, 256, shape).astype(np.float64)
+    acc = sum(a[dy:dy + h, dx:dx + w] for dy in range(5) for dx in range(5)) / 25.0
+    acc = (acc - acc.mean()) * 4.0 + 128.0
+    return np.clip(np.rint(acc), 0, 255).astype(np.uint8)
+
+
+def want(img, prm):
+    return sn.detect(img, **prm)
+
+
+def same(got, exp, what):
+    assert len(got[0]) == len(exp[0]), (what, len(got[0]), len(exp[0]))
+    for k, col in enumerate(("xy", "size", "response")):
+        assert got[k].dtype == np.float32 and np.array_equal(got[k], exp[k]), (what, col)
+
+
+def same_planes(ctx, img, prm, what, mem=None):
+    resp, size, border = ctx.star_responses(img, prm, mem=mem)
+    e_resp, e_size, e_border, _ = sn.responses(img, prm.get("max_size", 45))
+    assert border == e_border, what
+    assert resp.dtype == np.float32 and size.dtype == np.int16
+    assert np.array_equal(size, e_size), (what, "size plane")
+    assert np.array_equal(resp, e_resp), (what, "response plane", float(np.abs(resp - e_resp).max()))
+
+
+def check(ctx, img, prm, what, planes=True, mem=None):
+    if planes:
+        same_planes(ctx, img, prm, what, mem)
+    exp = want(img, prm)
+    same(ctx.star_detect([img], prm, mem=mem)[0], exp, what)
+    return len(exp[0])
+
+
+# ------------------------------------------------------------------------------------------------------------- fixtures
+@pytest.mark.parametrize("name", sorted(sf.CASES))
+def test_parity_on_every_fixture(ctx, name):
+    img, prm = sf.case(name)
+    n = check(ctx, img, prm, name)
+    assert name in ("flat", "twins", "small") or n > 0
+    check(ctx, img, prm, (name, "device"), mem=capi.MEM_DEVICE)
+    assert capi.star_layout(img.shape[1], img.shape[0], prm.get("max_size", 45)) == sn.layout(img.shape[1], img.shape[0],
+                                                                                              prm.get("max_size", 45))
+
+
+# ------------------------------------------------------------------------------------------------------------- shapes
+@pytest.mark.parametrize("w,h", [(64, 48), (131, 97)])
+def test_small_shapes_at_three_sizes(ctx, w, h):
+    total = 0
+    for k, max_size in enumerate((4, 8, 16)):
+        for img in (smooth(w, h, 10 + k), smooth(w, h, 20 + k, channels=3)):
+            total += check(ctx, img, dict(max_size=max_size, response_threshold=3), (w, h, max_size, img.ndim))
+    assert total > 0
+
+
+def test_default_parameters_at_160_by_150(ctx):
+    img = sf.large()
+    assert sn.layout(160, 150, 45) == (9, 13, 69)
+    assert check(ctx, img, dict(response_threshold=2), "160x150") > 0
+    bgr = np.stack([img, img[::-1], img[:, ::-1]], -1).copy()
+    check(ctx, bgr, dict(response_threshold=2), "160x150 bgr")
+
+
+@pytest.mark.parametrize("transpose", [False, True])
+def test_tile_columns_64_and_65_with_partial_tiles(ctx, transpose):
+    """max_size 4: border 6; tiles of 3: 204 -> 64 columns, 205 -> 65 with one pixel, 206 -> 65 with two."""
+    total = 0
+    for k, w in enumerate((204, 205, 206)):
+        img = smooth(w, 40, 30 + k)
+        img = np.ascontiguousarray(img.T) if transpose else img
+        assert [-(-(w - 12) // 3)] == [{204: 64, 205: 65, 206: 65}[w]]
+        total += check(ctx, img, dict(max_size=4, response_threshold=2), (w, transpose))
+    assert total > 0
+
+
+def test_tile_columns_256_and_257(ctx):
+    total = 0
+    for k, w in enumerate((780, 781)):
+        assert -(-(w - 12) // 3) == 256 + k
+        total += check(ctx, smooth(w, 40, 40 + k), dict(max_size=4, response_threshold=2), w)
+    assert total > 0
+
+
+@pytest.mark.parametrize("nonmax", [1, 3, 5, 7])
+def test_suppression_sizes(ctx, nonmax):
+    n = 0
+    for img in (smooth(131, 97, 50), sf.twins(), sf.bar()):
+        n += check(ctx, img, dict(max_size=16, response_threshold=3, suppress_nonmax_size=nonmax), nonmax, planes=False)
+    assert n > 0
+
+
+def test_thresholds_zero_and_above_every_response(ctx):
+    img = smooth(131, 97, 51)
+    assert check(ctx, img, dict(max_size=16, response_threshold=0), "threshold 0") > 0
+    assert check(ctx, noise(64, 48, 52), dict(max_size=8, response_threshold=0), "threshold 0, noise") >= 0
+    top = int(np.abs(sn.responses(img, 16)[0]).max()) + 1
+    assert check(ctx, img, dict(max_size=16, response_threshold=top), "no key points", planes=False) == 0
+    # line thresholds at their ends: 0 removes everything whose Hessian is not negative, a huge one nothing
+    for lt in (0, 1, 1000000):
+        check(ctx, img, dict(max_size=16, response_threshold=3, line_threshold_projected=lt, line_threshold_binarized=lt), lt, planes=False)
+
+
+def test_images_too_small_for_a_key_point(ctx):
+    for w, h in ((1, 1), (6, 6), (7, 6), (6, 40), (3, 200)):
+        img = noise(w, h, 60 + w)
+        assert check(ctx, img, dict(max_size=4, response_threshold=0), (w, h)) == 0
+        assert check(ctx, img, dict(max_size=4, response_threshold=0), (w, h, "device"), mem=capi.MEM_DEVICE) == 0
+    # one interior pixel: a single tile of one pixel
+    check(ctx, noise(7, 7, 61), dict(max_size=3, response_threshold=0), "7x7")
+    check(ctx, noise(13, 13, 62), dict(max_size=4, response_threshold=0), "13x13")
+
+
+# ------------------------------------------------------------------------------------------------------------- memory
+def raw_detect(ctx, imgs, prm, cap, mem, guard=64, want_cols=True):
+    """The C call with a guard band on both sides of every output -> (rc, n, xy, size, resp) as host arrays, bands attached."""
+    import torch
+
+    nimg = len(imgs)
+    h, w = imgs[0].shape[:2]
+    c = 1 if imgs[0].ndim == 2 else imgs[0].shape[2]
+    n = (C.c_int * nimg)(*([-1] * nimg))
+    lens = (nimg * cap * 2, nimg * cap, nimg * cap)
+    if mem == capi.MEM_DEVICE:
+        keep = [torch.from_numpy(np.ascontiguousarray(im)).cuda() for im in imgs]
+        bufs = [torch.full((m + 2 * guard,), -77.0, dtype=torch.float32, device="cuda") for m in lens]
+        torch.cuda.synchronize()
+        addr = [b.data_ptr() + 4 * guard for b in bufs]
+        ptrs = (C.c_void_p * nimg)(*[k.data_ptr() for k in keep])
+    else:
+        keep = [np.ascontiguousarray(im) for im in imgs]
+        bufs = [np.full(m + 2 * guard, -77.0, np.float32) for m in lens]
+        addr = [b.ctypes.data + 4 * guard for b in bufs]
+        ptrs = (C.c_void_p * nimg)(*[k.ctypes.data for k in keep])
+    args = [C.c_void_p(addr[0]), C.c_void_p(addr[1] if want_cols else 0), C.c_void_p(addr[2] if want_cols else 0)]
+    rc = ctx.lib.svo_star_detect_batch(ctx._h, ptrs, nimg, w, h, c, C.byref(prm), cap, *args, n, mem)
+    ctx.sync()
+    host = [b.cpu().numpy() if mem == capi.MEM_DEVICE else b for b in bufs]
+    for b in host:
+        assert (b[:guard] == -77).all() and (b[-guard:] == -77).all(), "a guard band was written"
+    return rc, list(n), host[0][guard:-guard], host[1][guard:-guard], host[2][guard:-guard]
+
+
+@pytest.mark.parametrize("mem", [capi.MEM_HOST, capi.MEM_DEVICE], ids=["host", "device"])
+def test_guard_bands_and_capacity(ctx, mem):
+    imgs = [smooth(131, 97, 70), smooth(131, 97, 71)[::-1]]
+    prm = capi.star_params(max_size=16, response_threshold=3)
+    exp = [want(im, dict(max_size=16, response_threshold=3)) for im in imgs]
+    needed = [len(e[0]) for e in exp]
+    assert min(needed) > 8
+    for cap in (max(needed) + 5, max(needed), min(needed) - 3, 1):
+        rc, n, xy, size, resp = raw_detect(ctx, imgs, prm, cap, mem)
+        assert rc == (capi.SVO_OK if cap >= max(needed) else capi.SVO_ERR_CAPACITY) and n == needed, cap
+        for k, e in enumerate(exp):
+            m = min(needed[k], cap)
+            assert np.array_equal(xy[2 * k * cap:2 * (k * cap + m)].reshape(-1, 2), e[0][:m])
+            assert np.array_equal(size[k * cap:k * cap + m], e[1][:m]) and np.array_equal(resp[k * cap:k * cap + m], e[2][:m])
+            # the slots between an image's count and cap are untouched
+            assert (xy[2 * (k * cap + m):2 * (k + 1) * cap] == -77).all() and (size[k * cap + m:(k + 1) * cap] == -77).all()
+            assert (resp[k * cap + m:(k + 1) * cap] == -77).all()
+    # size and response are optional
+    rc, n, xy, size, resp = raw_detect(ctx, imgs, prm, max(needed), mem, want_cols=False)
+    assert rc == capi.SVO_OK and n == needed and (size == -77).all() and (resp == -77).all()
+    assert np.array_equal(xy[:2 * needed[0]].reshape(-1, 2), exp[0][0])
+    with pytest.raises(capi.SvoError) as err:
+        ctx.star_detect(imgs, prm, cap=min(needed) - 1, mem=mem)
+    assert err.value.code == capi.SVO_ERR_CAPACITY and err.value.needed == needed
+    for k, got in enumerate(ctx.star_detect(imgs, prm, mem=mem)):                  # a later call with enough room is correct
+        same(got, exp[k], ("after overflow", k))
+
+
+@pytest.mark.parametrize("mem", [capi.MEM_HOST, capi.MEM_DEVICE], ids=["host", "device"])
+def test_planes_behind_guard_bands(ctx, mem):
+    import torch
+
+    guard = 64
+    for img, max_size in ((smooth(67, 45, 72), 4), (smooth(67, 45, 73, channels=3), 8), (noise(9, 30, 74), 16)):
+        h, w = img.shape[:2]
+        c = 1 if img.ndim == 2 else 3
+        px = w * h
+        prm = capi.star_params(max_size=max_size)
+        border = C.c_int(-3)
+        if mem == capi.MEM_DEVICE:
+            src = torch.from_numpy(img).cuda()
+            rb = torch.full((px + 2 * guard,), -77.0, dtype=torch.float32, device="cuda")
+            sb = torch.full((px + 2 * guard,), -77, dtype=torch.int16, device="cuda")
+            torch.cuda.synchronize()
+            args = [C.c_void_p(src.data_ptr()), C.c_void_p(rb.data_ptr() + 4 * guard), C.c_void_p(sb.data_ptr() + 2 * guard)]
+        else:
+            src = np.ascontiguousarray(img)
+            rb, sb = np.full(px + 2 * guard, -77.0, np.float32), np.full(px + 2 * guard, -77, np.int16)
+            args = [C.c_void_p(src.ctypes.data), C.c_void_p(rb.ctypes.data + 4 * guard), C.c_void_p(sb.ctypes.data + 2 * guard)]
+        rc = ctx.lib.svo_star_responses(ctx._h, args[0], w, h, c, C.byref(prm), args[1], args[2], C.byref(border), mem)
+        ctx.sync()
+        assert rc == capi.SVO_OK
+        rb, sb = (b.cpu().numpy() if mem == capi.MEM_DEVICE else b for b in (rb, sb))
+        for b in (rb, sb):
+            assert (b[:guard] == -77).all() and (b[-guard:] == -77).all(), "a guard band was written"
+        e_resp, e_size, e_border, _ = sn.responses(img, max_size)
+        assert border.value == e_border
+        assert np.array_equal(rb[guard:-guard].reshape(h, w), e_resp) and np.array_equal(sb[guard:-guard].reshape(h, w), e_size)
+
+
+def test_batch_of_16_equals_16_single_calls(ctx):
+    imgs = [smooth(75, 61, 100 + k) for k in range(12)] + [noise(75, 61, 200 + k) for k in range(4)]
+    prm = dict(max_size=8, response_threshold=3)
+    for mem in (capi.MEM_HOST, capi.MEM_DEVICE):
+        batch = ctx.star_detect(imgs, prm, mem=mem)
+        assert len(batch) == 16 and sum(len(b[0]) for b in batch) > 16
+        for k, img in enumerate(imgs):
+            same(batch[k], ctx.star_detect([img], prm, mem=mem)[0], ("single", k))
+            same(batch[k], want(img, prm), ("restatement", k))
+    bgr = [smooth(50, 47, 300 + k, channels=3) for k in range(16)]
+    for k, got in enumerate(ctx.star_detect(bgr, prm)):
+        same(got, want(bgr[k], prm), ("bgr batch", k))
+
+
+# ------------------------------------------------------------------------------------------------------------- refusals
+def test_every_refusal_writes_nothing(ctx):
+    lib = ctx.lib
+    img = np.ascontiguousarray(smooth(64, 48, 80))
+    ptrs = (C.c_void_p * 17)(*([img.ctypes.data] * 17))
+    good = capi.star_params(max_size=8, response_threshold=3)
+    xy, size, resp = np.full((4096, 2), -5, np.float32), np.full(4096, -5, np.float32), np.full(4096, -5, np.float32)
+    plane_r, plane_s = np.full((48, 64), -5, np.float32), np.full((48, 64), -5, np.int16)
+    n = (C.c_int * 17)(*([-3] * 17))
+    border = C.c_int(-3)
+    X, S, R = (a.ctypes.data_as(C.c_void_p) for a in (xy, size, resp))
+    PR, PS = plane_r.ctypes.data_as(C.c_void_p), plane_s.ctypes.data_as(C.c_void_p)
+
+    def detect(images=ptrs, nimg=1, w=64, h=48, c=1, prm=good, cap=4, xy_=X, size_=S, resp_=R, n_=n, mem=capi.MEM_HOST, h_=ctx._h):
+        return lib.svo_star_detect_batch(h_, images, nimg, w, h, c, C.byref(prm) if prm else None, cap, xy_, size_, resp_, n_, mem)
+
+    def planes(image=C.c_void_p(img.ctypes.data), w=64, h=48, c=1, prm=good, r_=PR, s_=PS, b_=C.byref(border), mem=capi.MEM_HOST,
+               h_=ctx._h):
+        return lib.svo_star_responses(h_, image, w, h, c, C.byref(prm) if prm else None, r_, s_, b_, mem)
+
+    sp = capi.star_params
+    bad_prm = [sp(max_size=2), sp(max_size=129), sp(response_threshold=-1), sp(line_threshold_projected=-1),
+               sp(line_threshold_binarized=-1), sp(suppress_nonmax_size=0), sp(suppress_nonmax_size=32)]
+    shared = [dict(prm=None), dict(c=0), dict(c=2), dict(c=4), dict(w=0), dict(h=0), dict(w=-4), dict(w=16385), dict(h=16385),
+              dict(mem=2), dict(h_=None)] + [dict(prm=p) for p in bad_prm]
+    odd = lambda a: C.c_void_p(a.ctypes.data + 2)
+    cases = shared + [dict(images=None), dict(xy_=None), dict(n_=None), dict(nimg=0), dict(nimg=17), dict(nimg=-1), dict(cap=0),
+                      dict(cap=-1), dict(xy_=odd(xy)), dict(size_=odd(size)), dict(resp_=odd(resp)), dict(n_=C.c_void_p(C.addressof(n) + 2)),
+                      dict(images=(C.c_void_p * 2)(img.ctypes.data, None), nimg=2)]
+    for kw in cases:
+        assert detect(**kw) == capi.SVO_ERR_ARG, kw
+        assert b"svo_star_detect_batch" in lib.svo_last_error(), kw
+    for kw in shared + [dict(image=None), dict(r_=None), dict(s_=None), dict(b_=None), dict(r_=odd(plane_r)),
+                        dict(s_=C.c_void_p(plane_s.ctypes.data + 1)), dict(b_=C.c_void_p(C.addressof(n) + 2))]:
+        assert planes(**kw) == capi.SVO_ERR_ARG, kw
+        assert b"svo_star_responses" in lib.svo_last_error(), kw
+    # the int32 tables could overflow: refused before anything is allocated or read
+    for w, h in ((16384, 515), (2902, 2902), (16384, 16384)):
+        assert detect(w=w, h=h) == capi.SVO_ERR_CAPACITY and planes(w=w, h=h) == capi.SVO_ERR_CAPACITY
+    assert (xy == -5).all() and (size == -5).all() and (resp == -5).all() and all(v == -3 for v in n) and border.value == -3
+    assert (plane_r == -5).all() and (plane_s == -5).all(), "a refused call wrote something"
+    for bad in ((0, 48, 45), (64, 16385, 45), (64, 48, 2), (64, 48, 129)):
+        assert lib.svo_star_layout(*bad, None, None, None) == capi.SVO_ERR_ARG
+    assert lib.svo_star_layout(64, 48, 45, None, None, None) == capi.SVO_OK
+    # the legal neighbours of the refusals
+    assert detect(cap=4096) == capi.SVO_OK and n[0] == len(want(img, dict(max_size=8, response_threshold=3))[0]) > 0
+    assert detect(prm=sp(max_size=3, response_threshold=0, line_threshold_projected=0, line_threshold_binarized=0,
+                         suppress_nonmax_size=31), cap=4096) == capi.SVO_OK
+    assert planes() == capi.SVO_OK and border.value == 12
+
+
+# ------------------------------------------------------------------------------------------------------------- determinism
+def blob(res):
+    return b"".join(a.tobytes() for r in res for a in r)
+
+
+def test_five_runs_and_two_contexts_give_identical_bytes(ctx):
+    imgs = [smooth(160, 120, 90), smooth(160, 120, 91), noise(160, 120, 92)]
+    prm = dict(max_size=16, response_threshold=2)
+    run = lambda c: blob(c.star_detect(imgs, prm)) + b"".join(a.tobytes() for a in c.star_responses(imgs[0], prm)[:2])
+    runs = [run(ctx) for _ in range(5)]
+    assert all(r == runs[0] for r in runs[1:]) and len(runs[0]) > 160 * 120 * 6 + 100
+    other = capi.Context(0)
+    try:
+        for _ in range(2):                          # taking turns
+            assert run(other) == runs[0]
+            assert run(ctx) == runs[0]
+    finally:
+        other.close()
+
+
+# ------------------------------------------------------------------------------------------------------------- neighbours
+def test_fast_brief_and_surf_are_undisturbed(ctx):
+    img = smooth(200, 150, 95)
+    pts = (np.random.default_rng(4).random((300, 2)) * [140, 90] + 30).astype(np.float32)
+
+    def neighbours():
+        return (blob(ctx.fast_detect([img, img[::-1].copy()], 5, True, score=True)) + blob(ctx.brief_describe([img], [pts]))
+                + blob([r[:6] for r in ctx.surf_extract([img], descriptors=False)]))
+
+    before = neighbours()
+    ctx.star_detect([img] * 3, dict(max_size=16, response_threshold=2))
+    ctx.star_responses(sf.colour(), dict(max_size=8))
+    ctx.star_detect([sf.large()] * 16, dict(response_threshold=2), mem=capi.MEM_DEVICE)
+    assert neighbours() == before and len(before) > 30000
+
+
+# ------------------------------------------------------------------------------------------------------------- Star + BRIEF
+def test_star_brief_composition_device_equals_host(ctx):
+    """The four calls with every list left where the call before wrote it -- Star's columns (image i at i * cap) are the descriptor
+    call's input, its descriptors and kept indices the matcher's and the ratio test's; the host sees the counts only -- against the
+    same four calls on host arrays."""
+    import torch
+
+    left = smooth(320, 200, 96)
+    right = np.roll(left, -7, axis=1)
+    prm = dict(max_size=16, response_threshold=3)
+    # host memory, through the wrappers
+    kps = ctx.star_detect([left, right], prm)
+    (d1, i1), (d2, i2) = ctx.brief_describe([left, right], [k[0] for k in kps], 32)
+    idx, dist = ctx.knn_match(d1, d2, 2, capi.MATCH_L2_U8)
+    p1, p2, mask = ctx.ratio_pairs(idx, dist, kps[0][0][i1], kps[1][0][i2], 0.8)
+    assert len(p1) >= 8
+    # device memory, the C calls on device buffers
+    lib, h_, V = ctx.lib, ctx._h, C.c_void_p
+    cap = max(len(k[0]) for k in kps) + 3
+    dev = [torch.from_numpy(im).cuda() for im in (left, right)]
+    ptrs = (C.c_void_p * 2)(*[d.data_ptr() for d in dev])
+    f32 = lambda n: torch.full((n,), -7.0, dtype=torch.float32, device="cuda")
+    xy, size, resp = f32(2 * cap * 2), f32(2 * cap), f32(2 * cap)
+    kept = torch.full((2 * cap,), -7, dtype=torch.int32, device="cuda")
+    desc = torch.zeros(2 * cap * 32, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    sp = capi.star_params(**prm)
+    n, m = (C.c_int * 2)(), (C.c_int * 2)()
+    assert lib.svo_star_detect_batch(h_, ptrs, 2, 320, 200, 1, C.byref(sp), cap, V(xy.data_ptr()), V(size.data_ptr()),
+                                     V(resp.data_ptr()), n, capi.MEM_DEVICE) == capi.SVO_OK
+    assert list(n) == [len(k[0]) for k in kps]
+    assert lib.svo_brief_describe_batch(h_, ptrs, 2, 320, 200, 1, 32, V(xy.data_ptr()), n, cap, V(kept.data_ptr()),
+                                        V(desc.data_ptr()), m, capi.MEM_DEVICE) == capi.SVO_OK
+    assert list(m) == [len(i1), len(i2)]
+    ctx.sync()
+    # the key points the filter kept, gathered on the device
+    pts = xy.view(2, cap, 2)
+    kxy = [pts[k][kept.view(2, cap)[k, :m[k]].long()].contiguous() for k in range(2)]
+    didx = torch.full((m[0] * 2,), -7, dtype=torch.int32, device="cuda")
+    ddist, dp1, dp2 = f32(m[0] * 2), f32(m[0] * 2), f32(m[0] * 2)
+    dmask = torch.zeros(m[0], dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    qo, to, cnt = (C.c_int * 2)(0, m[0]), (C.c_int * 2)(0, m[1]), C.c_int()
+    assert lib.svo_knn_match(h_, capi.MATCH_L2_U8, V(desc.data_ptr()), V(desc.data_ptr() + cap * 32), 32, qo, to, 1, 2,
+                             V(didx.data_ptr()), V(ddist.data_ptr()), capi.MEM_DEVICE) == capi.SVO_OK
+    assert lib.svo_ratio_pairs(h_, V(didx.data_ptr()), V(ddist.data_ptr()), m[0], 2, C.c_double(0.8), V(kxy[0].data_ptr()),
+                               V(kxy[1].data_ptr()), V(dp1.data_ptr()), V(dp2.data_ptr()), V(dmask.data_ptr()), C.byref(cnt),
+                               capi.MEM_DEVICE) == capi.SVO_OK
+    ctx.sync()
+    assert cnt.value == len(p1)
+    host = lambda t: t.cpu().numpy()
+    for k in range(2):
+        for got, exp in ((host(pts[k])[:n[k]], kps[k][0]), (host(size.view(2, cap)[k])[:n[k]], kps[k][1]),
+                         (host(resp.view(2, cap)[k])[:n[k]], kps[k][2]), (host(kept.view(2, cap)[k])[:m[k]], (i1, i2)[k]),
+                         (host(desc.view(2, cap, 32)[k])[:m[k]], (d1, d2)[k])):
+            assert got.dtype == exp.dtype and np.array_equal(got, exp), k
+    assert np.array_equal(host(didx).reshape(-1, 2), idx) and np.array_equal(host(ddist).reshape(-1, 2), dist)
+    assert np.array_equal(host(dp1).reshape(-1, 2)[:cnt.value], p1) and np.array_equal(host(dp2).reshape(-1, 2)[:cnt.value], p2)
+    assert np.array_equal(host(dmask), mask)
+    # the matches are the shift
+    assert np.median(p1[:, 0] - p2[:, 0]) == 7 and np.median(np.abs(p1[:, 1] - p2[:, 1])) == 0
+
+
+# ------------------------------------------------------------------------------------------------------------- the adaptor
+def test_star_brief_smoke_runs_on_gpu(ctx, tmp_path):
+    from ros_stereo_slam_amd import sequence, synth
+    from test_star_abi import build_smoke
+
+    # a fronto-parallel texture at a disparity of 12 pixels (depth fx b / 12): every point has a depth whose sign means something
+    K4 = (360.0, 360.0, 320.0, 120.0)
+    left, right = synth.textured_pair(640, 240, 3, shift=(-12.0, 0.0), seed=4)
+    exe = tmp_path / "star_brief_smoke"
+    build_smoke(exe)
+    files = [str(tmp_path / "left.ppm"), str(tmp_path / "right.ppm")]
+    for f, im in zip(files, (left, right)):
+        sequence.write_image(f, im)
+    max_size, thr = 16, 8
+    run = subprocess.run([str(exe), *files, *(repr(v) for v in K4), repr(synth.KITTI_BASELINE), str(max_size), str(thr)],
+                         capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0 and "star brief smoke ok" in run.stdout, (run.returncode, run.stdout[-2000:], run.stderr)
+    sections, name = {}, None
+    for line in run.stdout.splitlines():
+        if line.startswith("# "):
+            name = line.split()[1]
+            sections[name] = []
+        elif name and line[0] in "-0123456789":
+            sections[name].append([float(v) for v in line.split()])
+    star = np.array(sections["star"], np.float32).reshape(-1, 4)
+    prm = dict(max_size=max_size, response_threshold=thr)
+    exp = want(left, prm)                       # the program's key points are the library's, and the library's are the restatement's
+    assert len(star) > 20 and np.array_equal(star[:, :2], exp[0]) and np.array_equal(star[:, 2], exp[1])
+    assert np.array_equal(star[:, 3], exp[2])
+    # the branch is the four calls
+    kps = ctx.star_detect([left, right], prm)
+    (d1, i1), (d2, i2) = ctx.brief_describe([left, right], [k[0] for k in kps], 32)
+    idx, dist = ctx.knn_match(d1, d2, 2, capi.MATCH_L2_U8)
+    p1, p2, _ = ctx.ratio_pairs(idx, dist, kps[0][0][i1], kps[1][0][i2], 0.8)
+    pairs = np.array(sections["pairs"], np.float32).reshape(-1, 5)
+    assert len(pairs) >= 8 and np.array_equal(pairs[:, :2], p1)
+    depth = pairs[:, 4]
+    good = np.abs(p1[:, 0] - p2[:, 0] - 12.0) < 0.5
+    assert good.mean() > 0.5 and (depth[good] > 0).all()
