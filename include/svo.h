@@ -825,6 +825,39 @@ int svo_ba_3d2d(svo_ctx *ctx, const float *pts2d, const float *pts3d, int n, con
                 const double *R9, double *t3, int iterations, double *R9_out, double *pts3d_out,
                 double *info, int mem);
 
+/* ---- windowed bundle adjustment: several poses, free points, mono and stereo observations ----- */
+/* OURS in scope (upstream's README names it as future work), g2o's in arithmetic: Levenberg over
+ * BlockSolver<6,3> with n_poses VertexSE3Expmap (poses12: R9 | t3 per pose, world -> camera; a pose
+ * whose pose_fixed byte is non-zero is held) and n_points FREE, marginalised VertexSBAPointXYZ.
+ * Observations are stored CSR by point: point i owns obs_start[i] .. obs_start[i+1]-1, each with
+ * the index of the observing pose and (u, v, u_right).  u_right NaN: EdgeSE3ProjectXYZ, residual
+ * (u - (fx x/z + cx), v - (fy y/z + cy)); else EdgeStereoSE3ProjectXYZ, which adds
+ * u_right - (fx x/z + cx - bf/z).  Identity information.  huber_* > 0: g2o's RobustKernelHuber of
+ * that delta on the observations of that kind (H and b scaled by rho', chi2 sums rho).
+ * lambda0 = 1e-5 max|diag H| over pose and point blocks, at most ten trials per iteration, the
+ * stopping rules of svo_ba_3d2d.  A point without observations is skipped and comes back
+ * unchanged.  Refused with SVO_ERR_ARG, nothing written: n_poses outside 1..32, more than 16 or no
+ * free poses, n_points < 1, an obs_pose out of range, an obs_start that decreases or does not
+ * begin at 0, a point seen twice by one pose, a free pose with fewer than three observations,
+ * iterations < 0, a negative Huber delta, a stereo observation with bf <= 0, a bad mem;
+ * SVO_ERR_CAPACITY beyond 2^20 points or 2^28 observations.  poses12 / pose_fixed and the optional
+ * outputs are HOST in both modes: pts3d_out n_points*3 doubles, obs_chi2_out the final e^T e of
+ * every observation (no kernel applied), info[6] = {chi2 before, chi2 after, final lambda,
+ * iterations run, trials, observations}.  Every sum runs in a fixed order: the result is the same
+ * bit for bit on every run.  The host reads one small record per trial; the call synchronises.   */
+typedef struct svo_ba_window_params {
+    double fx, fy, cx, cy;   /* g2o EdgeSE3ProjectXYZ / EdgeStereoSE3ProjectXYZ read both focal lengths */
+    double bf;               /* fx * baseline; read by stereo observations only                           */
+    int    iterations;       /* default 10                                                                */
+    double huber_mono;       /* 0 (default) = no kernel; else Huber delta on a 2-residual observation     */
+    double huber_stereo;     /* 0 (default) = no kernel; else Huber delta on a 3-residual observation     */
+} svo_ba_window_params;
+void svo_ba_window_default_params(svo_ba_window_params *p);
+int svo_ba_window(svo_ctx *ctx, const svo_ba_window_params *p, int n_poses, double *poses12,
+                  const uint8_t *pose_fixed, int n_points, const float *pts3d, const int *obs_start,
+                  const int *obs_pose, const float *obs_uvr, double *pts3d_out, double *obs_chi2_out,
+                  double *info, int mem);
+
 /* ---- the front-end frame loop: visualSLAM::initSequence, src/VisualSLAM.cpp:11-169 ----------- */
 typedef struct svo_vo_params {
     double fx, fy, cx, cy;    /* include/visualSLAM.h:82-87 (KITTI 00-02)                      */

@@ -40,6 +40,60 @@ class visualOdometry {
             (t.rows == 3 ? t.at<double>(i, 0) : t.at<double>(0, i)) = tv(i);
     }
 
+    // OURS (upstream's README names it as future work): svo_ba_window behind the class's types.  R / t: one 3x3 / 3x1 CV_64F per
+    // pose, world -> camera, written back; fixed: one flag per pose (non-zero = held).  Observations CSR by point: point i owns
+    // obs_start[i] .. obs_start[i + 1] - 1, each with its pose index and (u, v, u_right), u_right NaN = mono.  K 3x3 CV_64F (both
+    // focal lengths are read); bf = fx * baseline.  baIterations, baWindowHuberMono / Stereo are the parameters; lastWindowInfo
+    // receives chi2 before / after, lambda, iterations, trials, observations.  Optional: the refined points (3 doubles each) and
+    // the final e^T e of every observation.
+    double baWindowHuberMono = 0, baWindowHuberStereo = 0;
+    double lastWindowInfo[6] = {0, 0, 0, 0, 0, 0};
+    void BundleAdjustWindow(std::vector<Mat> &R, std::vector<Mat> &t, const std::vector<unsigned char> &fixed,
+                            const std::vector<Point3f> &points_3d, const std::vector<int> &obs_start, const std::vector<int> &obs_pose,
+                            const std::vector<float> &obs_uvr, Mat &K, double bf, std::vector<double> *points_out = nullptr,
+                            std::vector<double> *obs_chi2 = nullptr)
+    {
+        const size_t np = R.size(), n = points_3d.size();
+        if (np == 0 || t.size() != np || fixed.size() != np || n == 0 || obs_start.size() != n + 1 ||
+            obs_uvr.size() != 3 * obs_pose.size() || obs_start.back() != (int)obs_pose.size())
+            throw std::invalid_argument("BundleAdjustWindow: one R, t and flag per pose; obs_start of n + 1 entries ending at the "
+                                        "observation count; three floats per observation");
+        std::vector<double> poses(12 * np);
+        for (size_t j = 0; j < np; j++) {
+            const Mat33d Rm = mat33_of(R[j]);
+            const Vec3d tv = vec3_of(t[j]);
+            for (int k = 0; k < 9; k++)
+                poses[12 * j + k] = Rm.m[k];
+            for (int k = 0; k < 3; k++)
+                poses[12 * j + 9 + k] = tv(k);
+        }
+        const Mat33d Km = mat33_of(K);
+        svo_ba_window_params prm;
+        svo_ba_window_default_params(&prm);
+        prm.fx = Km(0, 0);
+        prm.fy = Km(1, 1);
+        prm.cx = Km(0, 2);
+        prm.cy = Km(1, 2);
+        prm.bf = bf;
+        prm.iterations = baIterations;
+        prm.huber_mono = baWindowHuberMono;
+        prm.huber_stereo = baWindowHuberStereo;
+        if (points_out)
+            points_out->assign(3 * n, 0.0);
+        if (obs_chi2)
+            obs_chi2->assign(obs_pose.size(), 0.0);
+        check(svo_ba_window(ctx_, &prm, (int)np, poses.data(), fixed.data(), (int)n, reinterpret_cast<const float *>(points_3d.data()),
+                            obs_start.data(), obs_pose.data(), obs_uvr.data(), points_out ? points_out->data() : nullptr,
+                            obs_chi2 && !obs_chi2->empty() ? obs_chi2->data() : nullptr, lastWindowInfo, SVO_MEM_HOST));
+        for (size_t j = 0; j < np; j++) {
+            for (int r = 0; r < 3; r++) {
+                for (int c = 0; c < 3; c++)
+                    R[j].at<double>(r, c) = poses[12 * j + 3 * r + c];
+                (t[j].rows == 3 ? t[j].at<double>(r, 0) : t[j].at<double>(0, r)) = poses[12 * j + 9 + r];
+            }
+        }
+    }
+
     // detector->detect(img, kps) + detector->compute(img, kps, desc) with SURF::create(surfHessian): 64 floats per key point
     void surfFeatures(const Mat &img, std::vector<KeyPoint> &kps, std::vector<float> &desc)
     {

@@ -1505,6 +1505,51 @@ def ba_3d2d(self, pts2d, pts3d, K4, R, t, iterations=10):
                                  iterations=int(info[3]), trials=int(info[4]))
 
 
+class ba_window_params(C.Structure):
+    """``svo_ba_window_params``; ``ba_window_params.default()`` holds the library's defaults."""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("bf", C.c_double),
+                ("iterations", C.c_int), ("huber_mono", C.c_double), ("huber_stereo", C.c_double)]
+
+    @classmethod
+    def default(cls, **kw):
+        p = cls()
+        load().svo_ba_window_default_params(C.byref(p))
+        for k, v in kw.items():
+            if k not in dict(cls._fields_):
+                raise TypeError(f"svo_ba_window_params has no field {k}")
+            setattr(p, k, v)
+        return p
+
+
+@_ctx_method
+def ba_window(self, poses, fixed, pts3d, obs_start, obs_pose, obs_uvr, params=None, mem=MEM_HOST):
+    """Windowed bundle adjustment (``svo_ba_window``) -> (poses (P, 12), points (N, 3), per-observation chi2, info).  ``poses``: R9 | t3
+    per pose, world -> camera; ``fixed``: one byte per pose; the observations CSR by point.  ``pts3d``, ``obs_start``, ``obs_pose``
+    and ``obs_uvr`` follow ``mem`` (device: tensors or addresses, with ``obs_start`` readable for its sizes only through the
+    library); ``params``: a ``ba_window_params`` or a dict of its fields."""
+    if params is None:
+        params = ba_window_params.default()
+    elif isinstance(params, dict):
+        params = ba_window_params.default(**params)
+    P = np.array(poses, np.float64).reshape(-1, 12).copy()
+    fx = np.ascontiguousarray(fixed, np.uint8).reshape(-1)
+    assert fx.shape[0] == P.shape[0]
+    if mem == MEM_HOST:
+        pts3d = np.ascontiguousarray(pts3d, np.float32).reshape(-1, 3)
+        obs_start = np.ascontiguousarray(obs_start, np.int32).reshape(-1)
+        obs_pose = np.ascontiguousarray(obs_pose, np.int32).reshape(-1)
+        obs_uvr = np.ascontiguousarray(obs_uvr, np.float32).reshape(-1, 3)
+        n, n_obs = pts3d.shape[0], obs_pose.shape[0]
+        assert obs_start.shape[0] == n + 1 and obs_uvr.shape[0] == n_obs and (n_obs == 0 or int(obs_start.max()) <= n_obs)
+    else:
+        n, n_obs = int(obs_start.shape[0]) - 1, int(obs_pose.shape[0])
+    Xout, chi, info = np.zeros((n, 3)), np.zeros(n_obs), np.zeros(6)
+    _check(self.lib.svo_ba_window(self._h, C.byref(params), P.shape[0], _ptr(P), _ptr(fx), n, _ptr(pts3d), _ptr(obs_start),
+                                  _ptr(obs_pose), _ptr(obs_uvr), _ptr(Xout), _ptr(chi), _ptr(info), mem))
+    return P, Xout, chi, dict(chi2_before=info[0], chi2_after=info[1], lambda_final=info[2], iterations=int(info[3]),
+                              trials=int(info[4]), observations=int(info[5]))
+
+
 class VoParams(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
                 ("baseline", C.c_double), ("grid_step", C.c_int), ("anms_keep", C.c_int),

@@ -179,6 +179,8 @@ struct svo_ctx {
     // fast.hip: the grey, fired and score planes of a batch, the per-wavefront counts and offsets of the ordered compaction, the
     // key-point lists of host calls and of the chained ANMS (layout: fast_plan.hip.h)
     DevBuf fast_work;
+    // ba_window.hip: the host copy of a device caller's CSR arrays, which the refusals are decided on
+    std::vector<unsigned char> ba_win_host;
 };
 
 // Low-latency host wait for everything queued on the context's stream: records an event and
