@@ -19,6 +19,8 @@
 // every thread carries redundantly (no broadcast, no extra barrier).
 // Bound: f64 VALU latency of one workgroup (the problem is 4096 x ~1 kflop per pass); HBM traffic
 // is the points once (20 B each) + 48 B per point per pass of L2-resident estimates.
+#include "ba_window_plan.hip.h"  // the Levenberg accept / reject rule, shared with svo_ba_window's host loop
+#include "se3_solve.hip.h"
 #include "small_solve.hip.h"
 #include "svo_internal.h"
 #include "wave_ops.hip.h"
@@ -50,25 +52,14 @@ __device__ __forceinline__ void ba_linearize(const double *R, const double *t, c
     const double w = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + t[2];
     L.e[0] = (double)zx - (x / w * f + cx);
     L.e[1] = (double)zy - (y / w * f + cy);
-    const double w2 = w * w;
     const double t02 = -x / w * f, t12 = -y / w * f, s = -1. / w;
+    // NOT shared with bw_linearize's A: the two round differently, each pinned to its own checker -- do not unify
 #pragma unroll
     for (int c = 0; c < 3; c++) {
         L.A[c] = s * (f * R[c] + t02 * R[6 + c]);
         L.A[3 + c] = s * (f * R[3 + c] + t12 * R[6 + c]);
     }
-    L.B[0] = x * y / w2 * f;
-    L.B[1] = -(1. + (x * x / w2)) * f;
-    L.B[2] = y / w * f;
-    L.B[3] = -1. / w * f;
-    L.B[4] = 0.;
-    L.B[5] = x / w2 * f;
-    L.B[6] = (1. + y * y / w2) * f;
-    L.B[7] = -x * y / w2 * f;
-    L.B[8] = -x / w * f;
-    L.B[9] = 0.;
-    L.B[10] = -1. / w * f;
-    L.B[11] = y / w2 * f;
+    svo::project_pose_jacobian(x, y, w, f, f, L.B);
 }
 
 __device__ __forceinline__ void ba_point_blocks(const BaLin &L, double *Hll, double *bl, double *Hpl)
@@ -88,54 +79,6 @@ __device__ __forceinline__ void ba_point_blocks(const BaLin &L, double *Hll, dou
 #pragma unroll
         for (int c = 0; c < 3; c++)
             Hpl[3 * r + c] = B[r] * A[c] + B[6 + r] * A[3 + c];
-}
-
-__device__ __forceinline__ void ba_sym3_inv(const double *Hll, double lambda, double *Vi)
-{
-    const double a = Hll[0] + lambda, b = Hll[1], c = Hll[2], d = Hll[3] + lambda, e = Hll[4], g = Hll[5] + lambda;
-    const double c00 = d * g - e * e, c01 = c * e - b * g, c02 = b * e - c * d;
-    const double det = a * c00 + b * c01 + c * c02;
-    const double id = 1. / det;
-    Vi[0] = c00 * id;
-    Vi[1] = c01 * id;
-    Vi[2] = c02 * id;
-    Vi[3] = (a * g - c * c) * id;
-    Vi[4] = (b * c - a * e) * id;
-    Vi[5] = (a * d - b * b) * id;
-}
-
-// SE3Quat::exp([omega; upsilon]) * (R, t)
-__device__ void ba_se3_exp_mul(const double *d, const double *R, const double *t, double *Rn, double *tn)
-{
-    const double wx = d[0], wy = d[1], wz = d[2];
-    const double th = sqrt(wx * wx + wy * wy + wz * wz);
-    const double O[9] = {0, -wz, wy, wz, 0, -wx, -wy, wx, 0};
-    double O2[9], E[9], V[9];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++)
-            O2[3 * i + j] = O[3 * i] * O[j] + O[3 * i + 1] * O[3 + j] + O[3 * i + 2] * O[6 + j];
-    if (th < 0.00001) {
-        for (int k = 0; k < 9; k++) {
-            E[k] = ((k % 4) == 0 ? 1. : 0.) + O[k] + O2[k];
-            V[k] = E[k];
-        }
-    } else {
-        const double sn = svo_sin(th), cn = svo_cos(th);
-        const double a = sn / th, b = (1. - cn) / (th * th), c = (th - sn) / (th * th * th);
-        for (int k = 0; k < 9; k++) {
-            const double I = (k % 4) == 0 ? 1. : 0.;
-            E[k] = I + a * O[k] + b * O2[k];
-            V[k] = I + b * O[k] + c * O2[k];
-        }
-    }
-    double u[3];
-    for (int i = 0; i < 3; i++)
-        u[i] = V[3 * i] * d[3] + V[3 * i + 1] * d[4] + V[3 * i + 2] * d[5];
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++)
-            Rn[3 * i + j] = E[3 * i] * R[j] + E[3 * i + 1] * R[3 + j] + E[3 * i + 2] * R[6 + j];
-        tn[i] = (E[3 * i] * t[0] + E[3 * i + 1] * t[1] + E[3 * i + 2] * t[2]) + u[i];
-    }
 }
 
 struct BaResult {  // device -> host record
@@ -167,7 +110,8 @@ __global__ __launch_bounds__(BA_T) void ba_3d2d_kernel(BaArgs a)
         for (int c = 0; c < 3; c++)
             X[3 * i + c] = (double)a.pts3d[3 * i + c];
     // a thread only ever reads the X / Xn entries it wrote itself: no barrier is needed for them
-    double lambda = 0, ni = 2, chi_first = 0, chi_last = 0;
+    ba_window_plan::LmState st;
+    double chi_first = 0, chi_last = 0;
     int it_run = 0, trials_total = 0;
     for (int it = 0; it < a.iterations; it++) {
         // ---- computeActiveErrors ----
@@ -178,9 +122,9 @@ __global__ __launch_bounds__(BA_T) void ba_3d2d_kernel(BaArgs a)
             c1[0] += e[0] * e[0] + e[1] * e[1];
         }
         svo::block_sum<1>(c1, s_red);
-        const double chi = c1[0];
+        st.chi = c1[0];  // the rule measures a trial against THIS value, recomputed, not the one it carried over
         if (it == 0)
-            chi_first = chi_last = chi;
+            chi_first = chi_last = st.chi;
         // ---- buildSystem: Hpp, bp ----
         double acc[27], md = 0;
 #pragma unroll
@@ -221,13 +165,13 @@ __global__ __launch_bounds__(BA_T) void ba_3d2d_kernel(BaArgs a)
             double maxdiag = svo::block_max(md, s_red);
             for (int r = 0; r < 6; r++)
                 maxdiag = fmax(maxdiag, fabs(Hpp[7 * r]));
-            lambda = 1e-5 * maxdiag;
-            ni = 2;
+            st.lambda = ba_window_plan::lambda_init(maxdiag);
+            st.ni = 2;
         }
-        double rho = 0;
-        int qmax = 0;
+        st.qmax = 0;
         bool bad = false;
         do {
+            const double lambda = st.lambda;
             // ---- pass 1: Schur complement onto the pose ----
 #pragma unroll
             for (int k = 0; k < 27; k++)
@@ -237,14 +181,8 @@ __global__ __launch_bounds__(BA_T) void ba_3d2d_kernel(BaArgs a)
                 double Hll[6], bl[3], Hpl[18], Vi[6], Y[18];
                 ba_linearize(R, t, X + 3 * i, z[i].x, z[i].y, f, cx, cy, L);
                 ba_point_blocks(L, Hll, bl, Hpl);
-                ba_sym3_inv(Hll, lambda, Vi);
-#pragma unroll
-                for (int r = 0; r < 6; r++) {
-                    const double *h = Hpl + 3 * r;
-                    Y[3 * r] = h[0] * Vi[0] + h[1] * Vi[1] + h[2] * Vi[2];
-                    Y[3 * r + 1] = h[0] * Vi[1] + h[1] * Vi[3] + h[2] * Vi[4];
-                    Y[3 * r + 2] = h[0] * Vi[2] + h[1] * Vi[4] + h[2] * Vi[5];
-                }
+                svo::sym3_inv_damped(Hll, lambda, Vi);
+                svo::sym3_mul_rows6(Hpl, Vi, Y);
                 int k = 0;
 #pragma unroll
                 for (int r = 0; r < 6; r++)
@@ -272,9 +210,9 @@ __global__ __launch_bounds__(BA_T) void ba_3d2d_kernel(BaArgs a)
                     bs[r] = bp[r] - acc[21 + r];
             }
             const bool ok2 = svo::chol6_solve(S, bs, dp);  // wave-uniform
-            double Rn[9], tn[3], tempChi, scale = 0;
+            double Rn[9], tn[3], tempChi = 0, scale = 0;  // tempChi: lm_trial does not read it after a failed solve
             if (ok2) {
-                ba_se3_exp_mul(dp, R, t, Rn, tn);
+                svo::se3_exp_mul(dp, R, t, Rn, tn);
                 // ---- pass 2: points' back-substitution, trial estimates, new error, scale ----
                 double c2[2] = {0, 0};
                 for (int i = tid; i < n; i += BA_T) {
@@ -282,7 +220,7 @@ __global__ __launch_bounds__(BA_T) void ba_3d2d_kernel(BaArgs a)
                     double Hll[6], bl[3], Hpl[18], Vi[6], r3[3], dl[3], e[2], xn[3];
                     ba_linearize(R, t, X + 3 * i, z[i].x, z[i].y, f, cx, cy, L);
                     ba_point_blocks(L, Hll, bl, Hpl);
-                    ba_sym3_inv(Hll, lambda, Vi);
+                    svo::sym3_inv_damped(Hll, lambda, Vi);
 #pragma unroll
                     for (int c = 0; c < 3; c++) {
                         double s = 0;
@@ -291,9 +229,7 @@ __global__ __launch_bounds__(BA_T) void ba_3d2d_kernel(BaArgs a)
                             s += Hpl[3 * r + c] * dp[r];
                         r3[c] = bl[c] - s;
                     }
-                    dl[0] = Vi[0] * r3[0] + Vi[1] * r3[1] + Vi[2] * r3[2];
-                    dl[1] = Vi[1] * r3[0] + Vi[3] * r3[1] + Vi[4] * r3[2];
-                    dl[2] = Vi[2] * r3[0] + Vi[4] * r3[1] + Vi[5] * r3[2];
+                    svo::sym3_mul_vec(Vi, r3, dl);
 #pragma unroll
                     for (int c = 0; c < 3; c++) {
                         xn[c] = X[3 * i + c] + dl[c];
@@ -308,20 +244,9 @@ __global__ __launch_bounds__(BA_T) void ba_3d2d_kernel(BaArgs a)
                 tempChi = c2[1];
                 for (int r = 0; r < 6; r++)
                     scale += dp[r] * (lambda * dp[r] + bp[r]);
-            } else {
-                tempChi = 1.7976931348623157e308;
             }
             trials_total++;
-            rho = (chi - tempChi);
-            scale += 1e-3;
-            rho /= scale;
-            if (rho > 0 && isfinite(tempChi) && ok2) {
-                const double q = 2 * rho - 1;
-                double alpha = 1. - q * q * q;
-                alpha = fmin(alpha, 2. / 3.);
-                const double sf = fmax(1. / 3., alpha);
-                lambda *= sf;
-                ni = 2;
+            if (ba_window_plan::lm_trial(st, tempChi, scale, ok2)) {
                 for (int k = 0; k < 9; k++)
                     R[k] = Rn[k];
                 for (int k = 0; k < 3; k++)
@@ -330,18 +255,13 @@ __global__ __launch_bounds__(BA_T) void ba_3d2d_kernel(BaArgs a)
                     for (int c = 0; c < 3; c++)
                         X[3 * i + c] = Xn[3 * i + c];
                 chi_last = tempChi;
-            } else {
-                lambda *= ni;
-                ni *= 2;
-                if (!isfinite(lambda)) {
-                    bad = true;
-                    break;
-                }
+            } else if (!isfinite(st.lambda)) {
+                bad = true;
+                break;
             }
-            qmax++;
-        } while (rho < 0 && qmax < 10);
+        } while (st.rho < 0 && st.qmax < 10);
         it_run = it + 1;
-        if (qmax == 10 || rho == 0 || bad)
+        if (st.qmax == 10 || st.rho == 0 || bad)
             break;  // OptimizationAlgorithm::Terminate
     }
     if (tid == 0) {
@@ -351,7 +271,7 @@ __global__ __launch_bounds__(BA_T) void ba_3d2d_kernel(BaArgs a)
             a.out->R[k] = R[k];
         a.out->info[0] = chi_first;
         a.out->info[1] = chi_last;
-        a.out->info[2] = lambda;
+        a.out->info[2] = st.lambda;
         a.out->info[3] = it_run;
         a.out->info[4] = trials_total;
     }

@@ -28,6 +28,7 @@
 // per pass otherwise); 2 by the slab traffic (slabs x stride x 8 B, L2-resident); 3 by LDS latency and barriers of one workgroup
 // (about 3 x dim barriers); the trial as a whole by five launches and one host wait.
 #include "ba_window_plan.hip.h"
+#include "se3_solve.hip.h"
 #include "svo_internal.h"
 #include "wave_ops.hip.h"
 
@@ -93,24 +94,14 @@ __device__ __forceinline__ void bw_linearize(const double *P, const double *X, f
     bw_robust(L.e[0] * L.e[0] + L.e[1] * L.e[1] + L.e[2] * L.e[2], stereo ? c.huber_stereo : c.huber_mono, L.rho, L.w);
     const double x = xc[0], y = xc[1], z = xc[2], z2 = z * z;
     const double bfz2 = stereo ? c.bf / z2 : 0.;
+    // NOT shared with ba_linearize's A: the two round differently, each pinned to its own checker -- do not unify
 #pragma unroll
     for (int k = 0; k < 3; k++) {
         L.A[k] = -c.fx * P[k] / z + c.fx * x * P[6 + k] / z2;
         L.A[3 + k] = -c.fy * P[3 + k] / z + c.fy * y * P[6 + k] / z2;
         L.A[6 + k] = stereo ? L.A[k] - bfz2 * P[6 + k] : 0.;
     }
-    L.B[0] = x * y / z2 * c.fx;
-    L.B[1] = -(1. + (x * x / z2)) * c.fx;
-    L.B[2] = y / z * c.fx;
-    L.B[3] = -1. / z * c.fx;
-    L.B[4] = 0.;
-    L.B[5] = x / z2 * c.fx;
-    L.B[6] = (1. + y * y / z2) * c.fy;
-    L.B[7] = -x * y / z2 * c.fy;
-    L.B[8] = -x / z * c.fy;
-    L.B[9] = 0.;
-    L.B[10] = -1. / z * c.fy;
-    L.B[11] = y / z2 * c.fy;
+    svo::project_pose_jacobian(x, y, z, c.fx, c.fy, L.B);
     L.B[12] = stereo ? L.B[0] - bfz2 * y : 0.;
     L.B[13] = stereo ? L.B[1] + bfz2 * x : 0.;
     L.B[14] = stereo ? L.B[2] : 0.;
@@ -142,52 +133,6 @@ __device__ __forceinline__ void bw_coupling(const BwLin &L, double *Hpl)
 #pragma unroll
         for (int k = 0; k < 3; k++)
             Hpl[3 * r + k] = L.w * (L.B[r] * L.A[k] + L.B[6 + r] * L.A[3 + k] + L.B[12 + r] * L.A[6 + k]);
-}
-
-__device__ __forceinline__ void bw_sym3_inv(const double *Hll, double lambda, double *Vi)
-{
-    const double a = Hll[0] + lambda, b = Hll[1], c = Hll[2], d = Hll[3] + lambda, e = Hll[4], g = Hll[5] + lambda;
-    const double c00 = d * g - e * e, c01 = c * e - b * g, c02 = b * e - c * d;
-    const double det = a * c00 + b * c01 + c * c02;
-    const double id = 1. / det;
-    Vi[0] = c00 * id;
-    Vi[1] = c01 * id;
-    Vi[2] = c02 * id;
-    Vi[3] = (a * g - c * c) * id;
-    Vi[4] = (b * c - a * e) * id;
-    Vi[5] = (a * d - b * b) * id;
-}
-
-// SE3Quat::exp([omega; upsilon]) * (R, t) on poses stored R9 | t3
-__device__ void bw_se3_exp_mul(const double *d, const double *P, double *Pn)
-{
-    const double wx = d[0], wy = d[1], wz = d[2];
-    const double th = sqrt(wx * wx + wy * wy + wz * wz);
-    const double O[9] = {0, -wz, wy, wz, 0, -wx, -wy, wx, 0};
-    double O2[9], E[9], V[9];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++)
-            O2[3 * i + j] = O[3 * i] * O[j] + O[3 * i + 1] * O[3 + j] + O[3 * i + 2] * O[6 + j];
-    if (th < 0.00001) {
-        for (int k = 0; k < 9; k++) {
-            E[k] = ((k % 4) == 0 ? 1. : 0.) + O[k] + O2[k];
-            V[k] = E[k];
-        }
-    } else {
-        const double sn = svo_sin(th), cn = svo_cos(th);
-        const double a = sn / th, b = (1. - cn) / (th * th), c = (th - sn) / (th * th * th);
-        for (int k = 0; k < 9; k++) {
-            const double I = (k % 4) == 0 ? 1. : 0.;
-            E[k] = I + a * O[k] + b * O2[k];
-            V[k] = I + b * O[k] + c * O2[k];
-        }
-    }
-    for (int i = 0; i < 3; i++) {
-        const double u = V[3 * i] * d[3] + V[3 * i + 1] * d[4] + V[3 * i + 2] * d[5];
-        for (int j = 0; j < 3; j++)
-            Pn[3 * i + j] = E[3 * i] * P[j] + E[3 * i + 1] * P[3 + j] + E[3 * i + 2] * P[6 + j];
-        Pn[9 + i] = (E[3 * i] * P[9] + E[3 * i + 1] * P[10] + E[3 * i + 2] * P[11]) + u;
-    }
 }
 
 // device -> host record of one trial (and of the first look at the problem)
@@ -275,20 +220,16 @@ __global__ __launch_bounds__(64) void bw_schur_kernel(BwProblem q, const double 
         md = fmax(md, fmax(Hll[0], fmax(Hll[3], Hll[5])));
         double Vi[6] = {0, 0, 0, 0, 0, 0};
         if (SCHUR)
-            bw_sym3_inv(Hll, lambda, Vi);
+            svo::sym3_inv_damped(Hll, lambda, Vi);
         if (active && f >= 0) {
             if (SCHUR) {
-                double Hpl[18];
+                double Hpl[18], Y[18];
                 bw_coupling(L, Hpl);
+                svo::sym3_mul_rows6(Hpl, Vi, Y);
 #pragma unroll
-                for (int r = 0; r < 6; r++) {
-                    const double *h = Hpl + 3 * r;
-                    s_W[lane * 18 + 3 * r] = h[0];
-                    s_W[lane * 18 + 3 * r + 1] = h[1];
-                    s_W[lane * 18 + 3 * r + 2] = h[2];
-                    s_Y[lane * 18 + 3 * r] = h[0] * Vi[0] + h[1] * Vi[1] + h[2] * Vi[2];
-                    s_Y[lane * 18 + 3 * r + 1] = h[0] * Vi[1] + h[1] * Vi[3] + h[2] * Vi[4];
-                    s_Y[lane * 18 + 3 * r + 2] = h[0] * Vi[2] + h[1] * Vi[4] + h[2] * Vi[5];
+                for (int k = 0; k < 18; k++) {
+                    s_W[lane * 18 + k] = Hpl[k];
+                    s_Y[lane * 18 + k] = Y[k];
                 }
             }
             // the pose's own block: no other lane of this point holds the same pose
@@ -433,7 +374,7 @@ __global__ __launch_bounds__(256) void bw_solve_kernel(BwProblem q, const double
             d[k] = s_b[6 * tid + k];
         for (int k = 0; k < 12; k++)
             P[k] = poses[12 * j + k];
-        bw_se3_exp_mul(d, P, Pn);
+        svo::se3_exp_mul(d, P, P + 9, Pn, Pn + 9);
         for (int k = 0; k < 12; k++)
             trial[12 * j + k] = Pn[k];
     }
@@ -500,13 +441,11 @@ __global__ __launch_bounds__(plan::BLOCK) void bw_backsub_kernel(BwProblem q, co
                 }
             }
             double Vi[6], r3[3], dl[3];
-            bw_sym3_inv(Hll, lambda, Vi);
+            svo::sym3_inv_damped(Hll, lambda, Vi);
 #pragma unroll
             for (int k = 0; k < 3; k++)
                 r3[k] = bl[k] - hd[k];
-            dl[0] = Vi[0] * r3[0] + Vi[1] * r3[1] + Vi[2] * r3[2];
-            dl[1] = Vi[1] * r3[0] + Vi[3] * r3[1] + Vi[4] * r3[2];
-            dl[2] = Vi[2] * r3[0] + Vi[4] * r3[1] + Vi[5] * r3[2];
+            svo::sym3_mul_vec(Vi, r3, dl);
 #pragma unroll
             for (int k = 0; k < 3; k++) {
                 xn[k] = Xp[k] + dl[k];

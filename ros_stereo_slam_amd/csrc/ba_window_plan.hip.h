@@ -1,7 +1,8 @@
 // ba_window_plan.hip.h -- the host arithmetic of ba_window.hip with nothing of HIP in it: the refusals of svo_ba_window (the CSR
 // validation included), the numbering of the free poses, the slab geometry and buffer sizes, the packed upper-triangle index and
-// the Levenberg-Marquardt accept / reject rule the host applies once per trial.  ba_window.hip includes it; so does
-// tests/cpp/ba_window_plan_check.cpp, a stand-alone program that runs it under the address and undefined-behaviour sanitizers.
+// the Levenberg-Marquardt accept / reject rule, which the host applies once per trial and ba.hip's ba_3d2d_kernel on the device
+// (the one piece marked for both under hipcc).  ba_window.hip and ba.hip include it; so does tests/cpp/ba_window_plan_check.cpp, a
+// stand-alone program that runs it under the address and undefined-behaviour sanitizers.
 #pragma once
 
 #include <cmath>
@@ -9,6 +10,12 @@
 #include <cstdint>
 
 #include "../../include/svo.h"
+
+#if defined(__HIPCC__)  // as SVO_MATH_FN of include/svo_math.h
+#define BA_PLAN_FN __host__ __device__ inline
+#else
+#define BA_PLAN_FN inline
+#endif
 
 namespace ba_window_plan {
 
@@ -134,17 +141,17 @@ inline const char *check_starts(int n_points, const int *obs_start)
     return nullptr;
 }
 
-// ---- g2o's OptimizationAlgorithmLevenberg, one trial's decision -----------------------------------------------------------------
+// ---- g2o's OptimizationAlgorithmLevenberg, one trial's decision: svo_ba_window's host loop and ba_3d2d_kernel ----------------------
 struct LmState {
     double lambda = 0, ni = 2, chi = 0;   // chi: of the accepted estimate
     double rho = 0;
     int qmax = 0;
 };
 // computeLambdaInit: tau * max |diag H| over pose and point blocks
-inline double lambda_init(double max_diag) { return 1e-5 * max_diag; }
+BA_PLAN_FN double lambda_init(double max_diag) { return 1e-5 * max_diag; }
 // temp_chi / scale: the trial's chi2 and the sum dx (lambda dx + b) over every unknown; solved: the factorisation succeeded.
 // Returns true when the trial is accepted.  The caller stops the trials of an iteration when !(rho < 0 && qmax < 10).
-inline bool lm_trial(LmState &s, double temp_chi, double scale, bool solved)
+BA_PLAN_FN bool lm_trial(LmState &s, double temp_chi, double scale, bool solved)
 {
     if (!solved)
         temp_chi = 1.7976931348623157e308;   // g2o: a failed solve is the largest chi2

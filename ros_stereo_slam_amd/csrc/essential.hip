@@ -751,33 +751,6 @@ __device__ __forceinline__ float em_error(const double (&E)[9], double x1, doubl
     return (float)(d * d / (ex0 * ex0 + ex1 * ex1 + et0 * et0 + et1 * et1));
 }
 
-// the plain 5-sample of RANSAC iteration `it` (pnp.hip's draw; orc_draw_subset_plain in the checker); false: no sample
-__device__ __forceinline__ bool draw_plain(uint64_t seed, int it, int n, int (&idx)[MP])
-{
-    uint32_t draw = 0;
-    int guard = 0;
-    bool filled = true;
-#pragma unroll
-    for (int slot = 0; slot < MP; slot++) {
-        int v = 0;
-        bool got = false;
-        while (!got && guard < kMaxDraws) {
-            v = (int)(rng_u32(seed, (uint32_t)it, draw++) % (uint32_t)n);
-            guard++;
-            bool dup = false;
-#pragma unroll
-            for (int j = 0; j < MP; j++)
-                if (j < slot && idx[j] == v)
-                    dup = true;
-            got = !dup;
-        }
-        if (!got)
-            filled = false;
-        idx[slot] = v;
-    }
-    return filled;
-}
-
 struct EmJob {
     const float *p1, *p2;   // pixels, n pairs
     double2 *q1, *q2;       // normalised (workspace)
@@ -830,7 +803,8 @@ __global__ __launch_bounds__(256) void em_iter_kernel(EmBatch b, uint64_t seed, 
     for (int it = it0 + (int)blockIdx.x; it < lim; it += gridDim.x) {
         if (wave == 0) {
             int idx[MP] = {0, 1, 2, 3, 4};
-            const bool ok = n == MP || draw_plain(seed, it, n, idx);
+            uint32_t draw = 0;
+            const bool ok = n == MP || draw_distinct(seed, it, n, draw, idx);
             const int nm = ok ? em_solve_wave(q1, q2, idx, S, lane) : -1;
             if (lane == 0) {
                 S.nsol = nm;

@@ -171,27 +171,7 @@ __device__ int fr_solve_wave(const float *__restrict__ p1, const float *__restri
     for (int slot = 0; slot < M; slot++)
         idx[slot] = slot;
     for (int attempt = 0; attempt < kMaxAttempts && !ok; attempt++) {
-        int guard = 0;
-        bool filled = true;
-#pragma unroll
-        for (int slot = 0; slot < M; slot++) {
-            int v = 0;
-            bool got = false;
-            while (!got && guard < kMaxDraws) {
-                v = (int)(rng_u32(seed, (uint32_t)it, draw++) % (uint32_t)n);
-                guard++;
-                bool dup = false;
-#pragma unroll
-                for (int j = 0; j < M; j++)
-                    if (j < slot && idx[j] == v)
-                        dup = true;
-                got = !dup;
-            }
-            if (!got)
-                filled = false;
-            idx[slot] = v;
-        }
-        if (!filled)
+        if (!draw_distinct(seed, it, n, draw, idx))
             break;
         ok = !collinear_last(p1, idx) && !collinear_last(p2, idx);
     }

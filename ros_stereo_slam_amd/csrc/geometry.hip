@@ -19,10 +19,6 @@ using svo::smallest_right_singular_vector4;
 
 namespace {
 
-struct Mat34 {
-    double m[12];
-};
-
 struct TriJob {
     const float2 *x1, *x2;
     int n_host;

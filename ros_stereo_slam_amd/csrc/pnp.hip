@@ -353,30 +353,8 @@ __device__ __forceinline__ void pnp_hypothesis(const PnpJob &job, int it, int n,
     }
     // ---- sample (every lane draws the same indices) ----
     int idx[MP];
-    bool filled = true;
-    {
-        uint32_t draw = 0;
-        int guard = 0;
-#pragma unroll
-        for (int slot = 0; slot < MP; slot++) {
-            int v = 0;
-            bool got = false;
-            while (!got && guard < kMaxDraws) {
-                v = (int)(rng_u32(seed, (uint32_t)it, draw++) % (uint32_t)n);
-                guard++;
-                bool dup = false;
-#pragma unroll
-                for (int j = 0; j < MP; j++)
-                    if (j < slot && idx[j] == v)
-                        dup = true;
-                got = !dup;
-            }
-            if (!got)
-                filled = false;
-            idx[slot] = v;
-        }
-    }
-    if (!filled) {
+    uint32_t draw = 0;
+    if (!draw_distinct(seed, it, n, draw, idx)) {
         if (lane == 0)
             nmodels[it] = -1;
         if (lane == 0)

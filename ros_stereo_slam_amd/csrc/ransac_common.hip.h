@@ -1,4 +1,6 @@
-// ransac_common.hip.h -- device helpers shared by the F-matrix and PnP RANSAC kernels.
+// ransac_common.hip.h -- device helpers shared by the three RANSAC kernel files: fransac.hip (F matrix, 7-point samples),
+// pnp.hip (PnP, 5) and essential.hip (E matrix, 5): the counter-based generator, the draw of a sample, the iteration bound and
+// the replay of the sequential loop.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,6 +26,35 @@ __host__ __device__ __forceinline__ uint32_t rng_u32(uint64_t seed, uint32_t ite
 
 constexpr int kMaxAttempts = 8;
 constexpr int kMaxDraws = 64;
+
+// A sample of M distinct indices below n for RANSAC iteration `it` (orc_draw_subset_plain in the checker):
+// slot by slot, a value that an earlier slot holds is drawn again; at most kMaxDraws draws per call.  false: a slot could not be
+// filled.  The caller owns the draw counter: pnp_hypothesis and em_iter_kernel start it at 0, fr_solve_wave carries it on across
+// its kMaxAttempts re-draws of a degenerate sample.
+template <int M> __device__ __forceinline__ bool draw_distinct(uint64_t seed, int it, int n, uint32_t &draw, int (&idx)[M])
+{
+    int guard = 0;
+    bool filled = true;
+#pragma unroll
+    for (int slot = 0; slot < M; slot++) {
+        int v = 0;
+        bool got = false;
+        while (!got && guard < kMaxDraws) {
+            v = (int)(rng_u32(seed, (uint32_t)it, draw++) % (uint32_t)n);
+            guard++;
+            bool dup = false;
+#pragma unroll
+            for (int j = 0; j < M; j++)
+                if (j < slot && idx[j] == v)
+                    dup = true;
+            got = !dup;
+        }
+        if (!got)
+            filled = false;
+        idx[slot] = v;
+    }
+    return filled;
+}
 
 // cv RANSACUpdateNumIters
 __device__ __forceinline__ int update_num_iters(double p, double ep, int model_points, int max_iters)

@@ -20,10 +20,6 @@ namespace {
 
 using namespace replenish_plan;
 
-struct Mat34 {
-    double m[12];
-};
-
 // what a lane tests reference points against: BOX keeps the four limits, DISC the point and the radius
 struct Probe {
     double xl, xh, yl, yh;   // BOX: qx - r, qx + r, qy - r, qy + r in double
@@ -152,6 +148,7 @@ __global__ __launch_bounds__(64) void append_kernel(Mat34 Rt, const uint8_t *__r
     }
 }
 
+// p is never null (check_replenish refuses it); geometry.hip's to_mat34 differs: there null means "no transform", all zeros
 Mat34 to_mat34(const double *p)
 {
     Mat34 m;

@@ -59,6 +59,11 @@ struct PyrDev {
     int c;
 };
 
+// a 3 x 4 double matrix ([R|t], a projection) passed to kernels by value: geometry.hip, replenish.hip
+struct Mat34 {
+    double m[12];
+};
+
 // Two device words per pyramid live in a header of SVO_PYR_HEADER bytes in front of level 0's padded buffer, i.e. at
 // lvl[0] - PAD * pitch[0] - PAD * c - SVO_PYR_HEADER: whoever holds the PyrDev finds them, no pointer of their own.
 //   SVO_PYR_MONO         1: the image the pyramid was last built from has B == G == R in every pixel (c == 3 only;
