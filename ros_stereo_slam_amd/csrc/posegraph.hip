@@ -19,17 +19,30 @@
 //              in parallel (one wavefront each), a dense Schur complement on the separators
 //              (loop-closure endpoints + every 128th vertex), back-substitution -- see below;
 //   update     one thread per vertex: X <- X * fromVectorMQT(dx).
+//
+// The host logic is in two headers with nothing of HIP in them, each run on its own under the host sanitizers: the
+// elimination structure of the solve (pg_solve_plan.hip.h) and the .g2o reader with the test of an information matrix
+// (pg_g2o.hip.h); the pruning's is in pg_prune_plan.hip.h.
 #include <cmath>
 #include <cstring>
-#include <map>
-#include <utility>
+#include <string>
 #include <vector>
 
+#include "pg_g2o.hip.h"
 #include "pg_prune_plan.hip.h"
+#include "pg_solve_plan.hip.h"
 #include "svo_internal.h"
 #include "wave_ops.hip.h"
 
 namespace {
+
+namespace psp = pg_solve_plan;
+using pg_g2o::pg_tri;
+using pg_g2o::q_normalize;
+using pg_solve_plan::PG_MAX_SEG_CHORDS;
+using pg_solve_plan::PgTerm;
+using pg_solve_plan::SEG_L;
+using pg_solve_plan::TB;
 
 // ---- SE3 with unit quaternions: pose7 = tx ty tz qx qy qz qw -----------------------------------
 __host__ __device__ inline void q_mul(const double *a, const double *b, double *o)
@@ -48,13 +61,6 @@ __host__ __device__ inline void q_rot(const double *q, const double *v, double *
     o[0] = v[0] + 2 * (w * cx + dx);
     o[1] = v[1] + 2 * (w * cy + dy);
     o[2] = v[2] + 2 * (w * cz + dz);
-}
-__host__ __device__ inline void q_normalize(double *q)
-{
-    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    if (n > 0)
-        for (int i = 0; i < 4; i++)
-            q[i] /= n;
 }
 __host__ __device__ inline void se3_mul(const double *A, const double *B, double *O)
 {
@@ -125,13 +131,6 @@ __device__ inline double pg_robust_weight(int kind, double delta, double c, doub
     }
     *rho = r;
     return w;
-}
-
-// Index of entry (i, j), i <= j, of a symmetric 6 x 6 matrix stored as its upper triangle, row-major (g2o's order)
-__host__ __device__ constexpr int pg_tri(int i, int j)
-{
-    const int a = i <= j ? i : j, b = i <= j ? j : i;
-    return 6 * a - a * (a - 1) / 2 + (b - a);
 }
 
 // WEIGHTED = false: identity information, chi2 = e^T e, H = J^T J -- the kernel of every graph that stores no information.
@@ -419,9 +418,7 @@ __global__ __launch_bounds__(128) void pg_edge_eval_kernel(const double *__restr
 //   T x_seg + E_a C_l x_l + E_z C_z^T x_r = r_seg   =>   x_seg = y - Wl x_l - Wr x_r,
 //   y = T^-1 r_seg,  Wl = T^-1 E_a C_l,  Wr = T^-1 E_z C_z^T.
 
-constexpr int PG_MAX_SEG_CHORDS = 8;  // closure endpoints a segment takes inside (six right-hand-side columns each, two to a pass)
-constexpr int SEG_L = 104;  // regular separator spacing (rows): a segment and its 13 right-hand sides live in LDS
-constexpr int TB = 48;      // tile of the dense reduced solve (8 block rows)
+// (PG_MAX_SEG_CHORDS, SEG_L and TB: pg_solve_plan.hip.h)
 
 // A workgroup barrier that orders LDS traffic only.  __syncthreads() on gfx9 also waits for every global load and store of
 // the wave (one counter for both, and a release fence has to wait for the stores): loads asked for early would be drained
@@ -1073,18 +1070,8 @@ __global__ __launch_bounds__(BCR_WAVES * 64) void pg_segment_kernel(int nb, int 
 
 // Reduced (separator) system, assembled by gathers.  Block k of the launch owns one nonzero
 // 6x6 block (rb_row >= rb_col, in separator indices) or, for k >= n_blocks, the right-hand side
-// of separator k - n_blocks.  Sources src[ptr[k] .. ptr[k+1]) are added in list order:
-//   kind 0: + Dg[idx]  (right-hand side: + rneg[idx])        kind 1: + Cc[idx]
-//   kind 2: + Hij of edge idx                                 kind 3: + Hij^T of edge idx
-//   kind 7: - A^T W, term idx of the table: a segment couples to separator u through the block A = H[row_u][u] and to
-//           separator v through W_v = T^-1 E_{row_v} H[row_v][v]; the Schur complement takes A^T W_v[row_u] off the
-//           block (u, v) -- and A^T Y[row_u] off u's right-hand side.
-//           A: 0 Cc[a] (the segment's first row and the separator before it), 1 Cc[a]^T (its last row and the separator
-//              after it), 2 / 3 a closure's Hij / Hij^T (an endpoint inside the segment and the one that is a separator)
-//           W: 0 Wl, 1 Wr, 2 Wc (6 x 6 block w), 3 Y (6-vector w)
-struct PgTerm {
-    int a_kind, a, w_kind, w;
-};
+// of separator k - n_blocks.  Sources src[ptr[k] .. ptr[k+1]) = (kind, idx) are added in list order; the kinds, and those of a
+// term's A and W, are the enums of pg_solve_plan.hip.h, which builds the lists.
 __global__ __launch_bounds__(64) void pg_reduce_kernel(int n_blocks, int m, const int *__restrict__ rb_row,
                                                        const int *__restrict__ rb_col, const int *__restrict__ ptr,
                                                        const int2 *__restrict__ src, const PgTerm *__restrict__ terms,
@@ -1095,9 +1082,9 @@ __global__ __launch_bounds__(64) void pg_reduce_kernel(int n_blocks, int m, cons
                                                        double *__restrict__ R, int ldr, double *__restrict__ rR)
 {
     const int k = blockIdx.x, lane = threadIdx.x;
-    // A^T[p][t] = H[t][p] of a term = base[sa * t + sb * p]
+    // A^T[p][t] = H[t][p] of a term = base[sa * t + sb * p]; the kinds below A_HIJ read Cc, the odd ones are the transposes
     auto a_of = [&](const PgTerm &tm, const double *&base, int &sa, int &sb) {
-        base = tm.a_kind < 2 ? Cc + (size_t)tm.a * 36 : eo + (size_t)tm.a * EO_FIELDS + EO_HIJ;
+        base = tm.a_kind < psp::A_HIJ ? Cc + (size_t)tm.a * 36 : eo + (size_t)tm.a * EO_FIELDS + EO_HIJ;
         sa = (tm.a_kind & 1) ? 1 : 6;
         sb = (tm.a_kind & 1) ? 6 : 1;
     };
@@ -1110,13 +1097,13 @@ __global__ __launch_bounds__(64) void pg_reduce_kernel(int n_blocks, int m, cons
             const int kind = src[t].x, idx = src[t].y;
             double v = 0;
             switch (kind) {
-            case 0: v = Dg[(size_t)idx * 36 + lane]; break;
-            case 1: v = Cc[(size_t)idx * 36 + lane]; break;
-            case 2: v = eo[(size_t)idx * EO_FIELDS + EO_HIJ + lane]; break;
-            case 3: v = eo[(size_t)idx * EO_FIELDS + EO_HIJ + 6 * q + p]; break;
-            default: {
+            case psp::SRC_DG: v = Dg[(size_t)idx * 36 + lane]; break;
+            case psp::SRC_CC: v = Cc[(size_t)idx * 36 + lane]; break;
+            case psp::SRC_HIJ: v = eo[(size_t)idx * EO_FIELDS + EO_HIJ + lane]; break;
+            case psp::SRC_HIJ_T: v = eo[(size_t)idx * EO_FIELDS + EO_HIJ + 6 * q + p]; break;
+            default: {  // SRC_TERM
                 const PgTerm tm = terms[idx];
-                const double *W = (tm.w_kind == 0 ? Wl : tm.w_kind == 1 ? Wr : Wc) + (size_t)tm.w * 36, *A;
+                const double *W = (tm.w_kind == psp::W_L ? Wl : tm.w_kind == psp::W_R ? Wr : Wc) + (size_t)tm.w * 36, *A;
                 int sa, sb;
                 a_of(tm, A, sa, sb);
                 for (int t2 = 0; t2 < 6; t2++)
@@ -1137,9 +1124,9 @@ __global__ __launch_bounds__(64) void pg_reduce_kernel(int n_blocks, int m, cons
         for (int t = ptr[kk]; t < ptr[kk + 1]; t++) {
             const int kind = src[t].x, idx = src[t].y;
             double v = 0;
-            if (kind == 0)
+            if (kind == psp::SRC_DG)
                 v = rneg[(size_t)idx * 6 + lane];
-            else {
+            else {  // SRC_TERM, W_Y
                 const PgTerm tm = terms[idx];
                 const double *A;
                 int sa, sb;
@@ -1691,11 +1678,11 @@ __global__ __launch_bounds__(PG_UPD_ROWS * 6) void pg_backsub_update_kernel(int 
                                                                             const int *__restrict__ cwbase,
                                                                             const double *__restrict__ Wc,
                                                                             double *__restrict__ pose,
-                                                                            const double *__restrict__ dx_add,
-                                                                            double *__restrict__ dx_out)
+                                                                            const double *dx_add, double *dx_out)
 {
     // iterative refinement (svo_pg_set_refinement): a first pass leaves its dx in dx_out and does not touch the poses; the
-    // pass over the residual adds the first pass's dx (dx_add) and applies the sum
+    // pass over the residual adds the first pass's dx (dx_add) and applies the sum.  With two or more passes the middle ones
+    // accumulate in place, dx_add == dx_out (each thread reads its entry before it writes it): neither is __restrict__.
     __shared__ double s_dx[PG_UPD_ROWS * 6];
     const int t = blockIdx.x * (PG_UPD_ROWS * 6) + threadIdx.x;
     const int b = t / 6, r = t - 6 * b;
@@ -1851,14 +1838,10 @@ struct svo_posegraph {
     // does not depend on the information and is not rebuilt for it.
     int dev_ninfo = 0;
     // The elimination structure (separators, segments, gather lists) of the graph as last built; reused
-    // as long as no vertex or edge was added.  The host copies stay alive here so that their uploads
+    // as long as no vertex or edge was added.  The host copies (the plan's vectors) stay alive here so that their uploads
     // need no synchronisation of their own.
     int built_nv = -1, built_ne = -1;
-    std::vector<int> h_incptr, h_inc, h_struct;
-    int s_m = 0, s_nseg = 0, s_nrblocks = 0, s_T = 0, s_ldr = 0, s_maxseg = 0;
-    size_t s_wc_blocks = 0;
-    size_t o_seg_start = 0, o_seg_len = 0, o_sepidx = 0, o_lsep = 0, o_rsep = 0, o_rb_row = 0, o_rb_col = 0, o_rptr = 0,
-           o_rsrc = 0, o_rowseg = 0, o_cptr = 0, o_clrow = 0, o_cedge = 0, o_ctr = 0, o_cwbase = 0, o_csep = 0, o_terms = 0;
+    pg_solve_plan::Plan plan;
     DevBuf d_rkind, d_rdelta, d_eval;
     DevBuf d_pose, d_from, d_to, d_meas, d_info, d_eo, d_incptr, d_inc, d_struct, d_Dg, d_Cc, d_rneg, d_Y,
         d_Wl, d_Wr, d_Wc, d_R, d_Lo, d_Tinv, d_rR, d_xR, d_misc, d_dx, d_res;
@@ -1866,8 +1849,6 @@ struct svo_posegraph {
     int nv() const { return (int)(pose.size() / 7); }
     int ne() const { return (int)efrom.size(); }
 };
-
-static const double PG_INFO_IDENTITY[21] = {1, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 1, 0, 1};
 
 static void pg_drop_info(svo_posegraph *g)
 {
@@ -1877,47 +1858,31 @@ static void pg_drop_info(svo_posegraph *g)
     g->dev_ninfo = 0;
 }
 
-// A usable information matrix is finite and positive definite (host 6 x 6 Cholesky: every pivot > 0); `what` names the edge
+// A usable information matrix is finite and positive definite (pg_g2o::check_info); `what` names the edge
 static int pg_check_info(const double *info21, const char *what, int e)
 {
-    for (int k = 0; k < 21; k++)
-        if (!std::isfinite(info21[k])) {
-            svo_set_error("pose graph: %s %d: information entry %d is not finite", what, e, k);
-            return SVO_ERR_ARG;
-        }
-    double L[36];
-    for (int i = 0; i < 6; i++)
-        for (int j = 0; j <= i; j++) {
-            double v = info21[pg_tri(j, i)];
-            for (int k = 0; k < j; k++)
-                v -= L[6 * i + k] * L[6 * j + k];
-            if (i == j) {
-                if (!(v > 0)) {
-                    svo_set_error("pose graph: %s %d: information matrix is not positive definite (pivot %d = %g)", what, e, i, v);
-                    return SVO_ERR_ARG;
-                }
-                L[6 * i + i] = sqrt(v);
-            } else
-                L[6 * i + j] = v / L[6 * j + j];
-        }
-    return SVO_OK;
+    const std::string why = pg_g2o::check_info(info21, what, e);
+    if (why.empty())
+        return SVO_OK;
+    svo_set_error("%s", why.c_str());
+    return SVO_ERR_ARG;
 }
 
 // Stores the (checked) information of edge e; NULL or the exact identity = none.  The edge must exist.
 static void pg_store_info(svo_posegraph *g, int e, const double *info21)
 {
-    const bool none = !info21 || !memcmp(info21, PG_INFO_IDENTITY, sizeof(PG_INFO_IDENTITY));
+    const bool none = !info21 || !memcmp(info21, pg_g2o::INFO_IDENTITY, sizeof(pg_g2o::INFO_IDENTITY));
     if (g->info.empty()) {
         if (none)
             return;
         g->has_info.assign(g->ne(), 0);
         g->info.resize((size_t)21 * g->ne());
         for (int k = 0; k < g->ne(); k++)
-            memcpy(&g->info[(size_t)21 * k], PG_INFO_IDENTITY, sizeof(PG_INFO_IDENTITY));
+            memcpy(&g->info[(size_t)21 * k], pg_g2o::INFO_IDENTITY, sizeof(pg_g2o::INFO_IDENTITY));
     }
     g->n_info += (none ? 0 : 1) - (g->has_info[e] ? 1 : 0);
     g->has_info[e] = none ? 0 : 1;
-    memcpy(&g->info[(size_t)21 * e], none ? PG_INFO_IDENTITY : info21, sizeof(PG_INFO_IDENTITY));
+    memcpy(&g->info[(size_t)21 * e], none ? pg_g2o::INFO_IDENTITY : info21, sizeof(pg_g2o::INFO_IDENTITY));
     if (g->n_info == 0)
         pg_drop_info(g);  // all identity again: back to the identity kernel
     else if (e < g->dev_ninfo)
@@ -1929,7 +1894,7 @@ static void pg_append_info(svo_posegraph *g, const double *info21)
 {
     if (!g->info.empty()) {
         g->has_info.push_back(0);
-        g->info.insert(g->info.end(), PG_INFO_IDENTITY, PG_INFO_IDENTITY + 21);
+        g->info.insert(g->info.end(), pg_g2o::INFO_IDENTITY, pg_g2o::INFO_IDENTITY + 21);
     }
     pg_store_info(g, g->ne() - 1, info21);
 }
@@ -2169,7 +2134,7 @@ int svo_pg_set_edge_information(svo_posegraph *g, int e, const double *info21)
 int svo_pg_get_edge_information(const svo_posegraph *g, int e, double *info21)
 {
     SVO_CHECK_ARG(g && e >= 0 && e < g->ne() && info21);
-    memcpy(info21, g->info.empty() ? PG_INFO_IDENTITY : &g->info[(size_t)21 * e], sizeof(PG_INFO_IDENTITY));
+    memcpy(info21, g->info.empty() ? pg_g2o::INFO_IDENTITY : &g->info[(size_t)21 * e], sizeof(pg_g2o::INFO_IDENTITY));
     return SVO_OK;
 }
 
@@ -2227,265 +2192,20 @@ int svo_pg_optimize(svo_posegraph *g, int iters, double *chi2)
                 chi2[i] = 0;
         return SVO_OK;
     }
-    // ---- structure (host): incidence lists, separators, segments, gather lists; rebuilt only when the
-    // graph grew since the last solve ----
+    // ---- structure (host, pg_solve_plan.hip.h): incidence lists, separators, segments, gather lists; rebuilt only when the
+    // graph grew since the last solve.  SVO_PG_COVER=1 / 0 forces the cover / both ends (the tests run both).
     const bool rebuild = g->built_nv != nv || g->built_ne != ne;
     if (rebuild) {
-        std::vector<int> &incptr = g->h_incptr, &inc = g->h_inc, &hs = g->h_struct;
-        incptr.assign(nv + 1, 0);
-        inc.assign(2 * (size_t)ne, 0);
-        for (int e = 0; e < ne; e++) {
-            incptr[g->efrom[e] + 1]++;
-            incptr[g->eto[e] + 1]++;
-        }
-        for (int v = 0; v < nv; v++)
-            incptr[v + 1] += incptr[v];
-        {
-            std::vector<int> fill(incptr.begin(), incptr.end() - 1);
-            for (int e = 0; e < ne; e++) {  // ascending edge index within each vertex
-                inc[fill[g->efrom[e]]++] = 2 * e;
-                inc[fill[g->eto[e]]++] = 2 * e + 1;
-            }
-        }
-        // chords: the edges between non-neighbouring unknowns (loop closures)
-        struct Chord {
-            int e, i, j;  // rows of `from` and `to`
-        };
-        std::vector<Chord> chords;
-        for (int e = 0; e < ne; e++) {
-            const int i = g->efrom[e] - 1, j = g->eto[e] - 1;
-            if (i < 0 || j < 0 || i == j || i - j == 1 || j - i == 1)
-                continue;
-            chords.push_back({e, i, j});
-        }
-        // Separators: every separator adds six rows to the dense reduced system, whose tile steps are what a solve's time is
-        // made of.  Two structures, the cheaper by a small cost model (measured constants) is taken:
-        //   both   BOTH endpoints of every chord + a regular one only where that leaves a run longer than SEG_L - 1 rows;
-        //   cover  a COVER of the chords (where neither endpoint of a chord is a separator yet, the later row becomes one);
-        //          a chord's other endpoint stays inside its segment and costs that segment a pass of six more right-hand-
-        //          side columns (pg_segment_kernel: two closures to a pass, at most PG_MAX_SEG_CHORDS per segment, the
-        //          ones beyond that become separators after all).
-        // At 4541 vertices / 40 closures whose matches all lie in the first lap: cover = 45 separators instead of 81 (5 tile
-        // steps instead of 9, the solve 12 us instead of 25: -80 us) but four passes of 23 us in each of the first lap's
-        // segments (+91 us): 0.292 against 0.279 ms per iteration, and the model says so; closures whose endpoints spread
-        // take one pass per segment and the cover.  SVO_PG_COVER=1 / 0 forces one or the other (the tests run both).
-        std::vector<char> cover, is_sep;
-        std::vector<int> sepidx, seps, seg_start, seg_len, lsep, rsep, rowseg;
-        auto select = [&](const bool both_ends) -> int {  // -> closure endpoints inside the fullest segment
-        cover.assign(nb, 0);
-        for (const Chord &c : chords) {
-            if (both_ends)
-                cover[c.i] = cover[c.j] = 1;
-            else if (!cover[c.i] && !cover[c.j])
-                cover[c.i > c.j ? c.i : c.j] = 1;
-        }
-        int fullest = 0;
-        for (;;) {
-            is_sep = cover;
-            for (int b = 0, run = 0; b < nb - 1; b++) {
-                if (is_sep[b]) {
-                    run = 0;
-                    continue;
-                }
-                if (++run >= SEG_L) {
-                    is_sep[b] = 1;
-                    run = 0;
-                }
-            }
-            sepidx.assign(nb, -1);
-            seps.clear();
-            for (int b = 0; b < nb; b++)
-                if (is_sep[b]) {
-                    sepidx[b] = (int)seps.size();
-                    seps.push_back(b);
-                }
-            seg_start.clear();
-            seg_len.clear();
-            lsep.assign(nb, -1);
-            rsep.assign(nb, -1);
-            rowseg.assign(nb, -1);
-            for (int b = 0; b < nb;) {
-                if (is_sep[b]) {
-                    b++;
-                    continue;
-                }
-                int z = b;
-                while (z + 1 < nb && !is_sep[z + 1])
-                    z++;
-                for (int r = b; r <= z; r++) {
-                    lsep[r] = b > 0 ? sepidx[b - 1] : -1;
-                    rsep[r] = z + 1 < nb ? sepidx[z + 1] : -1;
-                    rowseg[r] = (int)seg_start.size();
-                }
-                seg_start.push_back(b);
-                seg_len.push_back(z - b + 1);
-                b = z + 1;
-            }
-            // a segment with too many closure endpoints inside: the surplus becomes separators, and once more
-            std::vector<int> inside(seg_start.size(), 0);
-            bool again = false;
-            fullest = 0;
-            for (const Chord &c : chords)
-                for (const int r : {c.i, c.j})
-                    if (!is_sep[r]) {
-                        if (++inside[rowseg[r]] > PG_MAX_SEG_CHORDS) {
-                            cover[r] = 1;
-                            again = true;
-                        } else if (inside[rowseg[r]] > fullest)
-                            fullest = inside[rowseg[r]];
-                    }
-            if (!again)
-                break;
-        }
-        return fullest;
-        };
-        {
-            const char *force = getenv("SVO_PG_COVER");
-            bool both_ends;
-            if (force)
-                both_ends = force[0] == '0';
-            else {
-                auto cost_us = [&](const bool b) {
-                    const int fullest = select(b), tiles = (6 * (int)seps.size() + TB - 1) / TB;
-                    return 16.7 * (tiles > 1 ? tiles - 1 : 0) + 2.3 * tiles + 23.0 * ((fullest + 1) / 2);
-                };
-                both_ends = cost_us(true) <= cost_us(false);
-            }
-            (void)select(both_ends);
-        }
-        const int m = (int)seps.size(), n_seg = (int)seg_start.size();
-        // what couples a segment to the separators: its two neighbours in the chain, and the closures that end inside it
-        struct Coupling {
-            int row, sep, a_kind, a, w_kind, wbase;  // W block of row r: Wl / Wr: r itself; Wc: wbase + (r - segment start)
-        };
-        std::vector<std::vector<Coupling>> coup(n_seg);
-        std::vector<int> cptr(n_seg + 1, 0), c_lrow, c_edge, c_tr, c_wbase, c_sep;
-        for (int sg = 0; sg < n_seg; sg++) {
-            const int a = seg_start[sg], z = a + seg_len[sg] - 1;
-            if (a > 0)
-                coup[sg].push_back({a, sepidx[a - 1], 0, a - 1, 0, 0});
-            if (z < nb - 1)
-                coup[sg].push_back({z, sepidx[z + 1], 1, z, 1, 0});
-        }
-        size_t wc_blocks = 0;
-        {
-            std::vector<std::vector<Coupling>> inner(n_seg);
-            for (const Chord &c : chords) {
-                if (is_sep[c.i] && is_sep[c.j])
-                    continue;
-                // (the cover: at least one endpoint is a separator)
-                const bool from_inside = !is_sep[c.i];
-                const int r = from_inside ? c.i : c.j, sp = from_inside ? c.j : c.i, sg = rowseg[r];
-                // H[r][sp]: r = `from`: Hij; r = `to`: Hij^T
-                inner[sg].push_back({r, sepidx[sp], from_inside ? 2 : 3, c.e, 2, 0});
-            }
-            for (int sg = 0; sg < n_seg; sg++) {
-                for (Coupling &k : inner[sg]) {
-                    k.wbase = (int)wc_blocks;
-                    wc_blocks += seg_len[sg];
-                    c_lrow.push_back(k.row - seg_start[sg]);
-                    c_edge.push_back(k.a);
-                    c_tr.push_back(k.a_kind == 3 ? 1 : 0);
-                    c_wbase.push_back(k.wbase);
-                    c_sep.push_back(k.sep);
-                    coup[sg].push_back(k);
-                }
-                cptr[sg + 1] = (int)c_lrow.size();
-            }
-        }
-        // gather lists of the reduced system
-        struct Key {
-            int r, c;
-            bool operator<(const Key &o) const { return r != o.r ? r < o.r : c < o.c; }
-        };
-        std::map<Key, std::vector<int2>> blocks;
-        std::vector<std::vector<int2>> rhs_src(m);
-        std::vector<int> terms;  // PgTerm: a_kind, a, w_kind, w
-        auto term = [&](const Coupling &u, int w_kind, int w) {
-            terms.insert(terms.end(), {u.a_kind, u.a, w_kind, w});
-            return make_int2(7, (int)(terms.size() / 4 - 1));
-        };
-        for (int k = 0; k < m; k++) {
-            const int sr = seps[k];
-            blocks[{k, k}].push_back(make_int2(0, sr));
-            rhs_src[k].push_back(make_int2(0, sr));
-            if (k > 0 && seps[k - 1] + 1 == sr)
-                blocks[{k, k - 1}].push_back(make_int2(1, seps[k - 1]));
-        }
-        for (const Chord &c : chords)
-            if (is_sep[c.i] && is_sep[c.j]) {  // block(row i, col j) = Ji^T Jj; stored at (hi, lo)
-                if (c.i > c.j)
-                    blocks[{sepidx[c.i], sepidx[c.j]}].push_back(make_int2(2, c.e));
-                else
-                    blocks[{sepidx[c.j], sepidx[c.i]}].push_back(make_int2(3, c.e));
-            }
-        for (int sg = 0; sg < n_seg; sg++)
-            for (const Coupling &u : coup[sg]) {
-                rhs_src[u.sep].push_back(term(u, 3, u.row));
-                for (const Coupling &v : coup[sg]) {
-                    if (u.sep < v.sep)
-                        continue;  // the lower triangle; for u.sep == v.sep both orders are terms of the diagonal block
-                    const int w = v.w_kind == 2 ? v.wbase + (u.row - seg_start[sg]) : u.row;
-                    blocks[{u.sep, v.sep}].push_back(term(u, v.w_kind, w));
-                }
-            }
-        std::vector<int> rb_row, rb_col, rptr(1, 0);
-        std::vector<int2> rsrc;
-        for (auto &kv : blocks) {
-            rb_row.push_back(kv.first.r);
-            rb_col.push_back(kv.first.c);
-            rsrc.insert(rsrc.end(), kv.second.begin(), kv.second.end());
-            rptr.push_back((int)rsrc.size());
-        }
-        for (int k = 0; k < m; k++) {  // right-hand sides
-            rsrc.insert(rsrc.end(), rhs_src[k].begin(), rhs_src[k].end());
-            rptr.push_back((int)rsrc.size());
-        }
-        g->s_m = m;
-        g->s_nseg = n_seg;
-        g->s_maxseg = 0;
-        for (int l : seg_len)
-            g->s_maxseg = l > g->s_maxseg ? l : g->s_maxseg;
-        g->s_nrblocks = (int)blocks.size();
-        g->s_T = (6 * m + TB - 1) / TB;
-        g->s_ldr = g->s_T * TB;
-        g->s_wc_blocks = wc_blocks;
-        // one int buffer for all the structure arrays
-        hs.clear();
-        auto put = [&](const std::vector<int> &v) {
-            const size_t off = hs.size();
-            hs.insert(hs.end(), v.begin(), v.end());
-            return off;
-        };
-        g->o_seg_start = put(seg_start);
-        g->o_seg_len = put(seg_len);
-        g->o_sepidx = put(sepidx);
-        g->o_lsep = put(lsep);
-        g->o_rsep = put(rsep);
-        g->o_rowseg = put(rowseg);
-        g->o_cptr = put(cptr);
-        g->o_clrow = put(c_lrow);
-        g->o_cedge = put(c_edge);
-        g->o_ctr = put(c_tr);
-        g->o_cwbase = put(c_wbase);
-        g->o_csep = put(c_sep);
-        g->o_rb_row = put(rb_row);
-        g->o_rb_col = put(rb_col);
-        g->o_rptr = put(rptr);
-        while (hs.size() & 3)
-            hs.push_back(0);
-        g->o_terms = put(terms);
-        g->o_rsrc = hs.size();
-        for (const int2 &v : rsrc) {
-            hs.push_back(v.x);
-            hs.push_back(v.y);
-        }
+        const char *force = getenv("SVO_PG_COVER");
+        pg_solve_plan::build(nv, ne, g->efrom.data(), g->eto.data(), !force ? -1 : force[0] == '0' ? 0 : 1, g->plan);
     }
-    const int m = g->s_m, nseg = g->s_nseg, n_rblocks = g->s_nrblocks, T = g->s_T, ldr = g->s_ldr;
-    const size_t o_seg_start = g->o_seg_start, o_seg_len = g->o_seg_len, o_sepidx = g->o_sepidx, o_lsep = g->o_lsep,
-                 o_rsep = g->o_rsep, o_rb_row = g->o_rb_row, o_rb_col = g->o_rb_col, o_rptr = g->o_rptr,
-                 o_rsrc = g->o_rsrc;
-    const size_t o_rowseg = g->o_rowseg, o_cptr = g->o_cptr, o_terms = g->o_terms;
+    const pg_solve_plan::Plan &plan = g->plan;
+    if (const int bound = pg_solve_plan::solve_lds_refusal(plan)) {
+        svo_set_error("pose graph: %d separators -- the distinct loop-closure endpoints plus one regular separator per %d vertices "
+                      "of a run without one -- are more than the separator solve holds in one workgroup's LDS (%d)", plan.m, SEG_L,
+                      bound);
+        return SVO_ERR_ARG;
+    }
     hipStream_t st = ctx->stream;
     int rc;
     // the weighted linearisation runs only for a graph that stores at least one non-identity information matrix, the robust
@@ -2493,22 +2213,23 @@ int svo_pg_optimize(svo_posegraph *g, int iters, double *chi2)
     const bool weighted = g->n_info > 0, robust = g->n_robust > 0;
     g->eo_w_ne = -1;
     if ((rc = g->d_eo.ensure((size_t)ne * EO_FIELDS * 8)) || (rc = g->d_incptr.ensure((size_t)(nv + 1) * 4)) ||
-        (rc = g->d_inc.ensure((size_t)2 * ne * 4)) || (rc = g->d_struct.ensure(g->h_struct.size() * 4 + 16)) ||
+        (rc = g->d_inc.ensure((size_t)2 * ne * 4)) || (rc = g->d_struct.ensure(plan.buf.size() * 4 + 16)) ||
         (rc = g->d_Dg.ensure((size_t)nb * 288)) || (rc = g->d_Cc.ensure((size_t)nb * 288)) ||
         (rc = g->d_rneg.ensure((size_t)nb * 48)) || (rc = g->d_dx.ensure((size_t)nb * 48)) || (rc = g->d_res.ensure((size_t)nb * 48)) ||
         (rc = g->d_Y.ensure((size_t)nb * 48)) || (rc = g->d_Wl.ensure((size_t)nb * 288)) ||
-        (rc = g->d_Wr.ensure((size_t)nb * 288)) || (rc = g->d_Wc.ensure(g->s_wc_blocks * 288 + 64)) || (rc = g->d_R.ensure((size_t)ldr * ldr * 8 + 64)) ||
-        (rc = g->d_Lo.ensure((size_t)ldr * ldr * 8 + 64)) || (rc = g->d_Tinv.ensure((size_t)2 * (T + 1) * TB * TB * 8 + 64)) ||
-        (rc = g->d_rR.ensure((size_t)ldr * 8 + 64)) || (rc = g->d_xR.ensure((size_t)ldr * 8 + 64)) ||
+        (rc = g->d_Wr.ensure((size_t)nb * 288)) || (rc = g->d_Wc.ensure(plan.wc_blocks * 288 + 64)) ||
+        (rc = g->d_R.ensure((size_t)plan.ldr * plan.ldr * 8 + 64)) || (rc = g->d_Lo.ensure((size_t)plan.ldr * plan.ldr * 8 + 64)) ||
+        (rc = g->d_Tinv.ensure((size_t)2 * (plan.T + 1) * TB * TB * 8 + 64)) ||
+        (rc = g->d_rR.ensure((size_t)plan.ldr * 8 + 64)) || (rc = g->d_xR.ensure((size_t)plan.ldr * 8 + 64)) ||
         (rc = g->d_misc.ensure(((size_t)iters + 6 + (ne + 127) / 128) * 8 + 64)))
         return rc;
-    // (g->pose / efrom / eto / meas and the structure vectors live in *g: the copies need no sync)
+    // (g->pose / efrom / eto / meas and the plan's vectors live in *g: the copies need no sync)
     if ((rc = pg_upload_graph(g, weighted, st)))
         return rc;
     if (rebuild) {
-        SVO_HIP(hipMemcpyAsync(g->d_incptr.p, g->h_incptr.data(), (size_t)(nv + 1) * 4, hipMemcpyHostToDevice, st));
-        SVO_HIP(hipMemcpyAsync(g->d_inc.p, g->h_inc.data(), (size_t)2 * ne * 4, hipMemcpyHostToDevice, st));
-        SVO_HIP(hipMemcpyAsync(g->d_struct.p, g->h_struct.data(), g->h_struct.size() * 4, hipMemcpyHostToDevice, st));
+        SVO_HIP(hipMemcpyAsync(g->d_incptr.p, plan.incptr.data(), (size_t)(nv + 1) * 4, hipMemcpyHostToDevice, st));
+        SVO_HIP(hipMemcpyAsync(g->d_inc.p, plan.inc.data(), (size_t)2 * ne * 4, hipMemcpyHostToDevice, st));
+        SVO_HIP(hipMemcpyAsync(g->d_struct.p, plan.buf.data(), plan.buf.size() * 4, hipMemcpyHostToDevice, st));
         g->built_nv = nv;
         g->built_ne = ne;
     }
@@ -2522,24 +2243,18 @@ int svo_pg_optimize(svo_posegraph *g, int iters, double *chi2)
     double *eo = g->d_eo.as<double>();
     double *Dg = g->d_Dg.as<double>(), *Cc = g->d_Cc.as<double>(), *rneg = g->d_rneg.as<double>();
     double *Y = g->d_Y.as<double>(), *Wl = g->d_Wl.as<double>(), *Wr = g->d_Wr.as<double>(), *Wc = g->d_Wc.as<double>();
-    const PgSegChords seg_chords = {ds + o_cptr, ds + g->o_clrow, ds + g->o_cedge, ds + g->o_ctr, ds + g->o_cwbase};
+    const PgSegChords seg_chords = {ds + plan.o_cptr, ds + plan.o_clrow, ds + plan.o_cedge, ds + plan.o_ctr, ds + plan.o_cwbase};
     double *R = g->d_R.as<double>(), *Lo = g->d_Lo.as<double>(), *Tinv = g->d_Tinv.as<double>();
     double *rR = g->d_rR.as<double>(), *xR = g->d_xR.as<double>();
-    // the separator solve keeps its vector and its running sums in LDS
-    const size_t solve_lds = (size_t)(2 * ldr + TB) * 8;
-    if (solve_lds > 158 * 1024) {
-        svo_set_error("pose graph: %d separators -- the distinct loop-closure endpoints plus one regular separator per %d vertices "
-                      "of a run without one -- are more than the separator solve holds in one workgroup's LDS (%d)", m, SEG_L,
-                      (158 * 1024 / 16 - TB) / 6);
-        return SVO_ERR_ARG;
-    }
+    // the separator solve keeps its vector and its running sums in LDS (what does not fit was refused above)
+    const size_t solve_lds = (size_t)(2 * plan.ldr + TB) * 8;
     if (solve_lds > 48 * 1024)
         SVO_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(pg_dense_solve_kernel),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)solve_lds));
     // a segment's rows live in LDS: SEG_L - 1 of them between two regular separators, SEG_L in a tail segment (the
     // regular-separator loop stops one row before the end) -- ADVICE r4: the bound to check is SEG_L itself
     static_assert(SEG_L <= BCR_MAX_ROWS, "a segment must fit the LDS of one workgroup");
-    const size_t seg_lds = (size_t)g->s_maxseg * BCR_ROW * 8;
+    const size_t seg_lds = (size_t)plan.maxseg * BCR_ROW * 8;
     if (seg_lds > 48 * 1024)
         SVO_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(pg_segment_kernel),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)seg_lds));
@@ -2565,29 +2280,33 @@ int svo_pg_optimize(svo_posegraph *g, int iters, double *chi2)
         const double *rhs = rneg;
         for (int pass = 0; pass <= g->refine; pass++) {
             const bool last = pass == g->refine;
-            if (nseg > 0 || m > 0)
-                hipLaunchKernelGGL(pg_segment_kernel, dim3(nseg + (m > 0 ? PG_CLEAR_WGS : 0)), dim3(BCR_WAVES * 64), seg_lds, st,
-                                   nb, nseg, ds + o_seg_start, ds + o_seg_len, Dg, Cc, rhs, Y, Wl, Wr, d_status, R, ldr, 6 * m,
-                                   rR, seg_chords, eo, Wc);
-            if (m > 0) {
-                hipLaunchKernelGGL(pg_reduce_kernel, dim3(n_rblocks + m), dim3(64), 0, st, n_rblocks, m, ds + o_rb_row,
-                                   ds + o_rb_col, ds + o_rptr, reinterpret_cast<const int2 *>(ds + o_rsrc),
-                                   reinterpret_cast<const PgTerm *>(ds + o_terms), Dg, Cc, rhs, eo, Y, Wl, Wr, Wc, R, ldr, rR);
-                double *Tp = Tinv + (size_t)(T + 1) * TB * TB;  // the inverses again, in the solve's layout
-                hipLaunchKernelGGL(pg_dense_potf2_kernel, dim3(1), dim3(256), 0, st, R, Tinv, Tp, ldr, 0, d_status, 1 << 20);
-                for (int kb = 0; kb + 1 < T; kb++) {
-                    const int nt = T - 1 - kb;
-                    hipLaunchKernelGGL(pg_dense_step_kernel, dim3(nt * (nt + 1) / 2 + 1), dim3(256), 0, st, R, Lo, Tinv, Tp, ldr, T, kb,
-                                       rR, xR, d_status, 1 << 20);
+            if (plan.nseg > 0 || plan.m > 0)
+                hipLaunchKernelGGL(pg_segment_kernel, dim3(plan.nseg + (plan.m > 0 ? PG_CLEAR_WGS : 0)), dim3(BCR_WAVES * 64),
+                                   seg_lds, st, nb, plan.nseg, ds + plan.o_seg_start, ds + plan.o_seg_len, Dg, Cc, rhs, Y, Wl, Wr,
+                                   d_status, R, plan.ldr, 6 * plan.m, rR, seg_chords, eo, Wc);
+            if (plan.m > 0) {
+                static_assert(sizeof(psp::Src) == sizeof(int2) && offsetof(psp::Src, kind) == offsetof(int2, x) &&
+                                  offsetof(psp::Src, idx) == offsetof(int2, y), "the kernel reads a source as an int2");
+                hipLaunchKernelGGL(pg_reduce_kernel, dim3(plan.nrblocks + plan.m), dim3(64), 0, st, plan.nrblocks, plan.m,
+                                   ds + plan.o_rb_row, ds + plan.o_rb_col, ds + plan.o_rptr,
+                                   reinterpret_cast<const int2 *>(ds + plan.o_rsrc),
+                                   reinterpret_cast<const PgTerm *>(ds + plan.o_terms), Dg, Cc, rhs, eo, Y, Wl, Wr, Wc, R, plan.ldr,
+                                   rR);
+                double *Tp = Tinv + (size_t)(plan.T + 1) * TB * TB;  // the inverses again, in the solve's layout
+                hipLaunchKernelGGL(pg_dense_potf2_kernel, dim3(1), dim3(256), 0, st, R, Tinv, Tp, plan.ldr, 0, d_status, 1 << 20);
+                for (int kb = 0; kb + 1 < plan.T; kb++) {
+                    const int nt = plan.T - 1 - kb;
+                    hipLaunchKernelGGL(pg_dense_step_kernel, dim3(nt * (nt + 1) / 2 + 1), dim3(256), 0, st, R, Lo, Tinv, Tp, plan.ldr,
+                                       plan.T, kb, rR, xR, d_status, 1 << 20);
                 }
-                hipLaunchKernelGGL(pg_dense_solve_kernel, dim3(1), dim3(PG_SOLVE_THREADS),
-                                   (size_t)(2 * ldr + TB) * 8, st, Lo, Tinv, Tp, ldr, T, rR, xR);
+                hipLaunchKernelGGL(pg_dense_solve_kernel, dim3(1), dim3(PG_SOLVE_THREADS), solve_lds, st, Lo, Tinv, Tp, plan.ldr,
+                                   plan.T, rR, xR);
             }
             double *dxs = g->d_dx.as<double>();
             hipLaunchKernelGGL(pg_backsub_update_kernel, dim3((nb + PG_UPD_ROWS - 1) / PG_UPD_ROWS), dim3(PG_UPD_ROWS * 6), 0, st,
-                               nb, ds + o_sepidx, ds + o_lsep, ds + o_rsep, xR, Y, Wl, Wr, ds + o_rowseg, ds + o_seg_start,
-                               ds + o_cptr, ds + g->o_csep, ds + g->o_cwbase, Wc, g->d_pose.as<double>(),
-                               pass > 0 ? dxs : nullptr, last ? nullptr : dxs);
+                               nb, ds + plan.o_sepidx, ds + plan.o_lsep, ds + plan.o_rsep, xR, Y, Wl, Wr, ds + plan.o_rowseg,
+                               ds + plan.o_seg_start, ds + plan.o_cptr, ds + plan.o_csep, ds + plan.o_cwbase, Wc,
+                               g->d_pose.as<double>(), pass > 0 ? dxs : nullptr, last ? nullptr : dxs);
             if (!last) {
                 hipLaunchKernelGGL(pg_residual_kernel, dim3((nb + PG_UPD_ROWS - 1) / PG_UPD_ROWS), dim3(PG_UPD_ROWS * 6), 0, st, nb,
                                    g->d_incptr.as<int>(), g->d_inc.as<int>(), g->d_from.as<int>(), g->d_to.as<int>(), eo, rneg, dxs,
@@ -2675,129 +2394,30 @@ int svo_pg_write_g2o(const svo_posegraph *g, const char *path)
     return SVO_OK;
 }
 
-/* The inverse of svo_pg_write_g2o / saveStructure: replaces the graph by the file's content.
- * Tags read: VERTEX_SE3:QUAT id x y z qx qy qz qw, EDGE_SE3:QUAT i j x y z qx qy qz qw [21 numbers of
- * the upper-triangular information matrix, ignored: the reference leaves it at identity,
- * poseGraph.h:102-104,122], FIX id (only vertex 0 may be fixed, as upstream fixes it, :75).  Vertex
- * ids must be 0..n-1 (any order in the file); other tags are skipped.                          */
+// The inverse of svo_pg_write_g2o / saveStructure: replaces the graph by the file's content (pg_g2o::read has the format and the
+// refusals); keep_info: the edges' 21 information numbers are kept, else ignored as the reference leaves them at identity.
 static int pg_read_g2o(svo_posegraph *g, const char *path, const bool keep_info)
 {
     SVO_CHECK_ARG(g && path);
-    FILE *f = fopen(path, "r");
-    if (!f) {
-        svo_set_error("cannot open %s", path);
+    pg_g2o::Graph in;
+    const std::string why = pg_g2o::read(path, keep_info, in);
+    if (!why.empty()) {
+        svo_set_error("%s", why.c_str());
         return SVO_ERR_ARG;
     }
-    std::vector<std::pair<int, std::vector<double>>> verts;
-    std::vector<int> ef, et;
-    std::vector<double> em, einfo;  // einfo: 21 per edge
-    std::vector<char> ehas;
-    char line[4096], tag[64];
-    int rc = SVO_OK, lineno = 0;
-    while (fgets(line, sizeof(line), f)) {
-        lineno++;
-        int off = 0;
-        if (sscanf(line, "%63s%n", tag, &off) != 1 || tag[0] == '#')
-            continue;
-        const char *rest = line + off;
-        if (!strcmp(tag, "VERTEX_SE3:QUAT")) {
-            int id;
-            double p[7];
-            if (sscanf(rest, "%d %lf %lf %lf %lf %lf %lf %lf", &id, p, p + 1, p + 2, p + 3, p + 4, p + 5, p + 6) != 8 ||
-                id < 0) {
-                svo_set_error("%s:%d: malformed VERTEX_SE3:QUAT", path, lineno);
-                rc = SVO_ERR_ARG;
-                break;
-            }
-            q_normalize(p + 3);
-            verts.emplace_back(id, std::vector<double>(p, p + 7));
-        } else if (!strcmp(tag, "EDGE_SE3:QUAT")) {
-            int i, j, used = 0;
-            double z[7];
-            if (sscanf(rest, "%d %d %lf %lf %lf %lf %lf %lf %lf%n", &i, &j, z, z + 1, z + 2, z + 3, z + 4, z + 5, z + 6, &used) != 9) {
-                svo_set_error("%s:%d: malformed EDGE_SE3:QUAT", path, lineno);
-                rc = SVO_ERR_ARG;
-                break;
-            }
-            if (keep_info) {  // none (identity) or exactly the 21 numbers of the upper triangle
-                double om[22];
-                int cnt = 0;
-                const char *c = rest + used;
-                for (;;) {
-                    char *end = nullptr;
-                    const double v = strtod(c, &end);
-                    if (end == c)
-                        break;
-                    if (cnt < 22)
-                        om[cnt] = v;
-                    cnt++;
-                    c = end;
-                }
-                while (*c == ' ' || *c == '\t' || *c == '\r' || *c == '\n')
-                    c++;
-                if ((cnt != 0 && cnt != 21) || *c) {
-                    svo_set_error("%s:%d: EDGE_SE3:QUAT with %d information numbers (0 or 21 expected)", path, lineno, cnt);
-                    rc = SVO_ERR_ARG;
-                    break;
-                }
-                if (cnt == 21 && pg_check_info(om, "edge", (int)ef.size())) {
-                    const std::string why = svo_last_error();
-                    svo_set_error("%s:%d: %s", path, lineno, why.c_str());
-                    rc = SVO_ERR_ARG;
-                    break;
-                }
-                ehas.push_back(cnt == 21);
-                einfo.insert(einfo.end(), cnt == 21 ? om : PG_INFO_IDENTITY, (cnt == 21 ? om : PG_INFO_IDENTITY) + 21);
-            }
-            q_normalize(z + 3);
-            ef.push_back(i);
-            et.push_back(j);
-            em.insert(em.end(), z, z + 7);
-        } else if (!strcmp(tag, "FIX")) {
-            int id = -1;
-            if (sscanf(rest, "%d", &id) != 1 || id != 0) {
-                svo_set_error("%s:%d: only vertex 0 can be fixed (FIX %d)", path, lineno, id);
-                rc = SVO_ERR_ARG;
-                break;
-            }
-        }
-    }
-    fclose(f);
-    if (rc)
-        return rc;
-    const int n = (int)verts.size();
-    std::vector<double> pose((size_t)n * 7, 0.);
-    std::vector<char> seen(n, 0);
-    for (auto &v : verts) {
-        if (v.first >= n || seen[v.first]) {
-            svo_set_error("%s: vertex ids must be 0..%d without gaps or repeats (id %d)", path, n - 1, v.first);
-            return SVO_ERR_ARG;
-        }
-        seen[v.first] = 1;
-        memcpy(&pose[(size_t)v.first * 7], v.second.data(), 7 * sizeof(double));
-    }
-    for (size_t e = 0; e < ef.size(); e++)
-        if (ef[e] < 0 || ef[e] >= n || et[e] < 0 || et[e] >= n || ef[e] == et[e]) {
-            svo_set_error("%s: edge %zu connects vertices %d -> %d of %d", path, e, ef[e], et[e], n);
-            return SVO_ERR_ARG;
-        }
-    if (n == 0) {
-        svo_set_error("%s: no VERTEX_SE3:QUAT lines", path);
-        return SVO_ERR_ARG;
-    }
-    g->pose = pose;
-    g->efrom = ef;
-    g->eto = et;
-    g->meas = em;
+    g->pose.swap(in.pose);
+    g->efrom.swap(in.efrom);
+    g->eto.swap(in.eto);
+    g->meas.swap(in.meas);
     pg_drop_info(g);
     pg_drop_robust(g);  // (the format has no field for kernels)
     g->lc_kind = SVO_PG_ROBUST_NONE;
     g->lc_delta = 0;
     g->eo_w_ne = -1;
-    for (size_t e = 0; e < ehas.size(); e++)
-        if (ehas[e])
-            pg_store_info(g, (int)e, &einfo[21 * e]);
-    g->prev = n - 1;
+    for (size_t e = 0; e < in.has_info.size(); e++)
+        if (in.has_info[e])
+            pg_store_info(g, (int)e, &in.info[21 * e]);
+    g->prev = g->nv() - 1;
     g->dev_nv = g->dev_ne = 0;
     g->built_nv = g->built_ne = -1;
     return SVO_OK;

@@ -69,6 +69,35 @@ def test_iterates_match_oracle(ctx, orc, n, laps, closures):
         g.close()
 
 
+@pytest.mark.parametrize("cover", ["1", "0"])
+@pytest.mark.parametrize("n,laps,closures", [(50, 1, [(48, 0), (49, 0)]), (215, 2, [(214, 107)])])
+def test_refinement_passes_two_to_four(ctx, orc, monkeypatch, n, laps, closures, cover):
+    """svo_pg_set_refinement(2 .. 4): the middle passes add their correction to the dx of the passes before IN PLACE
+    (pg_backsub_update_kernel with dx_add == dx_out, neither of them __restrict__).  The iterates meet the oracle within
+    test_iterates_match_oracle's tolerances, and the last chi2 is not above the one a single refinement pass reaches, within that
+    tolerance.  50 vertices, two closures to the fixed vertex (no separator at all); a chain of 215, two laps, with one closure a
+    lap back (regular separators; under the cover the closure's earlier endpoint stays inside a segment); both structures."""
+    monkeypatch.setenv("SVO_PG_COVER", cover)
+    gt, est = drifting_loop(n, laps=laps, yaw_drift=1e-3 / laps)
+    for iters in (1, 2, 4, 10):
+        o = _build(orc.PoseGraph, est, closures)
+        co, eo = o.optimize(iters), o.estimates()
+        last = {}
+        for passes in (1, 2, 3, 4):
+            g = _build(lambda: capi.PoseGraph(ctx), est, closures)
+            g.set_refinement(passes)
+            cg = g.optimize(iters)
+            last[passes] = cg[-1]
+            print(f"n {n} cover {cover} iters {iters} passes {passes}: chi2 {cg[-1]:.17g} (oracle {co[-1]:.17g}), "
+                  f"estimates max |diff| {np.abs(g.estimates() - eo).max():.3e}")
+            if passes >= 2:
+                assert np.allclose(cg, co, rtol=1e-8, atol=1e-18), (iters, passes, cg, co)
+                assert _close(g.estimates(), eo, 1e-8), (iters, passes)
+                assert np.array_equal(g.estimates()[0], [0, 0, 0, 0, 0, 0, 1])
+                assert cg[-1] <= last[1] + 1e-8 * abs(last[1]) + 1e-18, (iters, passes, cg[-1], last[1])
+            g.close()
+
+
 def test_awkward_segment_shapes(ctx, orc):
     """The elimination structure's corner cases in one graph of 760 vertices, four laps of a loop, every closure between
     true revisits (vertex i + 190 k and vertex i): runs of 0, 1, 2, 3, 13, 16, 17, 29, 64, 73, 74, 83 and 103 rows
