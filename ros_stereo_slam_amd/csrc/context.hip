@@ -170,8 +170,8 @@ int svo_ctx_create(int device, svo_ctx **out)
         svo_set_error("hipHostMalloc -> %s", hipGetErrorString(e));
         return SVO_ERR_HIP;
     }
-    if (hipMalloc(reinterpret_cast<void **>(&ctx->d_tickets), 256) != hipSuccess ||
-        hipMemset(ctx->d_tickets, 0, 256) != hipSuccess) {
+    if (hipMalloc(reinterpret_cast<void **>(&ctx->d_tickets), SVO_N_TICKETS * sizeof(unsigned)) != hipSuccess ||
+        hipMemset(ctx->d_tickets, 0, SVO_N_TICKETS * sizeof(unsigned)) != hipSuccess) {
         (void)hipHostFree(ctx->pinned);
         (void)hipStreamDestroy(ctx->stream);
         delete ctx;

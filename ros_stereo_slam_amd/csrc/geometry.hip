@@ -31,7 +31,7 @@ struct TriJob {
     VoChain *chain;  // chain mode (svo_tri_job::chain) or null
     float2 *out_x1;  // optional copy of x1
     const uint8_t *cimg;  // optional colour gather at x1: level 0 of the left pyramid (pixel (0,0)), its pitch and size
-    int cpitch, cw, chh, cc;
+    int cpitch, cw, chh, cc, cgdelta;  // cgdelta: svo_pyramid::gdelta[0], where a grey-stored pyramid keeps level 0
     float *cout;
 };
 template <int NJ> struct TriBatchN {  // blockIdx.y picks the job; NJ = 1: a lone problem (a sixteenth of the kernel arguments)
@@ -84,10 +84,11 @@ template <int NJ> __global__ __launch_bounds__(128) void triangulate_kernel(Mat3
         int cx = (int)a.x, cy = (int)a.y;
         cx = cx < 0 ? 0 : (cx >= job.cw ? job.cw - 1 : cx);
         cy = cy < 0 ? 0 : (cy >= job.chh ? job.chh - 1 : cy);
-        const uint8_t *px = job.cimg + (size_t)cy * job.cpitch + cx * job.cc;
+        int cstep;  // a grey-stored pyramid holds one byte per pixel: the storage word decides (svo_internal.h)
+        const uint8_t *px = svo_pyr_pixel0(job.cimg, job.cpitch, job.cc, job.cw, job.cgdelta, cx, cy, &cstep);
 #pragma unroll
         for (int k = 0; k < 3; k++)
-            job.cout[3 * i + k] = (float)px[job.cc >= 3 ? k : 0];
+            job.cout[3 * i + k] = (float)px[k * cstep];
     }
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -129,7 +130,7 @@ struct PlaceArgs {
     float2 *out_x1;
     float *out_cam, *out_world;
     const uint8_t *cimg;
-    int cpitch, cw, chh, cc;
+    int cpitch, cw, chh, cc, cgdelta;  // cgdelta: svo_pyramid::gdelta[0], where a grey-stored pyramid keeps level 0
     float *cout;
 };
 // what: 1 = the pose-free part (reference-set size and halt rule, the 2-D set, colours: all the next tracking pass
@@ -159,10 +160,11 @@ __global__ __launch_bounds__(64) void keyframe_place_kernel(PlaceArgs a, int wha
             int cx = (int)p.x, cy = (int)p.y;
             cx = cx < 0 ? 0 : (cx >= a.cw ? a.cw - 1 : cx);
             cy = cy < 0 ? 0 : (cy >= a.chh ? a.chh - 1 : cy);
-            const uint8_t *px = a.cimg + (size_t)cy * a.cpitch + cx * a.cc;
+            int cstep;
+            const uint8_t *px = svo_pyr_pixel0(a.cimg, a.cpitch, a.cc, a.cw, a.cgdelta, cx, cy, &cstep);
 #pragma unroll
             for (int k = 0; k < 3; k++)
-                a.cout[3 * i + k] = (float)px[a.cc >= 3 ? k : 0];
+                a.cout[3 * i + k] = (float)px[k * cstep];
         }
     }
     if (what & 2) {
@@ -192,7 +194,7 @@ __global__ __launch_bounds__(256) void transform_kernel(Mat34 Rt, const float *_
 }
 
 __global__ __launch_bounds__(256) void colors_kernel(const uint8_t *__restrict__ lvl0, int pitch, int w, int h,
-                                                     int c, const float2 *__restrict__ xy, int n_host,
+                                                     int c, int gdelta0, const float2 *__restrict__ xy, int n_host,
                                                      const int *__restrict__ d_n, float *__restrict__ out)
 {
     __builtin_amdgcn_s_setprio(3);  // short latency-bound kernel: win issue arbitration against co-resident LK waves
@@ -203,10 +205,11 @@ __global__ __launch_bounds__(256) void colors_kernel(const uint8_t *__restrict__
     int x = (int)xy[i].x, y = (int)xy[i].y;
     x = x < 0 ? 0 : (x >= w ? w - 1 : x);  // the reference reads out of bounds here; clamped
     y = y < 0 ? 0 : (y >= h ? h - 1 : y);
-    const uint8_t *px = lvl0 + (size_t)y * pitch + x * c;
+    int cstep;
+    const uint8_t *px = svo_pyr_pixel0(lvl0, pitch, c, w, gdelta0, x, y, &cstep);
 #pragma unroll
     for (int k = 0; k < 3; k++)
-        out[3 * i + k] = (float)px[c >= 3 ? k : 0];
+        out[3 * i + k] = (float)px[k * cstep];
 }
 
 // Order-preserving compaction of up to three float arrays by a byte mask.  Single-wave workgroups
@@ -335,6 +338,7 @@ int svo_launch_triangulate_batch(svo_ctx *ctx, const double *P1, const double *P
         j.out_x1 = reinterpret_cast<float2 *>(h.out_x1);
         j.cimg = h.color_src && h.color_out ? h.color_src->dev.lvl[0] : nullptr;
         j.cpitch = h.color_src ? h.color_src->dev.pitch[0] : 0;
+        j.cgdelta = h.color_src ? h.color_src->gdelta[0] : 0;
         j.cw = h.color_src ? h.color_src->w : 0;
         j.chh = h.color_src ? h.color_src->h : 0;
         j.cc = h.color_src ? h.color_src->c : 0;
@@ -379,6 +383,7 @@ int svo_launch_keyframe_place(svo_ctx *ctx, VoChain *chain, const float *x1, con
     a.out_world = out_world;
     a.cimg = color_src && color_out ? color_src->dev.lvl[0] : nullptr;
     a.cpitch = color_src ? color_src->dev.pitch[0] : 0;
+    a.cgdelta = color_src ? color_src->gdelta[0] : 0;
     a.cw = color_src ? color_src->w : 0;
     a.chh = color_src ? color_src->h : 0;
     a.cc = color_src ? color_src->c : 0;
@@ -412,7 +417,7 @@ int svo_launch_colors(svo_ctx *ctx, const svo_pyramid *pyr, const float *xy, int
     if (cap <= 0)
         return SVO_OK;
     hipLaunchKernelGGL(colors_kernel, dim3((cap + 255) / 256), dim3(256), 0, ctx->stream, pyr->dev.lvl[0],
-                       pyr->dev.pitch[0], pyr->w, pyr->h, pyr->c, reinterpret_cast<const float2 *>(xy), cap, d_n,
+                       pyr->dev.pitch[0], pyr->w, pyr->h, pyr->c, pyr->gdelta[0], reinterpret_cast<const float2 *>(xy), cap, d_n,
                        out);
     SVO_HIP(hipGetLastError());
     return SVO_OK;

@@ -51,6 +51,9 @@ struct LkParams {
     int lattice;                 // 0: every level interpolates its patches, integer positions too (SVO_LK_LATTICE=0, for A/B and tests)
     int cell_cache;              // 0: every iteration reloads and pairs its two tile rows, same cell or not (SVO_LK_CELL_CACHE=0, for A/B and tests)
     int mono;                    // 0: grey frames stored as BGR get the three-channel arithmetic too (SVO_LK_MONO=0, for A/B and tests)
+    // the grey regions of grey-stored three-channel pyramids (svo_internal.h): bytes from pixel (0, 0) of level l to pixel
+    // (0, 0) of grey level l, and element (0, 0) of grey derivative level l in ints; the pitches follow from the widths
+    int gdelta[SVO_MAX_LEVELS], gdoff[SVO_MAX_LEVELS];
 };
 static_assert(sizeof(LkBatch) + sizeof(LkParams) <= 4096, "kernel arguments are limited to 4 KB");
 
@@ -598,7 +601,6 @@ __global__ __launch_bounds__(64 * WAVES, C == 3 && !WANT_ERR ? 5 : 4) void lk_tr
     uint8_t *DB = lds;                                          // DT rows of packed (4 dx | 4 dy << 16), as loaded (after T)
     uint8_t *TJ = lds;                                          // TS x TS x C bytes (after D)
 
-    constexpr int TROW = Tile<C, PT>::ROW;
     const bool active = lane < 3 * WIN;
     const int wy = active ? lane / 3 : WIN - 1;  // window row of this lane
     const int ws = active ? lane - 3 * wy : 0;   // segment
@@ -624,24 +626,32 @@ __global__ __launch_bounds__(64 * WAVES, C == 3 && !WANT_ERR ? 5 : 4) void lk_tr
     if constexpr (C == 3) {
         // Wave-uniform, per job (the jobs of one launch may differ): the "channels agree" words of both pyramids, which sit
         // in front of level 0's padded buffer (svo_internal.h) -- two scalar loads and a scalar branch.
-        bool mono = false;
+        // Where both pyramids are grey-STORED as well (their storage words), the one-channel body stages one-channel tiles
+        // from their grey regions: a third of the bytes through the LDS, bytes and derivative words read directly.  Every
+        // other pair reads the three-channel regions, which lk_expand_kernel has filled for a grey-stored pyramid of it.
+        bool mono = false, grey = false;
         if (prm.mono) {
             const int *wp = svo_pyr_words(prev.lvl[0] - (ptrdiff_t)SVO_PYR_PAD * prev.pitch[0] - SVO_PYR_PAD * C);
             const int *wn = svo_pyr_words(next.lvl[0] - (ptrdiff_t)SVO_PYR_PAD * next.pitch[0] - SVO_PYR_PAD * C);
             mono = uniform(wp[SVO_PYR_MONO] & wn[SVO_PYR_MONO]) != 0;
+            grey = mono && uniform((wp[SVO_PYR_STORED] == 1) & (wn[SVO_PYR_STORED] == 1)) != 0;
         }
         // the three-channel body first: it is the fall-through of the branch (colour frames measured 2 us of 700 faster so)
         if (!mono) {
-            constexpr int CA = 3, MUL = C / CA;
+            constexpr int CA = 3, CS = 3, MUL = C / CA;
+            static_assert(CA == C || (CA == 1 && C == 3), "the one-channel body is for three equal channels");
+#include "lk_levels.hip.h"
+        } else if (!grey) {
+            constexpr int CA = 1, CS = 3, MUL = C / CA;
             static_assert(CA == C || (CA == 1 && C == 3), "the one-channel body is for three equal channels");
 #include "lk_levels.hip.h"
         } else {
-            constexpr int CA = 1, MUL = C / CA;
+            constexpr int CA = 1, CS = 1, MUL = C / CA;
             static_assert(CA == C || (CA == 1 && C == 3), "the one-channel body is for three equal channels");
 #include "lk_levels.hip.h"
         }
     } else {
-        constexpr int CA = C, MUL = C / CA;
+        constexpr int CA = C, CS = C, MUL = C / CA;
         static_assert(CA == C || (CA == 1 && C == 3), "the one-channel body is for three equal channels");
 #include "lk_levels.hip.h"
     }
@@ -654,6 +664,81 @@ __global__ __launch_bounds__(64 * WAVES, C == 3 && !WANT_ERR ? 5 : 4) void lk_tr
             err[p] = st ? errv : 0.f;
         if (min_eig_out)
             min_eig_out[p] = mineig0;
+    }
+}
+
+// A pair the three-channel-storage bodies must serve although a pyramid of it is grey-stored (the other is colour,
+// SVO_LK_MONO=0, a pyramid that never published its mono word): one small launch ahead of the tracking kernel writes the
+// pyramid's three-channel levels -- and derivative levels, for the pair's first image -- from its grey ones and marks them
+// valid (SVO_PYR_COLOUR_VALID; the pyramid's next build clears the mark).  EXPAND_WGS single-wave workgroups per job and
+// image loop over the dwords; in every other case they leave after their scalar loads.
+// Whether a slot (job, image) has work does not change during the launch, except through the mark itself.  All workgroups of
+// a slot that has work count themselves on the slot's ticket when they are done, and the last one sets the mark: so the
+// mark is first set by a slot ALL of whose workgroups did their share, and a workgroup that finds it set (two slots may name
+// one pyramid; an earlier launch may have expanded it) skips its share and still counts itself.
+constexpr int EXPAND_WGS = 32;
+template <int NJ>
+__global__ __launch_bounds__(64) void lk_expand_kernel(LkBatchN<NJ> batch, LkParams prm, unsigned *__restrict__ tickets, int force)
+{
+    svo_chain_priority();
+    const LkJob &job = batch.j[blockIdx.z];
+    if (job.gate && *job.gate == 0)
+        return;
+    const PyrDev &prev = job.prev, &next = job.next;
+    const bool first = blockIdx.y == 0;
+    const PyrDev &pyr = first ? prev : next;
+    int *wp = svo_pyr_words(prev.lvl[0] - (ptrdiff_t)SVO_PYR_PAD * prev.pitch[0] - SVO_PYR_PAD * 3);
+    int *wn = svo_pyr_words(next.lvl[0] - (ptrdiff_t)SVO_PYR_PAD * next.pitch[0] - SVO_PYR_PAD * 3);
+    int *words = first ? wp : wn;
+    if (uniform(words[SVO_PYR_STORED]) != 1)
+        return;
+    // the tracking kernel's own rule for the body that stages the grey regions
+    if (!force && prm.mono && uniform(wp[SVO_PYR_MONO] & wn[SVO_PYR_MONO]) != 0 &&
+        uniform((wp[SVO_PYR_STORED] == 1) & (wn[SVO_PYR_STORED] == 1)) != 0)
+        return;
+    const int need = first && job.dprev ? 3 : 1;
+    const int todo = need & ~uniform(__hip_atomic_load(&words[SVO_PYR_COLOUR_VALID], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    const int tid = blockIdx.x * 64 + threadIdx.x, nthreads = EXPAND_WGS * 64;
+    for (int l = 0; l <= prm.max_level; l++) {
+        const int w = pyr.w[l], h = pyr.h[l];
+        if (todo & 1) {
+            // the whole padded buffer, border and all: byte b of a row is byte b / 3 of the grey row (zero past the last pixel)
+            const int pitch = pyr.pitch[l], gpitch = svo_grey_pitch(w), nd = pitch >> 2, total = nd * (h + 2 * SVO_PYR_PAD);
+            uint8_t *dst = const_cast<uint8_t *>(pyr.lvl[l]) - (ptrdiff_t)SVO_PYR_PAD * pitch - SVO_PYR_PAD * 3;
+            const uint8_t *src = pyr.lvl[l] + prm.gdelta[l] - (ptrdiff_t)SVO_PYR_PAD * gpitch - SVO_PYR_PAD;
+            for (int i = tid; i < total; i += nthreads) {
+                const int row = i / nd, d = i - row * nd;
+                unsigned out = 0;
+#pragma unroll
+                for (int b = 0; b < 4; b++) {
+                    const int px = (4 * d + b) / 3;
+                    if (px < w + 2 * SVO_PYR_PAD)
+                        out |= (unsigned)src[(size_t)row * gpitch + px] << (8 * b);
+                }
+                reinterpret_cast<unsigned *>(dst + (size_t)row * pitch)[d] = out;
+            }
+        }
+        if (todo & 2) {
+            // the interiors: both zero borders stay as they are
+            const int dp = prm.dpitch[l] >> 2, gdp = svo_grey_dpitch(w) >> 2, ne = 3 * w, total = ne * h;
+            int *dst = const_cast<int *>(job.dprev) + prm.doff[l];
+            const int *src = job.dprev + prm.gdoff[l];
+            for (int i = tid; i < total; i += nthreads) {
+                const int y = i / ne, e = i - y * ne;
+                dst[(size_t)y * dp + e] = src[(size_t)y * gdp + e / 3];
+            }
+        }
+    }
+    __threadfence();
+    unsigned *ticket = tickets + 32 + 2 * blockIdx.z + blockIdx.y;  // slots 32..63 (0..31: fransac.hip, pnp.hip)
+    __shared__ unsigned s_last;
+    if (threadIdx.x == 0)
+        s_last = atomicAdd(ticket, 1u) == EXPAND_WGS - 1;
+    __syncthreads();
+    if (s_last && threadIdx.x == 0) {
+        __threadfence();
+        atomicOr(&words[SVO_PYR_COLOUR_VALID], need);
+        *ticket = 0;
     }
 }
 
@@ -705,6 +790,8 @@ int svo_launch_lk_batch(svo_ctx *ctx, int n_jobs, const LkJob *jobs, const svo_p
     for (int l = 0; l < SVO_MAX_LEVELS; l++) {
         prm.doff[l] = (int)geom->doff[l];
         prm.dpitch[l] = geom->dpitch[l];
+        prm.gdelta[l] = geom->gdelta[l];
+        prm.gdoff[l] = (int)geom->gdoff[l];
     }
     static const int lone_interleave = getenv("SVO_LK_INTERLEAVE") ? atoi(getenv("SVO_LK_INTERLEAVE")) : 1;  // A/B: +2.8 % frames/s for one chunk per GPU
     // Round 4: the launches of the lock-step groups deal their keypoints round-robin too.  Until then XCD x was given the
@@ -735,6 +822,14 @@ int svo_launch_lk_batch(svo_ctx *ctx, int n_jobs, const LkJob *jobs, const svo_p
     if (c != 1 && c != 3) {
         svo_set_error("lk: unsupported channel count %d (1 or 3)", c);
         return SVO_ERR_ARG;
+    }
+    if (c == 3) {
+        // grey-stored pyramids of pairs that the three-channel-storage bodies will serve (lk_expand_kernel)
+        if (n_jobs == 1)
+            hipLaunchKernelGGL((lk_expand_kernel<1>), dim3(EXPAND_WGS, 2, 1), dim3(64), 0, ctx->stream, one, prm, ctx->d_tickets, 0);
+        else
+            hipLaunchKernelGGL((lk_expand_kernel<SVO_LK_MAX_JOBS>), dim3(EXPAND_WGS, 2, n_jobs), dim3(64), 0, ctx->stream, batch, prm,
+                               ctx->d_tickets, 0);
     }
     auto launch = [&](auto c_c, auto err_c) {
         constexpr int CC = decltype(c_c)::value;
@@ -777,6 +872,31 @@ int svo_launch_lk(svo_ctx *ctx, svo_pyramid *prev, const svo_pyramid *next, cons
     job.err = err;
     job.min_eig = min_eig;
     return svo_launch_lk_batch(ctx, 1, &job, prev);
+}
+
+int svo_expand_grey_storage(svo_ctx *ctx, const svo_pyramid *pyr, bool deriv)
+{
+    if (pyr->c != 3)
+        return SVO_OK;
+    LkBatchN<1> one;
+    LkJob &job = one.j[0];
+    job.prev = job.next = pyr->dev;
+    job.dprev = deriv ? pyr->dbase : nullptr;
+    job.prev_pts = job.next_pts = job.err = job.min_eig = nullptr;
+    job.status = nullptr;
+    job.d_n = nullptr;
+    job.n_cap = 0;
+    LkParams prm = {};
+    prm.max_level = pyr->levels - 1;
+    for (int l = 0; l < SVO_MAX_LEVELS; l++) {
+        prm.doff[l] = (int)pyr->doff[l];
+        prm.dpitch[l] = pyr->dpitch[l];
+        prm.gdelta[l] = pyr->gdelta[l];
+        prm.gdoff[l] = (int)pyr->gdoff[l];
+    }
+    hipLaunchKernelGGL((lk_expand_kernel<1>), dim3(EXPAND_WGS, 2, 1), dim3(64), 0, ctx->stream, one, prm, ctx->d_tickets, 1);
+    SVO_HIP(hipGetLastError());
+    return SVO_OK;
 }
 
 // number of lattice points of the reference's loop `for (v = s; v < dim - s; v += s)`

@@ -1,14 +1,20 @@
 // lk_levels.hip.h -- the level loop of lk_track_kernel (lk.hip), included INSIDE the kernel once per body: the including
-// block defines `constexpr int CA` (channels of arithmetic per pixel, out of the C the pyramids store) and `MUL = C / CA`,
+// block defines `constexpr int CA` (channels of arithmetic per pixel), `CS` (channels per pixel of the levels it stages: the
+// kernel's C, or 1 for the grey regions of grey-stored three-channel pyramids) and `MUL = C / CA`,
 // everything else is the kernel's own scope.  Text instead of a lambda or a function template on purpose: wrapped in
 // either, the same statements compiled to 2 to 4 more registers in EVERY instantiation (66 / 70 instead of 64 / 70 at
 // C == 1, 98 / 102 instead of 96 / 100 at C == 3), which costs the three-channel kernels their fifth wave per SIMD.
 // No include guard: it is meant to be included more than once.
     for (int level = prm.max_level; level >= 0; level--) {
         const int lw = prev.w[level], lh = prev.h[level];
-        const uint8_t *I = prev.lvl[level];
-        const uint8_t *J = next.lvl[level];
-        const int pitch = prev.pitch[level];
+        // CS == C: the pyramids' own levels; CS = 1 with C = 3: the grey regions of two grey-stored pyramids, a one-channel
+        // pyramid's layout (svo_internal.h)
+        const uint8_t *I = CS == C ? prev.lvl[level] : prev.lvl[level] + prm.gdelta[level];
+        const uint8_t *J = CS == C ? next.lvl[level] : next.lvl[level] + prm.gdelta[level];
+        const int pitch = CS == C ? prev.pitch[level] : svo_grey_pitch(lw);
+        const int *dlevel = dprev + (CS == C ? prm.doff[level] : prm.gdoff[level]);
+        const int dpitch = CS == C ? prm.dpitch[level] : svo_grey_dpitch(lw);
+        constexpr int TROW = Tile<CS, PT>::ROW;
         const float scale = 1.f / (float)(1 << level);
         float px = ptx * scale, py = pty * scale;
         float nxp, nyp;
@@ -54,32 +60,32 @@
                 wv1 = (w01 & 0xffff) | (w11 << 16);
             }
             wave_lds_sync();
-            TileLoad<C, PT> tload;
-            tile_issue<C, PT>(tload, I, pitch, ipx - 1, ipy - 1, lane);
-            DtileLoad<C> dload;
-            dtile_issue<C>(dload, dprev + prm.doff[level], prm.dpitch[level], ipx, ipy, lane);
-            tile_commit<C, PT, DtileLoad<C>::N>(tload, T, lane);
+            TileLoad<CS, PT> tload;
+            tile_issue<CS, PT>(tload, I, pitch, ipx - 1, ipy - 1, lane);
+            DtileLoad<CS> dload;
+            dtile_issue<CS>(dload, dlevel, dpitch, ipx, ipy, lane);
+            tile_commit<CS, PT, DtileLoad<CS>::N>(tload, T, lane);
             const uint8_t *Ts = T + tload.shift;
             wave_lds_sync();
 
-            const int toff = (int)(Ts - lds) + (wy + 1) * TROW + (wx + 1) * C;
+            const int toff = (int)(Ts - lds) + (wy + 1) * TROW + (wx + 1) * CS;
             if constexpr (IDENT) {
                 // element k is its byte of the lane's row run, times 32: one permute spreads two bytes over the
                 // halves of a dword, one shift scales both (32 * 255 stays inside its half)
-                unsigned t0[ndwords(C)];
-                load_row_packed<C>(lds, toff, t0);
+                unsigned t0[ndwords(CS)];
+                load_row_packed<CS>(lds, toff, t0);
                 ForEachElem<CA, npairs(CA)>::run([&](auto jc) {
                     constexpr int j = decltype(jc)::value, k0 = 2 * j, k1 = 2 * j + 1;
-                    constexpr int b0 = elem_at(k0, CA, C), b1 = elem_at(k1 < NE ? k1 : k0, CA, C);  // their bytes
+                    constexpr int b0 = elem_at(k0, CA, CS), b1 = elem_at(k1 < NE ? k1 : k0, CA, CS);  // their bytes
                     constexpr unsigned hi = k1 < NE ? 4u + (unsigned)(b1 & 3) : 0x0cu;
                     constexpr unsigned sel = (unsigned)(b0 & 3) | (0x0cu << 8) | (hi << 16) | (0x0cu << 24);
                     Ivp[j] = (int)(__builtin_amdgcn_perm(t0[b1 >> 2], t0[b0 >> 2], sel) << 5);
                 });
             } else {
-                unsigned t0[ndwords(C)], t1[ndwords(C)];
-                load_row_packed<C>(lds, toff, t0);
-                load_row_packed<C>(lds, toff + TROW, t1);
-                lane_samples<CA, C, W_BITS - 5>(t0, t1, wv0, wv1, Ivp);
+                unsigned t0[ndwords(CS)], t1[ndwords(CS)];
+                load_row_packed<CS>(lds, toff, t0);
+                load_row_packed<CS>(lds, toff + TROW, t1);
+                lane_samples<CA, CS, W_BITS - 5>(t0, t1, wv0, wv1, Ivp);
             }
             // the Scharr derivatives of the window's 22x22 neighbourhood come from the derivative level
             // (zero outside the image: the level's border is zero); the tile takes the place of T.
@@ -93,11 +99,11 @@
             else
                 asm volatile("" : "+v"(dl) : "v"(Ivp[0]), "v"(Ivp[1]), "v"(Ivp[2]), "v"(Ivp[3]));
             wave_lds_sync();
-            dtile_commit<C>(dload, DB, dl);
+            dtile_commit<CS>(dload, DB, dl);
             const int *D = reinterpret_cast<const int *>(DB + dload.shift);
             wave_lds_sync();
-            constexpr int DROW = DTile<C>::ROW / 4;
-            int dlane = wy * DROW + wx * C;  // this lane's first tile entry
+            constexpr int DROW = DTile<CS>::ROW / 4;
+            int dlane = wy * DROW + wx * CS;  // this lane's first tile entry
             // Derivative tile entries are (4 dx | 4 dy << 16) (pyramid.hip; |4 d| <= 16320: int16).
             if constexpr (IDENT) {
                 // element k is its entry of the lane's row run: the low (x) / high (y) halves of two entries packed by
@@ -107,7 +113,7 @@
                 int e[NE + 1];
 #pragma unroll
                 for (int k = 0; k < NE; k++)
-                    e[k] = d0[elem_at(k, CA, C)];
+                    e[k] = d0[elem_at(k, CA, CS)];
                 e[NE] = 0;
                 // (The selectors do not depend on the level.  Left to itself the compiler forms them once, before
                 // the level loop, and keeps them and their constants in registers across the iteration loop, which
@@ -140,7 +146,7 @@
                     int vx[NV], sx[NE + 1];
                     ForEachElem<CA, NV>::run([&](auto kc) {
                         constexpr int k = decltype(kc)::value;
-                        vx[k] = half_pair<false>(d0[elem_at(k, CA, C)], d1[elem_at(k, CA, C)]);
+                        vx[k] = half_pair<false>(d0[elem_at(k, CA, CS)], d1[elem_at(k, CA, CS)]);
                     });
                     sx[NE] = 0;
 #pragma unroll
@@ -158,7 +164,7 @@
                     int vy[NV], sy[NE + 1];
                     ForEachElem<CA, NV>::run([&](auto kc) {
                         constexpr int k = decltype(kc)::value;
-                        vy[k] = half_pair<true>(d0[elem_at(k, CA, C)], d1[elem_at(k, CA, C)]);
+                        vy[k] = half_pair<true>(d0[elem_at(k, CA, CS)], d1[elem_at(k, CA, CS)]);
                     });
                     sy[NE] = 0;
 #pragma unroll
@@ -230,7 +236,7 @@
         nxp -= half;
         nyp -= half;
         float pdx = 0.f, pdy = 0.f;
-        const int lane_off = wy * Tile<C, TS>::ROW + wx * C;  // this lane's row run inside the window
+        const int lane_off = wy * Tile<CS, TS>::ROW + wx * CS;  // this lane's row run inside the window
         int ox = 0, oy = 0;
         bool have_tile = false;
         int tj_off = 0;          // LDS byte offset of the staged tile's pixel (0, 0): TJ's offset + the staging shift
@@ -256,12 +262,12 @@
                 ox = inx - JR;
                 oy = iny - JR;
                 wave_lds_sync();
-                tj_off = (int)(TJ - lds) + uniform(stage_tile<C, TS>(TJ, J, pitch, ox, oy, lane));
+                tj_off = (int)(TJ - lds) + uniform(stage_tile<CS, TS>(TJ, J, pitch, ox, oy, lane));
                 wave_lds_sync();
                 have_tile = true;
             }
             int V[(SEG + 1) * CA];
-            lane_load_pairs<CA, C>(lds, lane_off + (tj_off + (iny - oy) * Tile<C, TS>::ROW + (inx - ox) * C), V);
+            lane_load_pairs<CA, CS>(lds, lane_off + (tj_off + (iny - oy) * Tile<CS, TS>::ROW + (inx - ox) * CS), V);
             const int cx = inx, cy = iny;
             for (;;) {
                 int wv0, wv1;
@@ -329,7 +335,7 @@
                     ox = iqx - JR;
                     oy = iqy - JR;
                     wave_lds_sync();
-                    tj_off = (int)(TJ - lds) + uniform(stage_tile<C, TS>(TJ, J, pitch, ox, oy, lane));
+                    tj_off = (int)(TJ - lds) + uniform(stage_tile<CS, TS>(TJ, J, pitch, ox, oy, lane));
                     wave_lds_sync();
                     have_tile = true;
                 }
@@ -346,7 +352,7 @@
                     for (int k = 0; k < npairs(CA); k++)
                         Iv0[k] = Ivp[k];
                 }
-                int s1 = lane_abs_residual<CA, C>(lds, lane_off + (tj_off + (iqy - oy) * Tile<C, TS>::ROW + (iqx - ox) * C),
+                int s1 = lane_abs_residual<CA, CS>(lds, lane_off + (tj_off + (iqy - oy) * Tile<CS, TS>::ROW + (iqx - ox) * CS),
                                               (w00 & 0xffff) | (w10 << 16), (w01 & 0xffff) | (w11 << 16), Iv0);
                 if (!active)
                     s1 = 0;

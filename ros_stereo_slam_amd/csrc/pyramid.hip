@@ -20,6 +20,8 @@
 //   4. finish:  the reflect-101 borders of levels 1.. and, in the same launch, the Scharr derivative
 //               levels of the pyramids that carry them (edge pixels through reflect-101 indices again,
 //               so the two roles are independent).
+#include <cstdlib>
+
 #include "svo_internal.h"
 
 namespace {
@@ -46,7 +48,7 @@ constexpr int SW = 2 * TW + 3, SH = 2 * TH + 3;
 constexpr int ROWS_PER_BLOCK = 8;
 constexpr int PYR_JOBS = 2 * SVO_LK_MAX_JOBS;
 
-// everything the four launches need, by value (2.4 KB of the 4 KB kernel-argument space)
+// everything the launches of a build need, by value (2.4 KB of the 4 KB kernel-argument space)
 // NJ: PYR_JOBS for the lock-step groups; 2 for a chunk on its own (its left and right image): a sixteenth of the kernel
 // arguments per launch
 template <int NJ> struct PyrBuildN {
@@ -57,6 +59,10 @@ template <int NJ> struct PyrBuildN {
     int doff[SVO_MAX_LEVELS];               // element (0, 0) of each derivative level, in ints
     int pitch[SVO_MAX_LEVELS], dpitch[SVO_MAX_LEVELS], w[SVO_MAX_LEVELS], h[SVO_MAX_LEVELS];
     int levels;
+    // grey storage of a three-channel pyramid (svo_internal.h): pixel (0, 0) of grey level l is lvl[job][l] + gdelta[l],
+    // element (0, 0) of grey derivative level l is dlvl[job] + gdoff[l]; the pitches are svo_grey_pitch / svo_grey_dpitch
+    int gdelta[SVO_MAX_LEVELS], gdoff[SVO_MAX_LEVELS];
+    int storage;  // 0: three-channel storage always (SVO_PYR_MONO_STORAGE=0)
 };
 using PyrBuild = PyrBuildN<PYR_JOBS>;
 constexpr int PYR_FEW = 2;
@@ -76,8 +82,11 @@ inline PyrBuildN<PYR_FEW> pyr_few(const PyrBuild &b)
         f.dpitch[l] = b.dpitch[l];
         f.w[l] = b.w[l];
         f.h[l] = b.h[l];
+        f.gdelta[l] = b.gdelta[l];
+        f.gdoff[l] = b.gdoff[l];
     }
     f.levels = b.levels;
+    f.storage = b.storage;
     return f;
 }
 static_assert(sizeof(PyrBuild) <= 3072, "kernel arguments are limited to 4 KB");
@@ -93,7 +102,9 @@ static_assert(sizeof(PyrBuild) <= 3072, "kernel arguments are limited to 4 KB");
 // The filter is separable and the arithmetic integer, so the order of the two passes does not change a bit
 // of the result; rows first (as until round 2) filtered 19 rows of which the vertical pass used 8 outputs'
 // worth, and was 6 % of the vector instructions of a bench run.
-template <int C, bool RAW>
+// SC: bytes from a source pixel to the next (SC = 3 with C = 1: channel 0 of a raw BGR image, for the grey storage of a
+// grey frame -- every tile then takes the byte-gathering path of the edge tiles).
+template <int C, bool RAW, int SC = C>
 __device__ __forceinline__ void down_tile(const uint8_t *__restrict__ src, int spitch, int w, int h,
                                           uint8_t *__restrict__ dst, int dpitch, int dw, int dh, int tx, int ty)
 {
@@ -108,7 +119,7 @@ __device__ __forceinline__ void down_tile(const uint8_t *__restrict__ src, int s
     // a staged dword takes two source dwords (the shift): the furthest reaches 4 * ND + 3 bytes past the tile's
     // first byte -- inside the padded level always; inside the raw image unless the tile ends at the very last
     // bytes of the buffer
-    const bool interior = x0 >= 0 && x0 + SW <= w && y0 >= 0 && y0 + SH <= h &&
+    const bool interior = SC == C && x0 >= 0 && x0 + SW <= w && y0 >= 0 && y0 + SH <= h &&
                           (!RAW || (size_t)(y0 + SH - 1) * spitch + (size_t)x0 * C + (ND + 1) * 4 + 4 <= (size_t)h * spitch);
     if (interior) {
         for (int d = tid; d < ND; d += PB) {  // a thread per dword column (C = 4: 67 columns, two turns)
@@ -132,7 +143,7 @@ __device__ __forceinline__ void down_tile(const uint8_t *__restrict__ src, int s
             for (int bb = 0; bb < 4; bb++) {
                 const int cc = min(4 * d + bb, SW * C - 1);  // the row's spare bytes repeat its last one
                 const int px = cc / C, ch = cc - px * C;
-                sx[bb] = reflect101(x0 + px, w) * C + ch;
+                sx[bb] = reflect101(x0 + px, w) * SC + ch;
             }
 #pragma unroll 4
             for (int r = 0; r < SH; r++) {
@@ -197,37 +208,21 @@ __device__ __forceinline__ void down_tile(const uint8_t *__restrict__ src, int s
 }
 
 // one row of the padded level 0 from the raw image, one thread per output dword
-// C == 3 also answers "does a pixel of this image have B != G or G != R?" for the bytes it copies anyway (the pyramid's
-// "channels agree" word, svo_internal.h): a pixel is grey iff byte i equals byte i + 1 for every i of its row with
-// i % 3 != 2, and the thread that copies row bytes k .. k+3 of an IMAGE row (not a border row, which repeats one) owns the
-// pairs that start there.  The pair (k+3, k+4) needs one byte of the neighbouring dword: the interior path has fetched it
-// (an aligned dword pair holds at least five bytes from k on), the edge path reads it.  Returns true when a pair differs.
 template <int C>
-__device__ __forceinline__ bool pad_copy_row(const uint8_t *__restrict__ src, uint8_t *__restrict__ padded, int w, int h,
+__device__ __forceinline__ void pad_copy_row(const uint8_t *__restrict__ src, uint8_t *__restrict__ padded, int w, int h,
                                              int pitch, int row, int d)
 {
     const int Y = reflect101(row - SVO_PYR_PAD, h);
     const uint8_t *srow = src + (size_t)Y * w * C;
     uint32_t out = 0;
-    bool colour = false;
     const int k = d * 4 - SVO_PYR_PAD * C;  // byte index inside the source row of the dword's first byte
-    const bool image_row = C == 3 && row >= SVO_PYR_PAD && row < SVO_PYR_PAD + h;
     if (k >= 0 && k + 4 <= w * C && (Y < h - 1 || k + 8 <= w * C) && (Y > 0 || k >= 4)) {
         // interior: four consecutive source bytes, fetched as two aligned dwords (the source rows have
         // no particular alignment); neither dword reaches outside the image buffer
         const uintptr_t a = reinterpret_cast<uintptr_t>(srow + k);
         const uint32_t *p = reinterpret_cast<const uint32_t *>(a & ~(uintptr_t)3);
-        const uint32_t lo = p[0], hi = (C == 3 || (a & 3)) ? p[1] : 0u;
+        const uint32_t lo = p[0], hi = (a & 3) ? p[1] : 0u;
         out = __builtin_amdgcn_alignbyte(hi, lo, (unsigned)(a & 3));
-        if (image_row) {
-            // bytes k+1 .. k+4 beside bytes k .. k+3; k % 3 == d % 3 (the pad is a whole number of pixels), which tells
-            // the pairs that cross from one pixel into the next: they are masked out.  Where k + 4 is the row's end,
-            // pair (k+3, k+4) is such a crossing.
-            const uint32_t nxt = (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * ((unsigned)(a & 3) + 1u)));  // bytes k+1 .. k+4
-            const int m = d % 3;
-            const uint32_t own = m == 0 ? 0xff00ffffu : m == 1 ? 0xffff00ffu : 0x00ffff00u;
-            colour = ((out ^ nxt) & own) != 0;
-        }
     } else {
 #pragma unroll
         for (int b = 0; b < 4; b++) {
@@ -238,57 +233,134 @@ __device__ __forceinline__ bool pad_copy_row(const uint8_t *__restrict__ src, ui
                 out |= (uint32_t)srow[X * C + ch] << (8 * b);
             }
         }
-        if (image_row) {
-            // the ends of a row, the first dword of the image and the last bytes of its last row: pair by pair
+    }
+    reinterpret_cast<uint32_t *>(padded + (size_t)row * pitch)[d] = out;
+}
+
+// the same for the grey storage of a grey BGR image: four pixels' channel 0 per output dword, pitch svo_grey_pitch
+__device__ __forceinline__ void pad_copy_grey_row(const uint8_t *__restrict__ src, uint8_t *__restrict__ padded, int w, int h,
+                                                  int gpitch, int row, int d)
+{
+    const uint8_t *srow = src + (size_t)reflect101(row - SVO_PYR_PAD, h) * w * 3;
+    uint32_t out = 0;
 #pragma unroll
-            for (int b = 0; b < 4; b++) {
-                const int i = k + b;
-                if (i >= 0 && i + 1 < w * C && i % 3 != 2)
-                    colour = colour || srow[i] != srow[i + 1];
+    for (int b = 0; b < 4; b++) {
+        const int px = d * 4 + b;
+        if (px < w + 2 * SVO_PYR_PAD)
+            out |= (uint32_t)srow[reflect101(px - SVO_PYR_PAD, w) * 3] << (8 * b);
+    }
+    reinterpret_cast<uint32_t *>(padded + (size_t)row * gpitch)[d] = out;
+}
+
+// The head launch of a three-channel build: does a pixel of the raw image have B != G or G != R?  The later launches of the
+// set choose their roles by the answer, so it has to be there before the first of them.  A thread takes four pixels = three
+// dwords per turn when the image is dword-aligned (byte i beside byte i + 1, the pairs that cross into the next pixel masked
+// out), pixel by pixel otherwise and at the image's last pixels.  A wave that saw a colour pixel says so: every writer stores
+// the same value, so one lane's plain store does (no atomic); a grey image causes no store at all.
+constexpr int HEAD_TURNS = 4;
+template <int NJ> __global__ __launch_bounds__(PB) void pyr_head_kernel(PyrBuildN<NJ> b)
+{
+    svo_chain_priority();
+    const int job = blockIdx.y;
+    if (b.gate[job] && *b.gate[job] == 0)
+        return;
+    const uint8_t *img = b.img[job];
+    const int npix = b.w[0] * b.h[0];
+    const bool aligned = (reinterpret_cast<uintptr_t>(img) & 3) == 0;
+    bool colour = false;
+    for (int t = 0; t < HEAD_TURNS; t++) {
+        const int q = (blockIdx.x * HEAD_TURNS + t) * PB + threadIdx.x;  // pixels 4q .. 4q + 3
+        if (4 * q >= npix)
+            break;
+        if (aligned && 4 * q + 4 <= npix) {
+            const uint32_t *p = reinterpret_cast<const uint32_t *>(img) + 3 * (size_t)q;
+            const uint32_t a = p[0], bb = p[1], c = p[2];
+            const uint32_t x = (a ^ __builtin_amdgcn_alignbyte(bb, a, 1)) & 0xff00ffffu;   // pairs from bytes 0, 1, 3
+            const uint32_t y = (bb ^ __builtin_amdgcn_alignbyte(c, bb, 1)) & 0xffff00ffu;  // 4, 6, 7
+            const uint32_t z = (c ^ (c >> 8)) & 0x00ffff00u;                               // 9, 10
+            colour = colour || (x | y | z) != 0;
+        } else {
+            for (int i = 4 * q; i < min(4 * q + 4, npix); i++) {
+                const uint8_t *px = img + 3 * (size_t)i;
+                colour = colour || px[0] != px[1] || px[1] != px[2];
             }
         }
     }
-    reinterpret_cast<uint32_t *>(padded + (size_t)row * pitch)[d] = out;
-    return colour;
+    const unsigned long long saw = __builtin_amdgcn_ballot_w64(colour);
+    if (saw != 0 && (int)(threadIdx.x & 63) == __builtin_ctzll(saw))
+        svo_pyr_words(b.lvl[job][0] - (size_t)SVO_PYR_PAD * b.pitch[0] - SVO_PYR_PAD * 3)[SVO_PYR_COLOUR_SEEN] = 1;
 }
 
-// launch 1: workgroups [0, n_tiles) build level 1 from the raw image, the rest the padded level 0
+// Does this build of a three-channel pyramid store grey?  The head launch has finished (same stream): a scalar load and a
+// scalar branch per workgroup.  The base launch asks the collecting word, and one of its threads leaves the answer in
+// SVO_PYR_STORED for the launches after it (the finishing launch clears the collecting word, so it cannot ask it).
+template <int NJ> __device__ __forceinline__ int *pyr_words_of(const PyrBuildN<NJ> &b, int job, int C)
+{
+    return svo_pyr_words(b.lvl[job][0] - (size_t)SVO_PYR_PAD * b.pitch[0] - SVO_PYR_PAD * C);
+}
+
+// the base launch: workgroups [0, n_tiles) build level 1 from the raw image, the rest the padded level 0
 template <int C, int NJ> __global__ __launch_bounds__(PB) void pyr_base_kernel(PyrBuildN<NJ> b, int tiles_x, int n_tiles, int pad_x)
 {
     svo_chain_priority();
     const int job = blockIdx.y;
     if (b.gate[job] && *b.gate[job] == 0)
         return;
+    bool grey = false;
+    if constexpr (C == 3) {
+        int *words = pyr_words_of(b, job, C);
+        grey = b.storage && __builtin_amdgcn_readfirstlane(words[SVO_PYR_COLOUR_SEEN]) == 0;
+        if (blockIdx.x == 0 && threadIdx.x == 0)
+        {
+            words[SVO_PYR_STORED] = grey ? 1 : 3;
+            words[SVO_PYR_COLOUR_VALID] = 0;  // here too: a one-level build without derivative levels has no finishing launch
+        }
+    }
     if ((int)blockIdx.x < n_tiles) {
-        if (b.levels > 1)
-            down_tile<C, true>(b.img[job], b.w[0] * C, b.w[0], b.h[0], b.lvl[job][1], b.pitch[1], b.w[1], b.h[1],
-                               blockIdx.x % tiles_x, blockIdx.x / tiles_x);
+        if (b.levels > 1) {
+            if (C == 3 && grey)
+                down_tile<1, true, 3>(b.img[job], b.w[0] * 3, b.w[0], b.h[0], b.lvl[job][1] + b.gdelta[1], svo_grey_pitch(b.w[1]),
+                                      b.w[1], b.h[1], blockIdx.x % tiles_x, blockIdx.x / tiles_x);
+            else
+                down_tile<C, true>(b.img[job], b.w[0] * C, b.w[0], b.h[0], b.lvl[job][1], b.pitch[1], b.w[1], b.h[1],
+                                   blockIdx.x % tiles_x, blockIdx.x / tiles_x);
+        }
         return;
     }
     const int i = blockIdx.x - n_tiles;
     const int d = (i % pad_x) * PB + threadIdx.x, rb = i / pad_x;
+    const int row0 = rb * ROWS_PER_BLOCK, rend = min(row0 + ROWS_PER_BLOCK, b.h[0] + 2 * SVO_PYR_PAD);
+    if (C == 3 && grey) {
+        const int gpitch = svo_grey_pitch(b.w[0]);
+        if (d >= (gpitch >> 2))
+            return;
+        uint8_t *padded = b.lvl[job][0] + b.gdelta[0] - (size_t)SVO_PYR_PAD * gpitch - SVO_PYR_PAD;
+        for (int row = row0; row < rend; row++)
+            pad_copy_grey_row(b.img[job], padded, b.w[0], b.h[0], gpitch, row, d);
+        return;
+    }
     if (d >= (b.pitch[0] >> 2))
         return;
     uint8_t *padded = b.lvl[job][0] - (size_t)SVO_PYR_PAD * b.pitch[0] - SVO_PYR_PAD * C;
-    bool colour = false;
-    for (int row = rb * ROWS_PER_BLOCK, rend = min(row + ROWS_PER_BLOCK, b.h[0] + 2 * SVO_PYR_PAD); row < rend; row++)
-        colour = pad_copy_row<C>(b.img[job], padded, b.w[0], b.h[0], b.pitch[0], row, d) || colour;
-    if constexpr (C == 3) {
-        // a wave that saw a colour pixel says so: every writer stores the same value, so one lane's plain store does
-        // (no atomic); a grey image causes no store at all.  pyr_finish_kernel publishes and clears the word.
-        const unsigned long long saw = __builtin_amdgcn_ballot_w64(colour);
-        if (saw != 0 && (int)(threadIdx.x & 63) == __builtin_ctzll(saw))
-            svo_pyr_words(padded)[SVO_PYR_COLOUR_SEEN] = 1;
-    }
+    for (int row = row0; row < rend; row++)
+        pad_copy_row<C>(b.img[job], padded, b.w[0], b.h[0], b.pitch[0], row, d);
 }
 
-// launches 2 and 3: level l from level l - 1
+// the down launches: level l from level l - 1
 template <int C, int NJ> __global__ __launch_bounds__(PB) void pyr_down_kernel(PyrBuildN<NJ> b, int l)
 {
     svo_chain_priority();
-    if (b.gate[blockIdx.z] && *b.gate[blockIdx.z] == 0)
+    const int job = blockIdx.z;
+    if (b.gate[job] && *b.gate[job] == 0)
         return;
-    down_tile<C, false>(b.lvl[blockIdx.z][l - 1], b.pitch[l - 1], b.w[l - 1], b.h[l - 1], b.lvl[blockIdx.z][l], b.pitch[l],
+    if constexpr (C == 3) {
+        if (__builtin_amdgcn_readfirstlane(pyr_words_of(b, job, C)[SVO_PYR_STORED]) == 1) {
+            down_tile<1, false>(b.lvl[job][l - 1] + b.gdelta[l - 1], svo_grey_pitch(b.w[l - 1]), b.w[l - 1], b.h[l - 1],
+                                b.lvl[job][l] + b.gdelta[l], svo_grey_pitch(b.w[l]), b.w[l], b.h[l], blockIdx.x, blockIdx.y);
+            return;
+        }
+    }
+    down_tile<C, false>(b.lvl[job][l - 1], b.pitch[l - 1], b.w[l - 1], b.h[l - 1], b.lvl[job][l], b.pitch[l],
                         b.w[l], b.h[l], blockIdx.x, blockIdx.y);
 }
 
@@ -415,32 +487,23 @@ struct FinishPlan {
     int scharr_y0[SVO_MAX_LEVELS + 1];  // first blockIdx.y of level l's Scharr role; [levels] = end
     int publish;                        // 1: the launch ends a build from raw images (0: svo_build_derivatives)
 };
-template <int C, int NJ> __global__ __launch_bounds__(PB) void pyr_finish_kernel(PyrBuildN<NJ> b, FinishPlan plan)
+// the two roles of the finishing launch for a pyramid of S stored channels: levels at lvl[l] + ldelta[l] with pitch(l),
+// derivative levels at dlvl + ldoff[l] with dpitch(l)
+template <int S, int NJ, class Pitch, class DPitch>
+__device__ __forceinline__ void finish_roles(const PyrBuildN<NJ> &b, const FinishPlan &plan, int job, int by, const int (&ldelta)[SVO_MAX_LEVELS],
+                                             const int (&ldoff)[SVO_MAX_LEVELS], Pitch pitch, DPitch dpitch)
 {
-    svo_chain_priority();
-    const int job = blockIdx.z, by = blockIdx.y;
-    if (b.gate[job] && *b.gate[job] == 0)
-        return;
-    if constexpr (C == 3) {
-        // one thread per pyramid publishes what the base launch saw (same stream, finished by now) and clears the
-        // collecting word for the next build; a gated build has left above and keeps both words
-        if (plan.publish && blockIdx.x == 0 && by == 0 && threadIdx.x == 0) {
-            int *words = svo_pyr_words(b.lvl[job][0] - (size_t)SVO_PYR_PAD * b.pitch[0] - SVO_PYR_PAD * C);
-            words[SVO_PYR_MONO] = words[SVO_PYR_COLOUR_SEEN] == 0;
-            words[SVO_PYR_COLOUR_SEEN] = 0;
-        }
-    }
     if (by < plan.border_y0[b.levels]) {
         int l = 1;
         for (int i = 2; i < b.levels; i++)
             l = by >= plan.border_y0[i] ? i : l;
         const int d = blockIdx.x * PB + threadIdx.x;
-        if (d >= (b.pitch[l] >> 2))
+        if (d >= (pitch(l) >> 2))
             return;
-        uint8_t *padded = b.lvl[job][l] - (size_t)SVO_PYR_PAD * b.pitch[l] - SVO_PYR_PAD * C;
+        uint8_t *padded = b.lvl[job][l] + ldelta[l] - (size_t)SVO_PYR_PAD * pitch(l) - SVO_PYR_PAD * S;
         for (int row = (by - plan.border_y0[l]) * ROWS_PER_BLOCK, rend = min(row + ROWS_PER_BLOCK, b.h[l] + 2 * SVO_PYR_PAD);
              row < rend; row++)
-            fill_border_row<C>(padded, b.w[l], b.h[l], b.pitch[l], row, d);
+            fill_border_row<S>(padded, b.w[l], b.h[l], pitch(l), row, d);
         return;
     }
     if (!b.dlvl[job])
@@ -449,13 +512,45 @@ template <int C, int NJ> __global__ __launch_bounds__(PB) void pyr_finish_kernel
     for (int i = 1; i < b.levels; i++)
         l = by >= plan.scharr_y0[i] ? i : l;
     const int q = blockIdx.x * PB + threadIdx.x;  // quad of channel-bytes 4q .. 4q+3 of the row
-    if (4 * q >= b.w[l] * C)
+    if (4 * q >= b.w[l] * S)
         return;
     int edge_off[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (scharr_edge<C>(b.w[l], q))
-        scharr_edge_offsets<C>(b.w[l], q, edge_off);
+    if (scharr_edge<S>(b.w[l], q))
+        scharr_edge_offsets<S>(b.w[l], q, edge_off);
     for (int y = (by - plan.scharr_y0[l]) * ROWS_PER_BLOCK, yend = min(y + ROWS_PER_BLOCK, b.h[l]); y < yend; y++)
-        scharr_row<C>(b.lvl[job][l], b.dlvl[job] + b.doff[l], b.pitch[l], b.dpitch[l], b.w[l], b.h[l], y, q, edge_off);
+        scharr_row<S>(b.lvl[job][l] + ldelta[l], b.dlvl[job] + ldoff[l], pitch(l), dpitch(l), b.w[l], b.h[l], y, q, edge_off);
+}
+
+template <int C, int NJ> __global__ __launch_bounds__(PB) void pyr_finish_kernel(PyrBuildN<NJ> b, FinishPlan plan)
+{
+    svo_chain_priority();
+    const int job = blockIdx.z, by = blockIdx.y;
+    if (b.gate[job] && *b.gate[job] == 0)
+        return;
+    if constexpr (C == 3) {
+        int *words = pyr_words_of(b, job, C);
+        const bool grey = __builtin_amdgcn_readfirstlane(words[SVO_PYR_STORED]) == 1;
+        // one thread per pyramid publishes what the head launch saw (same stream, finished by now) and clears the
+        // collecting word for the next build; a gated build has left above and keeps every word.  What a grey-stored
+        // pyramid's three-channel regions held is stale now: levels and derivative levels after a build, the derivative
+        // levels after svo_build_derivatives.  (No other thread of this launch reads the words written here.)
+        if (blockIdx.x == 0 && by == 0 && threadIdx.x == 0) {
+            if (plan.publish) {
+                words[SVO_PYR_MONO] = words[SVO_PYR_COLOUR_SEEN] == 0;
+                words[SVO_PYR_COLOUR_SEEN] = 0;
+                words[SVO_PYR_COLOUR_VALID] = 0;
+            } else {
+                words[SVO_PYR_COLOUR_VALID] &= ~2;
+            }
+        }
+        if (grey) {
+            finish_roles<1>(b, plan, job, by, b.gdelta, b.gdoff, [&](int l) { return svo_grey_pitch(b.w[l]); },
+                            [&](int l) { return svo_grey_dpitch(b.w[l]); });
+            return;
+        }
+    }
+    const int zero[SVO_MAX_LEVELS] = {0, 0, 0, 0};
+    finish_roles<C>(b, plan, job, by, zero, b.doff, [&](int l) { return b.pitch[l]; }, [&](int l) { return b.dpitch[l]; });
 }
 
 }  // namespace
@@ -472,6 +567,12 @@ static int alloc_derivative_levels(svo_ctx *ctx, svo_pyramid *p)
         p->doff[l] = ints + (size_t)SVO_DERIV_PAD * (p->dpitch[l] / 4) + (size_t)SVO_DERIV_PAD * p->c;
         ints += (lvl_ints + 63) & ~(size_t)63;  // levels start 256-byte aligned
     }
+    if (p->c == 3)  // the grey derivative levels, behind the three-channel ones, in a one-channel pyramid's layout
+        for (int l = 0; l < p->levels; l++) {
+            const int gdp = svo_grey_dpitch(p->dev.w[l]);
+            p->gdoff[l] = ints + (size_t)SVO_DERIV_PAD * (gdp / 4) + (size_t)SVO_DERIV_PAD;
+            ints += ((size_t)(gdp / 4) * (p->dev.h[l] + 2 * SVO_DERIV_PAD) + 63) & ~(size_t)63;
+        }
     const size_t dbytes = ints * 4 + 1024;  // slack: 16-byte tile loads run a few vectors past a row
     hipError_t e = hipMalloc((void **)&p->dbase, dbytes);
     if (e == hipSuccess)
@@ -497,8 +598,14 @@ static void fill_build(PyrBuild &b, int k, svo_pyramid *const *pyrs, const uint8
         b.h[l] = p0->dev.h[l];
         b.dpitch[l] = 0;
         b.doff[l] = 0;
+        b.gdelta[l] = p0->gdelta[l];
+        b.gdoff[l] = 0;
     }
     b.levels = p0->levels;
+    // grey frames given as BGR are stored in one channel (the build's own choice per pyramid, from the head launch's word);
+    // SVO_PYR_MONO_STORAGE=0 keeps three-channel storage always (the same read-backs and tracks), for an A/B and for the tests
+    static const int mono_storage = getenv("SVO_PYR_MONO_STORAGE") ? atoi(getenv("SVO_PYR_MONO_STORAGE")) : 1;
+    b.storage = mono_storage;
     for (int a = 0; a < PYR_JOBS; a++) {
         svo_pyramid *p = pyrs[a < k ? a : 0];
         b.img[a] = d_images ? d_images[a < k ? a : 0] : nullptr;
@@ -510,6 +617,7 @@ static void fill_build(PyrBuild &b, int k, svo_pyramid *const *pyrs, const uint8
             for (int l = 0; l < SVO_MAX_LEVELS; l++) {
                 b.dpitch[l] = p->dpitch[l];
                 b.doff[l] = (int)p->doff[l];
+                b.gdoff[l] = (int)p->gdoff[l];
             }
     }
 }
@@ -589,6 +697,13 @@ static int build_levels(svo_ctx *ctx, int k, svo_pyramid *const *pyrs, const uin
 {
     PyrBuild b;
     fill_build(b, k, pyrs, d_images, false, gates);
+    if constexpr (C == 3) {
+        const int quads = (b.w[0] * b.h[0] + 3) / 4, gx = (quads + PB * HEAD_TURNS - 1) / (PB * HEAD_TURNS);
+        if (k <= PYR_FEW)
+            hipLaunchKernelGGL((pyr_head_kernel<PYR_FEW>), dim3(gx, k), dim3(PB), 0, ctx->stream, pyr_few(b));
+        else
+            hipLaunchKernelGGL((pyr_head_kernel<PYR_JOBS>), dim3(gx, k), dim3(PB), 0, ctx->stream, b);
+    }
     {
         const int tiles_x = b.levels > 1 ? (b.w[1] + TW - 1) / TW : 0, tiles_y = b.levels > 1 ? (b.h[1] + TH - 1) / TH : 0;
         const int n_tiles = tiles_x * tiles_y;
@@ -695,6 +810,14 @@ int svo_pyramid_create_ex(svo_ctx *ctx, int width, int height, int channels, int
         w = (w + 1) / 2;
         h = (h + 1) / 2;
     }
+    if (channels == 3)  // the grey levels, behind the three-channel ones, in a one-channel pyramid's layout
+        for (int l = 0; l < levels; l++) {
+            const int gp = svo_grey_pitch(p->dev.w[l]);
+            p->goff[l] = off;
+            p->gdelta[l] = (int)((p->goff[l] + (size_t)SVO_PYR_PAD * gp + SVO_PYR_PAD) -
+                                 (p->off[l] + (size_t)SVO_PYR_PAD * p->dev.pitch[l] + (size_t)SVO_PYR_PAD * channels));
+            off += ((size_t)gp * (p->dev.h[l] + 2 * SVO_PYR_PAD) + 255) & ~(size_t)255;
+        }
     p->bytes = off + 256;  // slack: 16-byte tile loads may run a few bytes past the last row
     hipError_t e = hipMalloc((void **)&p->base, p->bytes);
     if (e != hipSuccess) {
@@ -785,6 +908,9 @@ int svo_pyramid_get_level(svo_ctx *ctx, const svo_pyramid *pyr, int level, uint8
     if (h)
         *h = pyr->dev.h[level];
     if (out) {
+        const int rc = svo_expand_grey_storage(ctx, pyr, false);
+        if (rc)
+            return rc;
         const size_t rowb = (size_t)pyr->dev.w[level] * pyr->c;
         SVO_HIP(hipMemcpy2DAsync(out, rowb, pyr->origin(level), pyr->dev.pitch[level], rowb,
                                  pyr->dev.h[level],
@@ -811,6 +937,9 @@ int svo_pyramid_get_padded_level(svo_ctx *ctx, const svo_pyramid *pyr, int level
     if (ph)
         *ph = H;
     if (out) {
+        const int rc = svo_expand_grey_storage(ctx, pyr, false);
+        if (rc)
+            return rc;
         const size_t rowb = (size_t)W * pyr->c;  // the pitch's slack is dropped
         SVO_HIP(hipMemcpy2DAsync(out, rowb, pyr->base + pyr->off[level], pyr->dev.pitch[level], rowb, H,
                                  mem == SVO_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
@@ -834,6 +963,9 @@ int svo_pyramid_get_derivative_level(svo_ctx *ctx, const svo_pyramid *pyr, int l
     if (ph)
         *ph = H;
     if (out) {
+        const int rc = svo_expand_grey_storage(ctx, pyr, true);
+        if (rc)
+            return rc;
         const size_t rowb = (size_t)W * pyr->c * sizeof(int32_t);
         // doff names element (0, 0): the padded level starts SVO_DERIV_PAD rows and pixels in front of it
         const int *first = pyr->dbase + pyr->doff[level] - (size_t)SVO_DERIV_PAD * (pyr->dpitch[level] / 4) -

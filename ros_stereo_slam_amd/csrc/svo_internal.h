@@ -21,6 +21,9 @@
 // independent jobs one batched launch may carry (chunks of a context that run in lock step)
 #define SVO_LK_MAX_JOBS 16
 
+#define SVO_N_TICKETS 64
+static_assert(32 + 2 * SVO_LK_MAX_JOBS <= SVO_N_TICKETS, "svo_ctx::d_tickets: lk_expand_kernel's slots end past the allocation");
+
 void svo_set_error(const char *fmt, ...);
 
 // The short kernels between two tracking launches (F-RANSAC, PnP, ANMS, compaction, pyramids) run beside the
@@ -64,18 +67,44 @@ struct Mat34 {
     double m[12];
 };
 
-// Two device words per pyramid live in a header of SVO_PYR_HEADER bytes in front of level 0's padded buffer, i.e. at
+// A few device words per pyramid live in a header of SVO_PYR_HEADER bytes in front of level 0's padded buffer, i.e. at
 // lvl[0] - PAD * pitch[0] - PAD * c - SVO_PYR_HEADER: whoever holds the PyrDev finds them, no pointer of their own.
 //   SVO_PYR_MONO         1: the image the pyramid was last built from has B == G == R in every pixel (c == 3 only;
 //                        pyramids of 1 or 4 channels, and pyramids never built, say 0).  Published by the finishing launch
 //                        of a build, left alone by a gated build and by svo_build_derivatives.
-//   SVO_PYR_COLOUR_SEEN  collects during the base launch of a build, cleared when SVO_PYR_MONO is published
+//   SVO_PYR_COLOUR_SEEN  collects during the head launch of a build, cleared when SVO_PYR_MONO is published
+//   SVO_PYR_STORED       channels the last build stored: 1 = the grey regions (below) hold the levels and derivative levels,
+//                        anything else = the three-channel regions do.  Written by the base launch of a c == 3 build.
+//   SVO_PYR_COLOUR_VALID of a grey-stored pyramid: bit 0 = the three-channel levels, bit 1 = the three-channel derivative
+//                        levels have been expanded from the grey ones since the last build (lk.hip: lk_expand_kernel)
+// Grey storage (c == 3 only): a grey frame given as BGR is stored ONCE, in regions of their own behind the three-channel
+// levels (svo_pyramid::goff) and behind the three-channel derivative levels (svo_pyramid::gdoff), each in exactly the
+// layout of a one-channel pyramid of the same size: pitches svo_grey_pitch / svo_grey_dpitch.  Pixel (0, 0) of grey level l
+// lies svo_pyramid::gdelta[l] bytes behind pixel (0, 0) of level l: the same for every pyramid of one geometry, so the
+// kernels get it by value.
 #define SVO_PYR_HEADER 256
-enum { SVO_PYR_MONO = 0, SVO_PYR_COLOUR_SEEN = 1 };
+enum { SVO_PYR_MONO = 0, SVO_PYR_COLOUR_SEEN = 1, SVO_PYR_STORED = 2, SVO_PYR_COLOUR_VALID = 3 };
 // `padded`: the first byte of level 0's padded buffer
 __host__ __device__ __forceinline__ int *svo_pyr_words(const uint8_t *padded)
 {
     return reinterpret_cast<int *>(const_cast<uint8_t *>(padded) - SVO_PYR_HEADER);
+}
+__host__ __device__ __forceinline__ int svo_grey_pitch(int w) { return (w + 2 * SVO_PYR_PAD + 15) & ~15; }
+__host__ __device__ __forceinline__ int svo_grey_dpitch(int w) { return ((w + 2 * 32 /* SVO_DERIV_PAD */) * 4 + 15) & ~15; }
+// Level-0 pixel (x, y) of a pyramid of c channels for the colour gathers (geometry.hip): the address of its first byte and
+// the step to its next channel (0 where one stored byte stands for all three); gdelta0: svo_pyramid::gdelta[0]
+__device__ __forceinline__ const uint8_t *svo_pyr_pixel0(const uint8_t *lvl0, int pitch, int c, int w, int gdelta0, int x, int y,
+                                                         int *step)
+{
+    *step = c >= 3 ? 1 : 0;
+    if (c == 3) {
+        const int *words = svo_pyr_words(lvl0 - (ptrdiff_t)SVO_PYR_PAD * pitch - SVO_PYR_PAD * c);
+        if (words[SVO_PYR_STORED] == 1) {
+            *step = 0;
+            return lvl0 + gdelta0 + (ptrdiff_t)y * svo_grey_pitch(w) + x;
+        }
+    }
+    return lvl0 + (size_t)y * pitch + x * c;
 }
 
 struct svo_pyramid {
@@ -95,10 +124,16 @@ struct svo_pyramid {
     int *dbase = nullptr;
     size_t doff[SVO_MAX_LEVELS] = {0, 0, 0, 0};  // in ints: element (0, 0) of each level
     int dpitch[SVO_MAX_LEVELS] = {0, 0, 0, 0};   // bytes
+    // grey storage (c == 3): offsets in `base` of the grey levels' padded buffers, and element (0, 0) of the grey
+    // derivative levels in `dbase` (in ints)
+    size_t goff[SVO_MAX_LEVELS] = {0, 0, 0, 0}, gdoff[SVO_MAX_LEVELS] = {0, 0, 0, 0};
+    int gdelta[SVO_MAX_LEVELS] = {0, 0, 0, 0};  // bytes from origin(l) to pixel (0, 0) of grey level l
     bool want_deriv = true, has_deriv = false;
 };
 #define SVO_DERIV_PAD 32
 int svo_build_derivatives(svo_ctx *ctx, int k, svo_pyramid *const *pyrs);
+// lk.hip: a grey-stored pyramid's three-channel levels (and derivative levels) for the read-backs
+int svo_expand_grey_storage(svo_ctx *ctx, const svo_pyramid *pyr, bool deriv);
 int svo_pyramid_create_ex(svo_ctx *ctx, int width, int height, int channels, int levels, bool want_deriv,
                           svo_pyramid **out);
 
@@ -127,7 +162,9 @@ struct svo_ctx {
     DevBuf s_img, s_a, s_b, s_c, s_d, s_e, s_f, s_g;
     // work buffers used inside multi-kernel entry points
     DevBuf w_a, w_b, w_c, w_d, w_e;
-    unsigned *d_tickets = nullptr;  // 64 zeroed counters for "last workgroup finishes the job" kernels (self-resetting)
+    // SVO_N_TICKETS zeroed counters for "last workgroup finishes the job" kernels (self-resetting): 0..15 fransac.hip,
+    // 16..31 pnp.hip, 32.. lk.hip (lk_expand_kernel: one per job and image of a tracking launch)
+    unsigned *d_tickets = nullptr;
     void *pinned = nullptr;  // small pinned host block for scalar read-backs
     size_t pinned_bytes = 0;
     hipEvent_t wait_ev = nullptr;  // svo_wait(): event polled by the host
