@@ -255,6 +255,37 @@ int svo_sor_filter_large(svo_ctx *ctx, const float *xyz, const float *color, int
                          float z_limit, float *xyz_out, float *color_out, int *n_out, float *mean_dist_out,
                          int *n_pass_out, int mem);
 
+/* ---- voxel-grid down-sampling: Open3D's voxel_down_sample, the filter both clouds of the multiway-registration recipe pass
+ * through before estimate_normals and registration_icp -- the recipe PoseGraphOptimize's downSampleFactor * 15 / * 1.5 come from,
+ * src/ROSslam.py:34-40 (every recalled point and every choice of ours: tests/voxel_numpy.py) --------------
+ * xyz / color: n x 3 floats, n in 0 ... 4194304 (2^22, else SVO_ERR_CAPACITY); color may be NULL, then color_out is ignored.
+ *   1. A point with a NaN or infinite coordinate is dropped and takes part in nothing (svo_sor_filter_large's rule).
+ *   2. min_bound[a] = (double)min_a - voxel_size * 0.5 over the remaining points.
+ *   3. The cell of a point on axis a is (int64)floor(((double)p_a - min_bound[a]) / voxel_size): a double subtraction, a double
+ *      division, floor; no reciprocal, no contraction.
+ *   4. The key of a cell is (i_z << 42) | (i_y << 21) | i_x.  An axis that spans 2^21 cells or more (cells = the cell of the
+ *      largest coordinate + 1, svo_voxel_grid) is refused with SVO_ERR_CAPACITY and nothing is written: Open3D's "voxel_size is
+ *      too small".  It is decided on the host from the finite bounds before any key is formed; hence no index reaches 2^21.
+ *   5. One output row per occupied cell, in ascending key order: per component the double sum of the cell's points, taken left
+ *      to right in ascending input index, divided by (double)count and rounded to float at the store; colours likewise.
+ *   6. point_voxel (optional, n ints): the output row of every input point, -1 for a dropped one.  voxel_count (optional): the
+ *      points of every output row.
+ * Every output has n rows of capacity; rows past *n_out are left as they were.  *n_out is a HOST int in both modes and the call
+ * waits for it (and for the outputs).  In device mode the outputs must not overlap the inputs.  SVO_ERR_ARG, with nothing written:
+ * a null ctx, n < 0, a voxel_size that is <= 0, NaN or infinite, an unknown mem, a null xyz, xyz_out or n_out with n > 0, a null
+ * color_out with colours given.  n == 0 and a cloud whose every point is non-finite give *n_out = 0 and SVO_OK (point_voxel, when
+ * given, is all -1).  The sums are serial by definition: a cloud that falls into one cell costs one dependent double addition per
+ * point.  Left out: averaged normals (svo_cloud_estimate_normals runs after the down-sample, as in the recipe), PCL's VoxelGrid
+ * (float centroids, a leaf origin at multiples of the leaf) and a down-sample inside svo_map_*.
+ *
+ * svo_voxel_grid: host code, no context -- steps 2 and 4 for a cloud's finite bounds: min_bound3 and the cells each axis spans
+ * (INT64_MAX where the count passes 2^62).  SVO_OK; SVO_ERR_CAPACITY with both outputs written when an axis spans 2^21 cells or
+ * more (what svo_voxel_downsample refuses); SVO_ERR_ARG with nothing written for a null pointer, a voxel_size as above, a bound
+ * that is not finite or max below min.                                                                                          */
+int svo_voxel_downsample(svo_ctx *ctx, const float *xyz, const float *color, int n, double voxel_size,
+                         float *xyz_out, float *color_out, int *n_out, int *point_voxel, int *voxel_count, int mem);
+int svo_voxel_grid(const float *min_xyz, const float *max_xyz, double voxel_size, double *min_bound3, int64_t *cells3);
+
 /* ---- dense stereo: StereoProcess::stereoMatch / reprojectDisparity, src/StereoCV.cpp:21-59,227-250 -- */
 /* cv::StereoSGBM::create(1, 96, 7, 24, 96, 0, 60, 0, 3000, 5) + compute(grey1, grey2, disp) of
  * src/StereoCV.cpp:40-53 (MODE_SGBM: five paths, BT costs, median 3, filterSpeckles).  The recipe

@@ -98,8 +98,37 @@ class StereoProcess {
     // colour as the uint8_t r = colorMap.z, g = .y, b = .x fields (clamped to 0..255, truncated), then
     // pcl::StatisticalOutlierRemoval with MeanK 20 and StddevMulThresh 0.8 (svo_sor_filter_large, at most 2^22
     // points).  The kept points (x, y, z) and colours (r, g, b) go to publishedCloud / publishedColors, in input order;
-    // pts3d and colorMap are left as they are.
+    // pts3d and colorMap are left as they are.  voxelLeaf > 0 (ours, opt-in; 0, the default, changes nothing): the converted cloud
+    // first goes through voxelDownSample's filter at that leaf, in PCL's frame and units.
     std::vector<Point3f> publishedCloud, publishedColors;
+    double voxelLeaf = 0;
+    // Open3D's voxel_down_sample (svo_voxel_downsample): pts and colours are REPLACED by one point per
+    // occupied voxel of edge `leaf`, the mean of the voxel's points and of their colours, in ascending voxel order.  Points with
+    // a non-finite coordinate are dropped.  At most 2^22 points.
+    void voxelDownSample(std::vector<Point3f> &pts, std::vector<Point3f> &colours, double leaf)
+    {
+        if (colours.size() < pts.size())
+            throw std::invalid_argument("voxelDownSample: a colour for every point is needed");
+        const size_t n = pts.size();
+        if (n > (size_t)(1 << 22))
+            throw std::length_error("voxelDownSample: at most 2^22 points");
+        std::vector<float> xyz(n * 3), bgr(n * 3), xyz_out(n * 3), bgr_out(n * 3);
+        for (size_t i = 0; i < n; i++) {
+            xyz[3 * i] = pts[i].x, xyz[3 * i + 1] = pts[i].y, xyz[3 * i + 2] = pts[i].z;
+            bgr[3 * i] = colours[i].x, bgr[3 * i + 1] = colours[i].y, bgr[3 * i + 2] = colours[i].z;
+        }
+        int rows = 0;
+        check(svo_voxel_downsample(ctx(), xyz.data(), bgr.data(), (int)n, leaf, xyz_out.data(), bgr_out.data(), &rows, nullptr,
+                                   nullptr, SVO_MEM_HOST));
+        pts.clear();
+        colours.clear();
+        pts.reserve(rows);
+        colours.reserve(rows);
+        for (int i = 0; i < rows; i++) {
+            pts.emplace_back(xyz_out[3 * i], xyz_out[3 * i + 1], xyz_out[3 * i + 2]);
+            colours.emplace_back(bgr_out[3 * i], bgr_out[3 * i + 1], bgr_out[3 * i + 2]);
+        }
+    }
     void pclPublish(std::vector<Point3f> &pts3d, std::vector<Point3f> &colorMap)
     {
         publishedCloud.clear();
@@ -119,8 +148,15 @@ class StereoProcess {
             rgb[3 * i + 1] = pcl_channel(colorMap[i].y);
             rgb[3 * i + 2] = pcl_channel(colorMap[i].x);
         }
+        int n_sor = (int)n;
+        if (voxelLeaf > 0 && n > 0) {  // the voxel grid every PCL pipeline puts in front of the outlier removal: opt-in
+            check(svo_voxel_downsample(ctx(), xyz.data(), rgb.data(), (int)n, voxelLeaf, xyz_out.data(), rgb_out.data(), &n_sor,
+                                       nullptr, nullptr, SVO_MEM_HOST));
+            xyz.swap(xyz_out);
+            rgb.swap(rgb_out);
+        }
         int kept = 0;
-        check(svo_sor_filter_large(ctx(), xyz.data(), rgb.data(), (int)n, 20, 0.8, 0.0f, xyz_out.data(), rgb_out.data(),
+        check(svo_sor_filter_large(ctx(), xyz.data(), rgb.data(), n_sor, 20, 0.8, 0.0f, xyz_out.data(), rgb_out.data(),
                                    &kept, nullptr, nullptr, SVO_MEM_HOST));
         publishedCloud.reserve(kept);
         publishedColors.reserve(kept);

@@ -1247,6 +1247,58 @@ def sor_filter_large(self, xyz, color=None, mean_k=20, stddev_mul=0.8, z_limit=0
     return xo[:k].copy(), (co[:k].copy() if co is not None else None), md[:p].copy()
 
 
+def voxel_grid(min_xyz, max_xyz, voxel_size):
+    """``svo_voxel_grid`` (host code, no context): the grid of a cloud's finite bounds -> (min_bound [3] float64, cells [3]
+    int64, fits); fits is False when an axis spans 2^21 cells or more, which ``voxel_downsample`` refuses."""
+    lo = np.ascontiguousarray(min_xyz, np.float32).reshape(3)
+    hi = np.ascontiguousarray(max_xyz, np.float32).reshape(3)
+    mb, cells = np.zeros(3, np.float64), np.zeros(3, np.int64)
+    rc = load().svo_voxel_grid(_ptr(lo), _ptr(hi), C.c_double(voxel_size), _ptr(mb), _ptr(cells))
+    if rc != SVO_ERR_CAPACITY:
+        _check(rc)
+    return mb, cells, rc == SVO_OK
+
+
+@_ctx_method
+def voxel_downsample(self, xyz, voxel_size, color=None, trace=False, mem=None):
+    """``svo_voxel_downsample``: one point per occupied voxel of edge ``voxel_size``, the mean of the voxel's points (and colours),
+    in ascending voxel key order.  numpy arrays, or device tensors (float32, n x 3, on the context's device) which give device
+    tensors back; ``mem`` may say which explicitly.  -> (xyz_out, color_out or None[, point_voxel, voxel_count]); point_voxel:
+    the output row of every input point, -1 for a point with a non-finite coordinate."""
+    device = _is_device(xyz) if mem is None else mem == MEM_DEVICE
+    if device:
+        import torch
+
+        assert _is_device(xyz) and (color is None or _is_device(color)), "xyz and color must live in the same memory"
+        xt = xyz.reshape(-1, 3).contiguous()
+        ct = None if color is None else color.reshape(-1, 3).contiguous()
+        assert xt.dtype == torch.float32 and (ct is None or (ct.dtype == torch.float32 and ct.shape == xt.shape))
+        n = xt.shape[0]
+        xo = torch.empty((max(n, 1), 3), dtype=torch.float32, device=xt.device)
+        co = torch.empty_like(xo) if ct is not None else None
+        pv = torch.empty(max(n, 1), dtype=torch.int32, device=xt.device) if trace else None
+        vc = torch.empty(max(n, 1), dtype=torch.int32, device=xt.device) if trace else None
+        torch.cuda.synchronize(xt.device)
+        mem = MEM_DEVICE
+    else:
+        xt = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        ct = None if color is None else np.ascontiguousarray(color, np.float32).reshape(-1, 3)
+        assert ct is None or ct.shape == xt.shape
+        n = xt.shape[0]
+        xo = np.zeros((max(n, 1), 3), np.float32)
+        co = np.zeros((max(n, 1), 3), np.float32) if ct is not None else None
+        pv = np.zeros(max(n, 1), np.int32) if trace else None
+        vc = np.zeros(max(n, 1), np.int32) if trace else None
+        mem = MEM_HOST
+    rows = C.c_int()
+    _check(self.lib.svo_voxel_downsample(self._h, _ptr(xt), _ptr(ct), n, C.c_double(voxel_size), _ptr(xo), _ptr(co),
+                                         C.byref(rows), _ptr(pv), _ptr(vc), mem))
+    k = rows.value
+    own = (lambda a: a) if mem == MEM_DEVICE else (lambda a: a.copy())
+    res = (own(xo[:k]), own(co[:k]) if co is not None else None)
+    return res + (own(pv[:n]), own(vc[:k])) if trace else res
+
+
 # ---- two-view geometry: findEssentialMat / recoverPose (StereoProcess::monocularTriangulate) ----------------------
 def _problem_set(p1, p2, K):
     """one problem (p1, p2: n x 2 arrays or device tensors, K: 4 numbers) or lists of them -> (p1 and p2 back to back,

@@ -214,7 +214,8 @@ int svo_ctx_destroy(svo_ctx *ctx)
                       &ctx->sgbm_cost, &ctx->sgbm_misc, &ctx->sgbm_rp, &ctx->sor_grid, &ctx->icp_work, &ctx->ess,
                       &ctx->feat_img, &ctx->feat_sum, &ctx->sift_pyr, &ctx->sift_work, &ctx->sift_out,
                       &ctx->brief_work, &ctx->brief_pat, &ctx->surf_planes, &ctx->surf_work,
-                      &ctx->wls_work, &ctx->wls_maps, &ctx->wls_lut, &ctx->fast_work};
+                      &ctx->wls_work, &ctx->wls_maps, &ctx->wls_lut, &ctx->fast_work,
+                      &ctx->voxel_work, &ctx->voxel_stage};
     for (DevBuf *b : bufs)
         b->release();
     ctx->up_ring.release();

@@ -221,6 +221,9 @@ struct svo_ctx {
     // fast.hip: the grey, fired and score planes of a batch, the per-wavefront counts and offsets of the ordered compaction, the
     // key-point lists of host calls and of the chained ANMS (layout: fast_plan.hip.h)
     DevBuf fast_work;
+    // voxel.hip: the keys, the sort's ping-pong arrays and histograms, the rows gathered in voxel order and the segment
+    // starts (layout: voxel_plan.hip.h); voxel_stage: the inputs and outputs of a host call
+    DevBuf voxel_work, voxel_stage;
     // ba_window.hip: the host copy of a device caller's CSR arrays, which the refusals are decided on
     std::vector<unsigned char> ba_win_host;
 };

@@ -2,6 +2,9 @@
 coarse and a fine point-to-plane registration and the information matrix at the fine distance (``svo_icp_pairwise``);
 addPoseToGraph hangs the converted information on a measured loop closure of a ``capi.PoseGraph``.
 
+With ``voxel_down_sample=True`` array sources and array targets first pass through ``svo_voxel_downsample`` at
+``downSampleFactor``, the voxel size the recipe's two distances are stated in; the default does not.
+
 Two additions of ours: the target's normals are estimated (knn 30) when it has none -- the prototype never estimates
 them and Open3D would refuse such a cloud -- and the 6 x 6 matrix is converted to the graph's error coordinates
 (``icp_edge_information``) before it is stored.
@@ -17,9 +20,12 @@ from . import capi
 
 class PoseGraphOptimize:
     def __init__(self, ctx: capi.Context, pose_graph: capi.PoseGraph | None = None, downSampleFactor: float = 1.0,
-                 knn: int = 30, **icp_params):
+                 knn: int = 30, voxel_down_sample: bool = False, **icp_params):
         self.ctx = ctx
         self.downSampleFactor = downSampleFactor
+        # Open3D's recipe passes both clouds through voxel_down_sample(voxel_size = downSampleFactor) before estimate_normals and
+        # registration_icp, which is what the two distances below are stated in; off by default: every earlier call keeps its bits
+        self.voxel_down_sample = bool(voxel_down_sample)
         self.max_correspondence_distance_coarse = downSampleFactor * 15
         self.max_correspondence_distance_fine = downSampleFactor * 1.5
         self.knn = knn
@@ -28,8 +34,14 @@ class PoseGraphOptimize:
         # the closures addPoseToGraph added, Open3D's `uncertain` edges: (from, to, correspondence count), in the graph's edge order
         self.uncertain: list[tuple[int, int, float]] = []
 
+    def _thinned(self, cloud):
+        """an array cloud through ``voxel_downsample`` at downSampleFactor when voxel_down_sample is set; a ``capi.Cloud`` as given"""
+        if not self.voxel_down_sample or isinstance(cloud, capi.Cloud):
+            return cloud
+        return self.ctx.voxel_downsample(cloud, self.downSampleFactor)[0]
+
     def _target(self, target) -> capi.Cloud:
-        cloud = target if isinstance(target, capi.Cloud) else capi.Cloud(self.ctx, target)
+        cloud = target if isinstance(target, capi.Cloud) else capi.Cloud(self.ctx, self._thinned(target))
         if not cloud.has_normals:
             cloud.estimate_normals(self.knn)
         return cloud
@@ -37,7 +49,7 @@ class PoseGraphOptimize:
     def pairwiseRegistration(self, source, target):
         """source: n x 3 float32 points; target: the same or a ``capi.Cloud`` -> (T [4, 4], Lambda [6, 6]); T maps source
         coordinates into the target's frame."""
-        T, info, _ = self.ctx.icp_pairwise(source, self._target(target), self.max_correspondence_distance_coarse,
+        T, info, _ = self.ctx.icp_pairwise(self._thinned(source), self._target(target), self.max_correspondence_distance_coarse,
                                            self.max_correspondence_distance_fine, **self.icp_params)
         return T, info
 
@@ -60,7 +72,7 @@ class PoseGraphOptimize:
             T = np.eye(4)
             T[:3, :3] = np.asarray(R, np.float64).reshape(3, 3)
             T[:3, 3] = np.asarray(t, np.float64).reshape(3)
-            info, _ = self.ctx.icp_information(source, self._target(target), self.max_correspondence_distance_coarse, T)
+            info, _ = self.ctx.icp_information(self._thinned(source), self._target(target), self.max_correspondence_distance_coarse, T)
         info21 = capi.icp_edge_information(info, T)
         newest = self.poseGraph.num_vertices - 1
         self.poseGraph.add_loop_closure(int(node), capi.icp_meas7(T), info21)
