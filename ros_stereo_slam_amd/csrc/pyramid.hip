@@ -22,9 +22,12 @@
 //               so the two roles are independent).
 #include <cstdlib>
 
+#include "pyr_grey_plan.hip.h"
 #include "svo_internal.h"
 
 namespace {
+
+namespace pgp = pyr_grey_plan;
 
 __device__ __forceinline__ int reflect101(int p, int len)
 {
@@ -90,6 +93,9 @@ inline PyrBuildN<PYR_FEW> pyr_few(const PyrBuild &b)
     return f;
 }
 static_assert(sizeof(PyrBuild) <= 3072, "kernel arguments are limited to 4 KB");
+static_assert(pgp::PAD == SVO_PYR_PAD && pgp::LANES == PB && pgp::TILE_W == TW && pgp::TILE_H == TH && pgp::SRC_W == SW &&
+                  pgp::SRC_H == SH,
+              "pyr_grey_plan.hip.h restates these");
 
 // One 32x8 output tile of level l from level l-1 (RAW = false: the padded level; RAW = true: the raw
 // image, rows of w * C bytes without padding or alignment).  The (2*32+3) x (2*8+3) source tile is staged in
@@ -103,7 +109,8 @@ static_assert(sizeof(PyrBuild) <= 3072, "kernel arguments are limited to 4 KB");
 // of the result; rows first (as until round 2) filtered 19 rows of which the vertical pass used 8 outputs'
 // worth, and was 6 % of the vector instructions of a bench run.
 // SC: bytes from a source pixel to the next (SC = 3 with C = 1: channel 0 of a raw BGR image, for the grey storage of a
-// grey frame -- every tile then takes the byte-gathering path of the edge tiles).
+// grey frame -- an interior tile stages a dword per lane and turn from aligned dwords of the raw rows, the bytes picked by
+// v_perm_b32: pyr_grey_plan.hip.h; an edge tile takes the byte-gathering path).
 template <int C, bool RAW, int SC = C>
 __device__ __forceinline__ void down_tile(const uint8_t *__restrict__ src, int spitch, int w, int h,
                                           uint8_t *__restrict__ dst, int dpitch, int dw, int dh, int tx, int ty)
@@ -121,7 +128,28 @@ __device__ __forceinline__ void down_tile(const uint8_t *__restrict__ src, int s
     // bytes of the buffer
     const bool interior = SC == C && x0 >= 0 && x0 + SW <= w && y0 >= 0 && y0 + SH <= h &&
                           (!RAW || (size_t)(y0 + SH - 1) * spitch + (size_t)x0 * C + (ND + 1) * 4 + 4 <= (size_t)h * spitch);
-    if (interior) {
+    bool grey_interior = false;
+    if constexpr (RAW && C == 1 && SC == 3) {
+        static_assert(ND == pgp::SRC_ND, "the staged row of pyr_grey_plan.hip.h");
+        grey_interior = pgp::l1_tile_interior(src, w, h, x0, y0);
+    }
+    if (grey_interior) {
+        if constexpr (RAW && C == 1 && SC == 3) {
+            // all 64 lanes: item (row, dword) = turn * PB + lane, the loads of every turn issued before the first LDS store
+            uint32_t staged[pgp::L1_TURNS];
+#pragma unroll
+            for (int turn = 0; turn < pgp::L1_TURNS; turn++) {
+                const int i = min(turn * PB + tid, pgp::L1_ITEMS - 1);  // the last turn's spare lanes load the last item again
+                staged[turn] = pgp::l1_stage_item(src, w, x0, y0, i / ND, i % ND);
+            }
+#pragma unroll
+            for (int turn = 0; turn < pgp::L1_TURNS; turn++) {
+                const int i = turn * PB + tid;
+                if (i < pgp::L1_ITEMS)
+                    reinterpret_cast<uint32_t *>(s_src + (i / ND) * SROW)[i % ND] = staged[turn];
+            }
+        }
+    } else if (interior) {
         for (int d = tid; d < ND; d += PB) {  // a thread per dword column (C = 4: 67 columns, two turns)
             const uint8_t *col = src + (ptrdiff_t)y0 * spitch + x0 * C;
 #pragma unroll 1
@@ -237,21 +265,6 @@ __device__ __forceinline__ void pad_copy_row(const uint8_t *__restrict__ src, ui
     reinterpret_cast<uint32_t *>(padded + (size_t)row * pitch)[d] = out;
 }
 
-// the same for the grey storage of a grey BGR image: four pixels' channel 0 per output dword, pitch svo_grey_pitch
-__device__ __forceinline__ void pad_copy_grey_row(const uint8_t *__restrict__ src, uint8_t *__restrict__ padded, int w, int h,
-                                                  int gpitch, int row, int d)
-{
-    const uint8_t *srow = src + (size_t)reflect101(row - SVO_PYR_PAD, h) * w * 3;
-    uint32_t out = 0;
-#pragma unroll
-    for (int b = 0; b < 4; b++) {
-        const int px = d * 4 + b;
-        if (px < w + 2 * SVO_PYR_PAD)
-            out |= (uint32_t)srow[reflect101(px - SVO_PYR_PAD, w) * 3] << (8 * b);
-    }
-    reinterpret_cast<uint32_t *>(padded + (size_t)row * gpitch)[d] = out;
-}
-
 // The head launch of a three-channel build: does a pixel of the raw image have B != G or G != R?  The later launches of the
 // set choose their roles by the answer, so it has to be there before the first of them.  A thread takes four pixels = three
 // dwords per turn when the image is dword-aligned (byte i beside byte i + 1, the pairs that cross into the next pixel masked
@@ -331,12 +344,19 @@ template <int C, int NJ> __global__ __launch_bounds__(PB) void pyr_base_kernel(P
     const int d = (i % pad_x) * PB + threadIdx.x, rb = i / pad_x;
     const int row0 = rb * ROWS_PER_BLOCK, rend = min(row0 + ROWS_PER_BLOCK, b.h[0] + 2 * SVO_PYR_PAD);
     if (C == 3 && grey) {
-        const int gpitch = svo_grey_pitch(b.w[0]);
-        if (d >= (gpitch >> 2))
-            return;
+        // The grey storage of a grey BGR image: items of sixteen pixels = one aligned 16-byte store (the padded buffer starts
+        // 256-byte aligned, the pitch is a multiple of 16), dealt over ALL workgroups of the role -- the host sized the grid for
+        // three channels without knowing what the head launch would see (pyr_grey_plan.hip.h).
+        const int gpitch = svo_grey_pitch(b.w[0]), groups = gpitch / pgp::GROUP;
         uint8_t *padded = b.lvl[job][0] + b.gdelta[0] - (size_t)SVO_PYR_PAD * gpitch - SVO_PYR_PAD;
-        for (int row = row0; row < rend; row++)
-            pad_copy_grey_row(b.img[job], padded, b.w[0], b.h[0], gpitch, row, d);
+        int t0, t1;
+        pgp::l0_run(groups * (b.h[0] + 2 * SVO_PYR_PAD), (int)gridDim.x - n_tiles, i, &t0, &t1);
+        for (int t = t0 + (int)threadIdx.x; t < t1; t += PB) {
+            const int row = t / groups, g = t - row * groups;
+            uint32_t out[4];
+            pgp::l0_group(b.img[job], b.w[0], b.h[0], row, g, out);
+            *reinterpret_cast<uint4 *>(padded + (size_t)row * gpitch + pgp::GROUP * g) = make_uint4(out[0], out[1], out[2], out[3]);
+        }
         return;
     }
     if (d >= (b.pitch[0] >> 2))
