@@ -286,6 +286,63 @@ int svo_voxel_downsample(svo_ctx *ctx, const float *xyz, const float *color, int
                          float *xyz_out, float *color_out, int *n_out, int *point_voxel, int *voxel_count, int mem);
 int svo_voxel_grid(const float *min_xyz, const float *max_xyz, double voxel_size, double *min_bound3, int64_t *cells3);
 
+/* ---- stereo rectification and undistortion: cv::stereoRectify -> initUndistortRectifyMap -> remap on both images of every
+ * frame, and cv::undistortPoints -- what a raw rig (EuRoC MAV: radial-tangential distortion, a rotation between the cameras)
+ * needs in front of every other entry point.  DESIGN.md section 10p; every recalled point and every choice of ours is numbered
+ * in tests/rectify_numpy.py (N1 - N15).  Matrices are row-major doubles.
+ *
+ * The camera model: K (3 x 3), D with nD = 0, 4, 5 or 8 coefficients k1 k2 p1 p2 [k3 [k4 k5 k6]] (missing ones zero; D may be
+ * NULL when nD is 0).  Thin-prism and tilt terms (12, 14) are refused.  All arithmetic is double, in the order of N2.
+ *
+ * svo_stereo_rectify: host only, no context -- Bouguet's algorithm with flags = 0 or SVO_CALIB_ZERO_DISPARITY and alpha = -1.
+ * R, T: x2 = R x1 + T.  new_w x new_h: 0 x 0 or a size; with alpha = -1 it changes nothing (N7).  SVO_ERR_ARG, with nothing
+ * written: a null pointer, an nD outside {0, 4, 5, 8}, a size that is not positive, alpha != -1 (the free scaling parameter and
+ * the valid ROIs are not built), T = 0, an entry that is not finite.
+ *
+ * svo_rectify_map_create: the map of initUndistortRectifyMap(K, D, R, P, (w, h)) in OpenCV's fixed-point form -- per pixel an
+ * int16 pair (the top-left tap) and a uint16 fraction word fy * 32 + fx in 1/32 steps -- built by one kernel and kept on the
+ * device for the life of the handle.  R9 NULL = identity, P12 NULL = K.  src_w x src_h: the size of the images the map will
+ * sample, which may differ from w x h.  Coordinates saturate to int16 (N12).
+ * svo_rectify_map_from_float: the same words from a caller's own float maps (h x w each), converted as cv::remap converts them.
+ * svo_rectify_map_get: xy [h][w][2] int16 and frac [h][w] uint16, where `mem` says.
+ * svo_rectify_map_destroy: waits for the context's stream first; a NULL map is fine.
+ *
+ * svo_remap_batch: cv::remap(src, dst, map, INTER_LINEAR, BORDER_CONSTANT, border_value) on n_images (1..16) uint8 images of
+ * src_h x src_w x c (c = 1, or 3 interleaved), back to back where `mem` says, as svo_sgbm_compute takes them -> n_images images
+ * of h x w x c.  Weights 32 (32-a)(32-b) ... at 2^15, dst = (sum + 2^14) >> 15; a tap outside the source reads border_value
+ * (0..255, the same byte for every channel).  One launch.  In device mode dst must not overlap src, and neither needs any
+ * alignment.
+ * svo_rectify_pairs: both maps (one size, one source size) over n_pairs (1..16) left and right images in ONE launch; bit for
+ * bit what two svo_remap_batch calls give.
+ *
+ * svo_undistort_points: cv::undistortPoints(xy, K, D, R, P) on n float points: five fixed iterations, then R (NULL = none),
+ * then P's fx, fy, cx, cy (NULL = normalised coordinates out); double inside, float out.  n = 0 is SVO_OK.  At most 2^24 points.
+ * svo_undistort_points_host: the same arithmetic on the host with DOUBLE output and no context.
+ *
+ * Refusals: SVO_ERR_ARG with the outputs untouched (a null pointer, a count outside its range, c not 1 or 3, an unknown mem, a
+ * singular P R, two maps of different sizes); SVO_ERR_CAPACITY for a w, h, src_w or src_h above 32767 (the int16 map) and for
+ * more than 2^30 map pixels or source pixels per call.  Left out: alpha >= 0, fisheye, other interpolations and border modes,
+ * 16-bit images.                                                                                                              */
+typedef struct svo_rectify_map svo_rectify_map;
+#define SVO_CALIB_ZERO_DISPARITY 1024
+int svo_stereo_rectify(const double *K1, const double *D1, int nD1, const double *K2, const double *D2, int nD2, int w, int h,
+                       const double *R, const double *T, int flags, double alpha, int new_w, int new_h, double *R1, double *R2,
+                       double *P1, double *P2, double *Q);
+int svo_rectify_map_create(svo_ctx *ctx, const double *K9, const double *D, int nD, const double *R9, const double *P12, int w,
+                           int h, int src_w, int src_h, svo_rectify_map **map);
+int svo_rectify_map_from_float(svo_ctx *ctx, const float *mapx, const float *mapy, int w, int h, int src_w, int src_h, int mem,
+                               svo_rectify_map **map);
+int svo_rectify_map_destroy(svo_ctx *ctx, svo_rectify_map *map);
+int svo_rectify_map_get(svo_ctx *ctx, const svo_rectify_map *map, int16_t *xy, uint16_t *frac, int mem);
+int svo_remap_batch(svo_ctx *ctx, const svo_rectify_map *map, const uint8_t *src, int n_images, int c, int border_value,
+                    uint8_t *dst, int mem);
+int svo_rectify_pairs(svo_ctx *ctx, const svo_rectify_map *map_left, const svo_rectify_map *map_right, const uint8_t *lefts,
+                      const uint8_t *rights, int n_pairs, int c, int border_value, uint8_t *out_left, uint8_t *out_right, int mem);
+int svo_undistort_points(svo_ctx *ctx, const float *xy, int n, const double *K9, const double *D, int nD, const double *R9,
+                         const double *P12, float *out_xy, int mem);
+int svo_undistort_points_host(const float *xy, int n, const double *K9, const double *D, int nD, const double *R9,
+                              const double *P12, double *out_xy);
+
 /* ---- dense stereo: StereoProcess::stereoMatch / reprojectDisparity, src/StereoCV.cpp:21-59,227-250 -- */
 /* cv::StereoSGBM::create(1, 96, 7, 24, 96, 0, 60, 0, 3000, 5) + compute(grey1, grey2, disp) of
  * src/StereoCV.cpp:40-53 (MODE_SGBM: five paths, BT costs, median 3, filterSpeckles).  The recipe

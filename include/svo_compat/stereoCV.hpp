@@ -9,6 +9,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <memory>
 #include <stdexcept>
 
 #include "visualSLAM.hpp"
@@ -47,6 +48,12 @@ class StereoProcess {
         rImg = load_bgr(rFptr, iter);
         if (lImg.empty() || rImg.empty() || lImg.rows != rImg.rows || lImg.cols != rImg.cols)
             return Mat();
+        if (RECTIFY_FLAG) {
+            Mat l, r;
+            rectifyPair(lImg, rImg, l, r, false);
+            lImg = l;
+            rImg = r;
+        }
         svo_sgbm_params prm;
         svo_sgbm_default_params(&prm);
         Mat disp(lImg.rows, lImg.cols, kDisp16S);
@@ -79,12 +86,20 @@ class StereoProcess {
         if (disp.elemSize() != 2 || lImg.empty() || lImg.rows != disp.rows || lImg.cols != disp.cols)
             throw std::invalid_argument("reprojectDisparity: expected a CV_16S disparity map of lImg's size");
         double Q[16];
-        check(svo_stereo_rectify_q(focal_x, focal_y, cx, cy, metricDisparity ? -baseline : baseline, disp.cols, disp.rows, Q));
+        // the rig's own Q (svo_stereo_rectify) is the conventional, metric one: it takes disparities / 16 whatever metricDisparity says
+        const bool metric = metricDisparity || RECTIFY_FLAG;
+        if (RECTIFY_FLAG) {
+            ensureMaps(disp.cols, disp.rows);
+            for (int i = 0; i < 16; i++)
+                Q[i] = rectQ[i];
+        } else {
+            check(svo_stereo_rectify_q(focal_x, focal_y, cx, cy, metricDisparity ? -baseline : baseline, disp.cols, disp.rows, Q));
+        }
         const size_t n = (size_t)disp.rows * disp.cols;
         std::vector<float> xyz(n * 3), bgr(n * 3);
         int kept = 0;
         check(svo_stereo_reproject(ctx(), reinterpret_cast<const int16_t *>(disp.data), lImg.data, disp.cols, disp.rows,
-                                   lImg.channels(), Q, metricDisparity ? 1.0f / 16 : 1.0f, 0.01f, 5.0f, 1, xyz.data(),
+                                   lImg.channels(), Q, metric ? 1.0f / 16 : 1.0f, 0.01f, 5.0f, 1, xyz.data(),
                                    bgr.data(), &kept, SVO_MEM_HOST));
         reproject3dPoints.reserve(kept);
         colorMap.reserve(kept);
@@ -182,8 +197,57 @@ class StereoProcess {
     bool BRIEF_FLAG = false;
     int siftFeaturesStereo = 20000, briefBytes = 32;
     std::vector<Point2f> stereoPairs1, stereoPairs2, stereoInliers1, stereoInliers2;
-    void stereoTriangulate(const Mat &im1, const Mat &im2, std::vector<Point3f> &out3d)
+
+    // A raw rig (ours, opt-in; RECTIFY_FLAG = false, the default, changes nothing): setCalibration takes both cameras' K (9) and
+    // D (0, 4, 5 or 8 coefficients) and the pose of camera 1 in camera 2, x2 = R x1 + T (9, 3).  With RECTIFY_FLAG set,
+    // stereoMatch, stereoTriangulate and monocularTriangulate see images that went through svo_rectify_pairs (cv::stereoRectify
+    // with CALIB_ZERO_DISPARITY and alpha = -1 -> initUndistortRectifyMap -> remap; the maps are built at
+    // the first frame's size and kept), and reprojectDisparity takes Q from svo_stereo_rectify with disparities / 16 (that Q is metric,
+    // so metricDisparity is implied).  rectR1 ... rectQ hold the
+    // rectification once a frame was seen.  The intrinsics the triangulation uses (focal_x, cx, ..., baseline) stay the caller's to
+    // set: rectP1 / rectP2 hold the rectified ones.
+    bool RECTIFY_FLAG = false;
+    double rectR1[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, rectR2[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, rectP1[12] = {0}, rectP2[12] = {0},
+           rectQ[16] = {0};
+    void setCalibration(const std::vector<double> &K1, const std::vector<double> &D1, const std::vector<double> &K2,
+                        const std::vector<double> &D2, const std::vector<double> &R, const std::vector<double> &T)
     {
+        if (K1.size() != 9 || K2.size() != 9 || R.size() != 9 || T.size() != 3)
+            throw std::invalid_argument("setCalibration: K1, K2 and R hold 9 numbers, T holds 3");
+        calK1_ = K1, calD1_ = D1, calK2_ = K2, calD2_ = D2, calR_ = R, calT_ = T;
+        mapL_.reset();
+        mapR_.reset();
+        mapW_ = mapH_ = 0;
+    }
+    // cv::undistortPoints(pts, K, D, R_i, P_i) of one camera of the rig (svo_undistort_points): raw pixels -> rectified pixels.
+    // width x height: the frame size the rectification is computed for.
+    void undistortPoints(const std::vector<Point2f> &pts, std::vector<Point2f> &out, int width, int height, bool rightCamera = false)
+    {
+        ensureMaps(width, height);
+        out.assign(pts.size(), Point2f());
+        const std::vector<double> &K = rightCamera ? calK2_ : calK1_, &D = rightCamera ? calD2_ : calD1_;
+        check(svo_undistort_points(ctx(), fp(pts), (int)pts.size(), K.data(), D.empty() ? nullptr : D.data(), (int)D.size(),
+                                   rightCamera ? rectR2 : rectR1, rightCamera ? rectP2 : rectP1,
+                                   reinterpret_cast<float *>(out.data()), SVO_MEM_HOST));
+    }
+    // both images of a pair through the rig's maps; sameCamera: both are the LEFT camera's (monocularTriangulate)
+    void rectifyPair(const Mat &im1, const Mat &im2, Mat &out1, Mat &out2, bool sameCamera)
+    {
+        const int w = mat_cols(im1), h = mat_rows(im1), c = mat_channels(im1);
+        if (mat_data(im1) == nullptr || mat_data(im2) == nullptr || mat_cols(im2) != w || mat_rows(im2) != h || mat_channels(im2) != c)
+            throw std::invalid_argument("rectifyPair: two images of one size are needed");
+        ensureMaps(w, h);
+        out1 = Mat(h, w, im1.type());
+        out2 = Mat(h, w, im2.type());
+        check(svo_rectify_pairs(ctx(), mapL_.get(), sameCamera ? mapL_.get() : mapR_.get(), mat_data(im1), mat_data(im2), 1, c, 0,
+                                out1.data, out2.data, SVO_MEM_HOST));
+    }
+    void stereoTriangulate(const Mat &raw1, const Mat &raw2, std::vector<Point3f> &out3d)
+    {
+        Mat rect1, rect2;
+        if (RECTIFY_FLAG)
+            rectifyPair(raw1, raw2, rect1, rect2, false);
+        const Mat &im1 = RECTIFY_FLAG ? rect1 : raw1, &im2 = RECTIFY_FLAG ? rect2 : raw2;
         slam_.baseline = baseline;
         slam_.focal_x = focal_x;
         slam_.focal_y = focal_y;
@@ -234,8 +298,12 @@ class StereoProcess {
         kps.swap(k[0]);
         desc.swap(d[0]);
     }
-    void monocularTriangulate(const Mat &im1, const Mat &im2, std::vector<Point3f> &out3d)
+    void monocularTriangulate(const Mat &raw1, const Mat &raw2, std::vector<Point3f> &out3d)
     {
+        Mat rect1, rect2;
+        if (RECTIFY_FLAG)
+            rectifyPair(raw1, raw2, rect1, rect2, true);
+        const Mat &im1 = RECTIFY_FLAG ? rect1 : raw1, &im2 = RECTIFY_FLAG ? rect2 : raw2;
         std::vector<Point2f> pt1, pt2;
         if (SIFT_FLAG) {
             siftRatioPairs(im1, im2, pt1, pt2);
@@ -281,6 +349,27 @@ class StereoProcess {
 
   private:
     static const float *fp(const std::vector<Point2f> &v) { return reinterpret_cast<const float *>(v.data()); }
+    std::vector<double> calK1_, calD1_, calK2_, calD2_, calR_, calT_;
+    std::shared_ptr<svo_rectify_map> mapL_, mapR_;
+    int mapW_ = 0, mapH_ = 0;
+    // the rectification and both maps for frames of w x h, built once per size
+    void ensureMaps(int w, int h)
+    {
+        if (calK1_.empty())
+            throw std::logic_error("RECTIFY_FLAG / undistortPoints: setCalibration has not been called");
+        if (mapL_ && mapR_ && mapW_ == w && mapH_ == h)
+            return;
+        const double *d1 = calD1_.empty() ? nullptr : calD1_.data(), *d2 = calD2_.empty() ? nullptr : calD2_.data();
+        check(svo_stereo_rectify(calK1_.data(), d1, (int)calD1_.size(), calK2_.data(), d2, (int)calD2_.size(), w, h, calR_.data(),
+                                 calT_.data(), SVO_CALIB_ZERO_DISPARITY, -1.0, 0, 0, rectR1, rectR2, rectP1, rectP2, rectQ));
+        svo_ctx *c = ctx();
+        svo_rectify_map *l = nullptr, *r = nullptr;
+        check(svo_rectify_map_create(c, calK1_.data(), d1, (int)calD1_.size(), rectR1, rectP1, w, h, w, h, &l));
+        mapL_.reset(l, [c](svo_rectify_map *m) { svo_rectify_map_destroy(c, m); });
+        check(svo_rectify_map_create(c, calK2_.data(), d2, (int)calD2_.size(), rectR2, rectP2, w, h, w, h, &r));
+        mapR_.reset(r, [c](svo_rectify_map *m) { svo_rectify_map_destroy(c, m); });
+        mapW_ = w, mapH_ = h;
+    }
     // n images of one size through one svo_sift_extract_batch call
     // (desc == nullptr: detect only)
     void siftFeaturesBatch(const Mat *const *imgs, int n, int nfeatures, std::vector<KeyPoint> *kps, std::vector<float> *desc)

@@ -1299,6 +1299,195 @@ def voxel_downsample(self, xyz, voxel_size, color=None, trace=False, mem=None):
     return res + (own(pv[:n]), own(vc[:k])) if trace else res
 
 
+# ---- stereo rectification and undistortion: stereoRectify -> initUndistortRectifyMap -> remap, undistortPoints ----------
+CALIB_ZERO_DISPARITY = 1024
+StereoRectification = collections.namedtuple("StereoRectification", "R1 R2 P1 P2 Q")
+
+
+def _camera(K, D):
+    K = np.ascontiguousarray(K, np.float64).reshape(3, 3)
+    D = np.zeros(0) if D is None else np.ascontiguousarray(D, np.float64).reshape(-1)
+    return K, D, len(D)
+
+
+def _opt_matrix(M, shape):
+    return None if M is None else np.ascontiguousarray(M, np.float64).reshape(shape)
+
+
+def stereo_rectify(K1, D1, K2, D2, size, R, T, flags=CALIB_ZERO_DISPARITY, alpha=-1.0, new_size=(0, 0)):
+    """``svo_stereo_rectify`` (host code, no context): cv::stereoRectify with alpha = -1 -> StereoRectification(R1, R2, P1, P2,
+    Q), float64 matrices.  size: (w, h)."""
+    K1, D1, n1 = _camera(K1, D1)
+    K2, D2, n2 = _camera(K2, D2)
+    R, T = np.ascontiguousarray(R, np.float64).reshape(3, 3), np.ascontiguousarray(T, np.float64).reshape(3)
+    out = StereoRectification(np.zeros((3, 3)), np.zeros((3, 3)), np.zeros((3, 4)), np.zeros((3, 4)), np.zeros((4, 4)))
+    _check(load().svo_stereo_rectify(_ptr(K1), _ptr(D1), n1, _ptr(K2), _ptr(D2), n2, int(size[0]), int(size[1]), _ptr(R), _ptr(T),
+                                     int(flags), C.c_double(alpha), int(new_size[0]), int(new_size[1]), *[_ptr(a) for a in out]))
+    return out
+
+
+def undistort_points_host(xy, K, D, R=None, P=None):
+    """``svo_undistort_points_host``: float32 points in, float64 points out; no context."""
+    xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+    K, D, nD = _camera(K, D)
+    out = np.zeros((len(xy), 2), np.float64)
+    _check(load().svo_undistort_points_host(_ptr(xy), len(xy), _ptr(K), _ptr(D), nD, _ptr(_opt_matrix(R, (3, 3))),
+                                            _ptr(_opt_matrix(P, (3, 4))), _ptr(out)))
+    return out
+
+
+class RectifyMap:
+    """A fixed-point rectify map on the device (``svo_rectify_map``): ``Context.rectify_map`` / ``rectify_map_from_float``."""
+
+    def __init__(self, ctx, handle, size, src_size):
+        self.ctx, self._h, self.size, self.src_size = ctx, handle, tuple(size), tuple(src_size)
+        ctx._children.add(self)
+
+    def get(self):
+        """-> (xy [h, w, 2] int16, frac [h, w] uint16)"""
+        w, h = self.size
+        xy, frac = np.zeros((h, w, 2), np.int16), np.zeros((h, w), np.uint16)
+        _check(self.ctx.lib.svo_rectify_map_get(self.ctx._h, self._h, _ptr(xy), _ptr(frac), MEM_HOST))
+        return xy, frac
+
+    def close(self):
+        if self._h and self.ctx._h:
+            self.ctx.lib.svo_rectify_map_destroy(self.ctx._h, self._h)
+        self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+@_ctx_method
+def rectify_map(self, K, D, R, P, size, src_size=None):
+    """``svo_rectify_map_create``: initUndistortRectifyMap(K, D, R, P, size) -> RectifyMap.  R, P may be None (identity, K);
+    P is 3 x 4 (or 3 x 3); src_size: the size of the images to sample, ``size`` when None."""
+    K, D, nD = _camera(K, D)
+    if P is not None:
+        P = np.asarray(P, np.float64)
+        P = np.ascontiguousarray(np.hstack([P, np.zeros((3, 1))]) if P.shape == (3, 3) else P.reshape(3, 4))
+    src = tuple(size) if src_size is None else tuple(src_size)
+    h = C.c_void_p()
+    _check(self.lib.svo_rectify_map_create(self._h, _ptr(K), _ptr(D), nD, _ptr(_opt_matrix(R, (3, 3))), _ptr(P), int(size[0]),
+                                           int(size[1]), int(src[0]), int(src[1]), C.byref(h)))
+    return RectifyMap(self, h, size, src)
+
+
+@_ctx_method
+def rectify_map_from_float(self, mapx, mapy, src_size):
+    """``svo_rectify_map_from_float``: a caller's float maps (h x w each; numpy arrays or device tensors) -> RectifyMap."""
+    dev = _is_device(mapx)
+    assert dev == _is_device(mapy), "mapx and mapy must live in the same memory"
+    if dev:
+        import torch
+
+        mx, my = mapx.to(torch.float32).contiguous(), mapy.to(torch.float32).contiguous()
+        torch.cuda.synchronize(mx.device)
+    else:
+        mx, my = np.ascontiguousarray(mapx, np.float32), np.ascontiguousarray(mapy, np.float32)
+    assert mx.ndim == 2 and tuple(mx.shape) == tuple(my.shape)
+    hh, ww = mx.shape
+    h = C.c_void_p()
+    _check(self.lib.svo_rectify_map_from_float(self._h, _ptr(mx), _ptr(my), int(ww), int(hh), int(src_size[0]), int(src_size[1]),
+                                               MEM_DEVICE if dev else MEM_HOST, C.byref(h)))
+    return RectifyMap(self, h, (ww, hh), src_size)
+
+
+def _image_batch(images, src_size):
+    """one image (h x w or h x w x c) or a batch (n x h x w, n x h x w x c) of a map's source size -> (array, n, c, the leading
+    shape of the result, device).  A 3-D array whose LAST two axes are the source size is a grey batch; only otherwise is it one
+    image with channels (the two readings coincide only for a 1 x 1 or 3 x 3 source)."""
+    dev = _is_device(images)
+    a = images.contiguous() if dev else np.ascontiguousarray(images, np.uint8)
+    sw, sh = src_size
+    shape = tuple(a.shape)
+    if len(shape) == 2:
+        lead, n, c, hw = (), 1, 1, shape
+    elif len(shape) == 3 and shape[1:] == (sh, sw):
+        lead, n, c, hw = (shape[0],), shape[0], 1, shape[1:]
+    elif len(shape) == 3:
+        lead, n, c, hw = (), 1, shape[2], shape[:2]
+    else:
+        lead, n, c, hw = (shape[0],), shape[0], shape[3], shape[1:3]
+    assert len(shape) <= 4 and hw == (sh, sw) and c in (1, 3), f"images must be {sh} x {sw} with 1 or 3 channels, the map's source size"
+    if dev:
+        import torch
+
+        assert a.dtype == torch.uint8
+    return a, n, c, (lead, len(shape) - len(lead) == 3), dev
+
+
+def _remap_shape(lead_ch, size, c):
+    lead, with_channels = lead_ch
+    return lead + (size[1], size[0]) + ((c,) if with_channels else ())
+
+
+@_ctx_method
+def remap(self, map, images, border_value=0, mem=None):
+    """``svo_remap_batch``: cv::remap(INTER_LINEAR, BORDER_CONSTANT) of one image or a batch of 1..16 (numpy arrays or device
+    tensors, uint8, grey or 3 interleaved channels) through ``map`` -> images of the map's size with the same leading shape."""
+    a, n, c, lead, dev = _image_batch(images, map.src_size)
+    if mem is not None:
+        assert (mem == MEM_DEVICE) == dev
+    oshape = _remap_shape(lead, map.size, c)
+    if dev:
+        import torch
+
+        out = torch.empty(oshape, dtype=torch.uint8, device=a.device)
+        torch.cuda.synchronize(a.device)
+    else:
+        out = np.zeros(oshape, np.uint8)
+    _check(self.lib.svo_remap_batch(self._h, map._h, _ptr(a), n, c, int(border_value), _ptr(out), MEM_DEVICE if dev else MEM_HOST))
+    return out
+
+
+@_ctx_method
+def rectify_pairs(self, map_left, map_right, lefts, rights, border_value=0, mem=None):
+    """``svo_rectify_pairs``: both images of 1..16 stereo pairs through their maps in one launch -> (lefts, rights) rectified."""
+    a, n, c, lead, dev = _image_batch(lefts, map_left.src_size)
+    b, n2, c2, _, dev2 = _image_batch(rights, map_right.src_size)
+    assert (n, c, dev) == (n2, c2, dev2), "lefts and rights must pair up and live in the same memory"
+    if mem is not None:
+        assert (mem == MEM_DEVICE) == dev
+    oshape = _remap_shape(lead, map_left.size, c)
+    if dev:
+        import torch
+
+        ol, orr = torch.empty(oshape, dtype=torch.uint8, device=a.device), torch.empty(oshape, dtype=torch.uint8, device=a.device)
+        torch.cuda.synchronize(a.device)
+    else:
+        ol, orr = np.zeros(oshape, np.uint8), np.zeros(oshape, np.uint8)
+    _check(self.lib.svo_rectify_pairs(self._h, map_left._h, map_right._h, _ptr(a), _ptr(b), n, c, int(border_value), _ptr(ol),
+                                      _ptr(orr), MEM_DEVICE if dev else MEM_HOST))
+    return ol, orr
+
+
+@_ctx_method
+def undistort_points(self, xy, K, D, R=None, P=None, mem=None):
+    """``svo_undistort_points``: cv::undistortPoints on n x 2 float32 points (a numpy array, or a device tensor which gives a
+    device tensor back) -> n x 2 float32."""
+    dev = _is_device(xy)
+    if mem is not None:
+        assert (mem == MEM_DEVICE) == dev
+    K, D, nD = _camera(K, D)
+    if dev:
+        import torch
+
+        pts = xy.reshape(-1, 2).to(torch.float32).contiguous()
+        out = torch.empty_like(pts)
+        torch.cuda.synchronize(pts.device)
+    else:
+        pts = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        out = np.zeros_like(pts)
+    _check(self.lib.svo_undistort_points(self._h, _ptr(pts), int(pts.shape[0]), _ptr(K), _ptr(D), nD, _ptr(_opt_matrix(R, (3, 3))),
+                                         _ptr(_opt_matrix(P, (3, 4))), _ptr(out), MEM_DEVICE if dev else MEM_HOST))
+    return out
+
+
 # ---- two-view geometry: findEssentialMat / recoverPose (StereoProcess::monocularTriangulate) ----------------------
 def _problem_set(p1, p2, K):
     """one problem (p1, p2: n x 2 arrays or device tensors, K: 4 numbers) or lists of them -> (p1 and p2 back to back,

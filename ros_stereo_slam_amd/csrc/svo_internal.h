@@ -224,6 +224,8 @@ struct svo_ctx {
     // voxel.hip: the keys, the sort's ping-pong arrays and histograms, the rows gathered in voxel order and the segment
     // starts (layout: voxel_plan.hip.h); voxel_stage: the inputs and outputs of a host call
     DevBuf voxel_work, voxel_stage;
+    // rectify.hip: the images, maps and points of a host call (layout: rectify_plan.hip.h)
+    DevBuf rect_stage;
     // ba_window.hip: the host copy of a device caller's CSR arrays, which the refusals are decided on
     std::vector<unsigned char> ba_win_host;
 };

@@ -74,8 +74,10 @@ def absolute_scale(poses_path: str, frame_id: int):
 class StereoSequence:
     """``lFptr`` / ``rFptr`` of the reference: two printf patterns, frames by index."""
 
-    def __init__(self, left_pattern: str, right_pattern: str, channels: int = 3):
-        self.lp, self.rp, self.channels = left_pattern, right_pattern, channels
+    def __init__(self, left_pattern: str, right_pattern: str, channels: int = 3, rectifier=None):
+        """``rectifier``: None, or a pair (map_left, map_right) of ``capi.RectifyMap`` on one context for a raw rig; ``load``
+        then returns the pair rectified through ``svo_rectify_pairs``."""
+        self.lp, self.rp, self.channels, self.rectifier = left_pattern, right_pattern, channels, rectifier
 
     @classmethod
     def kitti(cls, seq_dir: str, channels: int = 3) -> "StereoSequence":
@@ -100,7 +102,11 @@ class StereoSequence:
         return lo + 1 if self.exists(0) else 0
 
     def load(self, i: int):
-        return read_image(format_path(self.lp, i), self.channels), read_image(format_path(self.rp, i), self.channels)
+        left, right = read_image(format_path(self.lp, i), self.channels), read_image(format_path(self.rp, i), self.channels)
+        if self.rectifier is None:
+            return left, right
+        ml, mr = self.rectifier
+        return ml.ctx.rectify_pairs(ml, mr, left, right)
 
 
 def read_calib(path: str):
