@@ -9,8 +9,10 @@
 //   sgbm_vsum_kernel    one thread per (x, d): the vertical block sum down the column with 3.2's quirks (R5) -> C
 //   sgbm_path_kernel    one wave per path line of the four top-to-bottom directions; a lane owns PER consecutive
 //                       disparities, Lr'(d +- 1) across lanes by shuffles, minLr' by a butterfly min; Lr of the previous
-//                       step in registers; each direction writes its own int16 plane (the sum of the four is formed once,
-//                       in int, by the WTA kernel: S = sat16(L0 + L1 + L2 + L3) exactly as the sequential sweep)
+//                       step in registers; each direction writes its own plane (the sum of the four is formed once,
+//                       in int, by the WTA kernel: S = sat16(L0 + L1 + L2 + L3) exactly as the sequential sweep).
+//                       The planes are int16 while every L provably fits (see planes_need_int); beyond that C and the
+//                       stored Lr wrap, the sweep still sums the int L (R7), and the planes are kept as int
 //   sgbm_wta_kernel     one wave per row: the right->left path, S, winner-take-all, uniqueness, sub-pixel, disp2 in LDS
 //                       (serial in x, so the tie rule is the reference's), then the left-right check over the row
 //   sgbm_median_kernel  medianBlur 3x3, replicated border (R12)
@@ -169,8 +171,8 @@ template <int PER> __device__ __forceinline__ void load_c(const int16_t *p, bool
 }
 
 // ---- the four top-to-bottom directions: one wave per line ---------------------------------------------------------------
-template <int PER>
-__global__ __launch_bounds__(256) void sgbm_path_kernel(SgbmGeom g, const int16_t *__restrict__ C, int16_t *__restrict__ planes,
+template <int PER, class PlaneT>
+__global__ __launch_bounds__(256) void sgbm_path_kernel(SgbmGeom g, const int16_t *__restrict__ C, PlaneT *__restrict__ planes,
                                                         int n_lines)
 {
     const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, pair = blockIdx.y;
@@ -200,7 +202,7 @@ __global__ __launch_bounds__(256) void sgbm_path_kernel(SgbmGeom g, const int16_
     }
     const bool active = lane * PER < D, last_lane = (lane + 1) * PER >= D;
     const int16_t *__restrict__ Cp = C + pair * g.cells + lane * PER;
-    int16_t *__restrict__ plane = planes + (size_t)dir * g.plane_stride + pair * g.cells + lane * PER;
+    PlaneT *__restrict__ plane = planes + (size_t)dir * g.plane_stride + pair * g.cells + lane * PER;
     int Lp[PER], L[PER], Cv[PER], Cn[PER];
 #pragma unroll
     for (int k = 0; k < PER; k++)
@@ -220,7 +222,7 @@ __global__ __launch_bounds__(256) void sgbm_path_kernel(SgbmGeom g, const int16_
 #pragma unroll
         for (int k = 0; k < PER; k++) {
             if (active)
-                plane[off + k] = (int16_t)L[k];
+                plane[off + k] = (PlaneT)L[k];
             mn = min(mn, L[k]);
             Lp[k] = (int16_t)L[k];
         }
@@ -230,8 +232,8 @@ __global__ __launch_bounds__(256) void sgbm_path_kernel(SgbmGeom g, const int16_
 }
 
 // ---- right -> left path, S, winner-take-all, disp2, left-right check: one wave per row ---------------------------------
-template <int PER>
-__global__ __launch_bounds__(64) void sgbm_wta_kernel(SgbmGeom g, const int16_t *__restrict__ C, const int16_t *__restrict__ planes,
+template <int PER, class PlaneT>
+__global__ __launch_bounds__(64) void sgbm_wta_kernel(SgbmGeom g, const int16_t *__restrict__ C, const PlaneT *__restrict__ planes,
                                                       int16_t *__restrict__ raw)
 {
     __shared__ int16_t drow[SGBM_MAXW], disp2[SGBM_MAXW];
@@ -249,7 +251,7 @@ __global__ __launch_bounds__(64) void sgbm_wta_kernel(SgbmGeom g, const int16_t 
     const bool active = lane * PER < D, last_lane = (lane + 1) * PER >= D;
     const size_t base = pair * g.cells + (size_t)y * W1 * D + lane * PER;
     const int16_t *__restrict__ Cp = C + base;
-    const int16_t *__restrict__ Pp[4] = {planes + base, planes + g.plane_stride + base, planes + 2 * g.plane_stride + base,
+    const PlaneT *__restrict__ Pp[4] = {planes + base, planes + g.plane_stride + base, planes + 2 * g.plane_stride + base,
                                          planes + 3 * g.plane_stride + base};
     int Lp[PER], L[PER], Cv[PER], Cn[PER], Sf[PER], Sn[PER];
 #pragma unroll
@@ -525,6 +527,34 @@ void rectify_q(double fx, double fy, double cx, double cy, double tx, int w, int
     Q[15] = (ccx - ccx) / tx;
 }
 
+// Whether some path cost L can leave int16.  While C does not wrap, C lies in [P2, P2 + the largest block sum]; R6 gives
+// C - P2 <= L <= C as long as the stored Lr' and minLr' are the true ones, so by induction every L lies in [0, 32767] when
+// that upper end does.  A pixel costs at most the largest derivative value (2 ftzero, a uchar: R1) plus 255 >> 2.
+bool planes_need_int(const SgbmGeom &g)
+{
+    const long long side = 2 * g.SW2 + 1, pixmax = (2 * g.ftzero < 255 ? 2 * g.ftzero : 255) + 63;
+    return g.P2 + side * side * pixmax > SHORT_MAX_;
+}
+
+template <int PER, class PlaneT>
+void launch_paths(const SgbmGeom &g, int n_pairs, hipStream_t st, const int16_t *dC, void *planes, int16_t *raw)
+{
+    const int n_lines = g.h + g.width1 + 2 * (g.width1 + g.h - 1);
+    hipLaunchKernelGGL((sgbm_path_kernel<PER, PlaneT>), dim3((n_lines + 3) / 4, n_pairs), dim3(256), 0, st, g, dC,
+                       static_cast<PlaneT *>(planes), n_lines);
+    hipLaunchKernelGGL((sgbm_wta_kernel<PER, PlaneT>), dim3(g.h, n_pairs), dim3(64), 0, st, g, dC,
+                       static_cast<const PlaneT *>(planes), raw);
+}
+
+template <int PER> void launch_paths(const SgbmGeom &g, bool wide, int n_pairs, hipStream_t st, const int16_t *dC, void *planes,
+                                     int16_t *raw)
+{
+    if (wide)
+        launch_paths<PER, int>(g, n_pairs, st, dC, planes, raw);
+    else
+        launch_paths<PER, int16_t>(g, n_pairs, st, dC, planes, raw);
+}
+
 int sgbm_check(const svo_sgbm_params *p, int w, int h)
 {
     SVO_CHECK_ARG(p != nullptr);
@@ -606,9 +636,10 @@ int svo_sgbm_compute(svo_ctx *ctx, const svo_sgbm_params *p, const uint8_t *left
         dr = ctx->s_b.as<uint8_t>();
         dout = ctx->s_c.as<int16_t>();
     }
-    // scratch, kept in the context and grown on demand: C, four direction planes (plane 3 holds hsum first), the raw
-    // disparities, the union-find parents and sizes
-    if ((rc = ctx->sgbm_cost.ensure(g.plane_stride * 5 * sizeof(int16_t) + 256)) ||
+    // scratch, kept in the context and grown on demand: C, four direction planes of int16 or int (hsum lies first where
+    // the fourth int16 plane does), the raw disparities, the union-find parents and sizes
+    const bool wide = planes_need_int(g);
+    if ((rc = ctx->sgbm_cost.ensure(g.plane_stride * (sizeof(int16_t) + 4 * (wide ? sizeof(int) : sizeof(int16_t))) + 256)) ||
         (rc = ctx->sgbm_misc.ensure(npix * (2 + 4 + 4) + 256)))
         return rc;
     int16_t *dC = ctx->sgbm_cost.as<int16_t>(), *planes = dC + g.plane_stride, *hs = planes + 3 * g.plane_stride;
@@ -618,20 +649,14 @@ int svo_sgbm_compute(svo_ctx *ctx, const svo_sgbm_params *p, const uint8_t *left
     if (W1 > 0) {
         hipLaunchKernelGGL(sgbm_hsum_kernel, dim3(h, n_pairs), dim3(256), 0, st, g, dl, dr, hs);
         hipLaunchKernelGGL(sgbm_vsum_kernel, dim3((unsigned)((W1 * g.D + 255) / 256), n_pairs), dim3(256), 0, st, g, hs, dC);
-        const int n_lines = h + W1 + 2 * (W1 + h - 1);
-        const dim3 pg((n_lines + 3) / 4, n_pairs);
-        if (g.D <= 64) {
-            hipLaunchKernelGGL(sgbm_path_kernel<1>, pg, dim3(256), 0, st, g, dC, planes, n_lines);
-            hipLaunchKernelGGL(sgbm_wta_kernel<1>, dim3(h, n_pairs), dim3(64), 0, st, g, dC, planes, raw);
-        } else if (g.D <= 128) {
-            hipLaunchKernelGGL(sgbm_path_kernel<2>, pg, dim3(256), 0, st, g, dC, planes, n_lines);
-            hipLaunchKernelGGL(sgbm_wta_kernel<2>, dim3(h, n_pairs), dim3(64), 0, st, g, dC, planes, raw);
-        } else {
-            hipLaunchKernelGGL(sgbm_path_kernel<4>, pg, dim3(256), 0, st, g, dC, planes, n_lines);
-            hipLaunchKernelGGL(sgbm_wta_kernel<4>, dim3(h, n_pairs), dim3(64), 0, st, g, dC, planes, raw);
-        }
+        if (g.D <= 64)
+            launch_paths<1>(g, wide, n_pairs, st, dC, planes, raw);
+        else if (g.D <= 128)
+            launch_paths<2>(g, wide, n_pairs, st, dC, planes, raw);
+        else
+            launch_paths<4>(g, wide, n_pairs, st, dC, planes, raw);
     } else {   // an empty band: every pixel invalid (3.2 returns early; the median keeps a constant image)
-        hipLaunchKernelGGL(sgbm_wta_kernel<1>, dim3(h, n_pairs), dim3(64), 0, st, g, dC, planes, raw);
+        hipLaunchKernelGGL((sgbm_wta_kernel<1, int16_t>), dim3(h, n_pairs), dim3(64), 0, st, g, dC, planes, raw);
     }
     const unsigned nb = (unsigned)((npix + 255) / 256);
     hipLaunchKernelGGL(sgbm_median_kernel, dim3(nb), dim3(256), 0, st, raw, dout, w, h, n_pairs);

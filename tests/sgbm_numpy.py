@@ -8,7 +8,10 @@ this project, so what follows is restated from recollection of modules/calib3d/s
 not copied.  The points that are recollections rather than citations (DESIGN.md section 10 keeps the same list):
 
  R1  pre-filter cap: ``ftzero = max(preFilterCap, 15) | 1`` (61 for the reference's 60), clip table
-     ``tab[v] = clamp(v, -ftzero, ftzero) + ftzero``.
+     ``tab[v] = (uchar)(clamp(v, -ftzero, ftzero) + ftzero)``.  The table is recalled as an array of PixType
+     (uchar), so for a cap above 127 (ftzero >= 129) the entries wrap modulo 256, and so does the border value
+     ``tab[0] = (uchar)ftzero`` of R2 in both channels.  That range rests on this recollection alone; no OpenCV was
+     run for it.
  R2  pre-filter: ``v = 2 (I[y][x+1] - I[y][x-1]) + I[y-1][x+1] - I[y-1][x-1] + I[y+1][x+1] - I[y+1][x-1]`` for
      x in [1, w-1); rows y-1 / y+1 replaced by row y itself at the top / bottom edge; columns 0 and w-1 of the derivative
      row are ``tab[0] = ftzero``.  The second cost channel is the raw intensity, whose columns 0 and w-1 are ALSO set to
@@ -107,16 +110,17 @@ def c_div(a, b):
 
 
 def _prefilter_rows(img: np.ndarray, ftzero: int):
-    """(derivative channel, intensity channel) int32 h x w (R1, R2)."""
+    """(derivative channel, intensity channel) int32 h x w holding uint8 values (R1, R2): the table entries and the
+    border value tab[0] are stored as uchar, so they wrap modulo 256 once ftzero exceeds 127."""
     I = img.astype(np.int32)
     h, w = I.shape
     up = np.concatenate([I[:1], I[:-1]], 0)
     dn = np.concatenate([I[1:], I[-1:]], 0)
-    der = np.full((h, w), ftzero, np.int32)
-    inten = np.full((h, w), ftzero, np.int32)
+    der = np.full((h, w), ftzero & 255, np.int32)
+    inten = np.full((h, w), ftzero & 255, np.int32)
     if w > 2:
         v = (I[:, 2:] - I[:, :-2]) * 2 + up[:, 2:] - up[:, :-2] + dn[:, 2:] - dn[:, :-2]
-        der[:, 1:-1] = np.clip(v, -ftzero, ftzero) + ftzero
+        der[:, 1:-1] = (np.clip(v, -ftzero, ftzero) + ftzero) & 255
         inten[:, 1:-1] = I[:, 1:-1]
     return der, inten
 

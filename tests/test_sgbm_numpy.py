@@ -26,6 +26,38 @@ def test_path_recurrence_by_hand():
     assert Lint[0].tolist() == [0, 2, 10] and int(m16[0]) == 0
 
 
+def test_sweep_sums_the_int_path_costs_not_the_stored_ones():
+    """R6 / R7 where Lr leaves int16: one band pixel, P2 = 32000, C = [-1000, 5].  Every path starts here, so each of
+    the five L is C + min(0, .., P2) - P2 = [-33000, -31995].  The stored Lr wraps to 32536; the sum takes the int:
+    sat16(4 * -33000) = -32768, and sat16(-32768 - 33000) = -32768 (a sum of stored values would give 32767 - 33000)."""
+    p = sn.Params(p1=24, p2=32000)
+    C = np.array([[[-1000, 5]]], np.int16)
+    Lint, L16, m16 = sn.path_step(C[0], np.zeros((1, 2), np.int16), np.zeros(1, np.int16), 24, 32000)
+    assert Lint[0].tolist() == [-33000, -31995] and L16[0].tolist() == [32536, -31995] and int(m16[0]) == 32536
+    assert sn.aggregate(C, p)[0, 0].tolist() == [-32768, -32768]
+
+
+def test_prefilter_is_stored_as_uchar_above_cap_127():
+    """R1 / R2 by hand on one row (the rows above and below are the row itself: v = 4 (I[x+1] - I[x-1])).
+    v = [., 300, 300, -340, 500, 40, 60, -40, .]."""
+    row = np.array([[10, 0, 85, 75, 0, 200, 10, 215, 0]], np.uint8)
+    inner = [0, 85, 75, 0, 200, 10, 215]
+    # cap 127, ftzero 127: nothing wraps; clamp(v) + 127
+    der, inten = sn._prefilter_rows(row, max(127, 15) | 1)
+    assert der[0].tolist() == [127, 254, 254, 0, 254, 167, 187, 87, 127] and inten[0].tolist() == [127, *inner, 127]
+    # cap 200, ftzero 201: +300 clamps to 201 and stores (201 + 201) & 255 = 146; 40 + 201 = 241 fits, 60 + 201 = 261
+    # wraps to 5; the border tab[0] = 201 in both channels
+    der, inten = sn._prefilter_rows(row, max(200, 15) | 1)
+    assert der[0].tolist() == [201, 146, 146, 0, 146, 241, 5, 161, 201] and inten[0].tolist() == [201, *inner, 201]
+    # cap 300, ftzero 301: the border stores 301 & 255 = 45; 300 + 301 = 601 -> 89, 301 + 301 = 602 -> 90
+    der, inten = sn._prefilter_rows(row, max(300, 15) | 1)
+    assert der[0].tolist() == [45, 89, 89, 0, 90, 85, 105, 5, 45] and inten[0].tolist() == [45, *inner, 45]
+    # and through pixel_cost: the costs of cap 200 are those of uchar rows, below 256 in the derivative channel
+    left, right = np.repeat(row, 3, 0), np.repeat(row[:, ::-1], 3, 0)
+    pix = sn.pixel_cost(left, right, sn.Params(min_disparity=0, num_disparities=4, pre_filter_cap=200))
+    assert pix.max() <= 255 + (255 >> 2)
+
+
 def test_c_division_truncates_toward_zero():
     assert sn.c_div(-7, 4) == -1 and sn.c_div(7, 4) == 1 and sn.c_div(-8, 4) == -2 and sn.c_div(-614, 116) == -5
 
