@@ -626,6 +626,59 @@ int svo_knn_match(svo_ctx *ctx, int norm, const void *query, const void *train, 
  * At most 32768 queries.                                                                                              */
 int svo_ratio_pairs(svo_ctx *ctx, const int *idx, const float *dist, int nq, int k, double ratio, const float *xy_query,
                     const float *xy_train, float *p1, float *p2, uint8_t *mask, int *count, int mem);
+/* ---- cross-check, radius and masked matching: the rest of cv::BFMatcher ---------------------------------------------
+ * The three calls below share svo_knn_match's conventions: the norms and their selection keys, the order (ascending key,
+ * equal keys to the lower index, a NaN key behind every number), batches of 1..16 problems over host offset arrays that
+ * return the bits of their problems one call at a time, `mem`, 4-byte alignment, 32768 rows per problem
+ * (SVO_ERR_CAPACITY), SVO_ERR_ARG; a refusal leaves every output untouched.  None forms an nq x nt matrix in memory.
+ *
+ * svo_match_cross: BFMatcher(norm, true).match.  idx / dist: ONE entry per query row; a query without a partner gets
+ * -1 / +inf.  Every comparison is made on the selection key, never on the rooted float (ours: two keys whose roots round
+ * to the same float still order by key).
+ *   SVO_CROSS_MUTUAL  query i is paired with train j exactly when j is i's best train row and i is j's best query row,
+ *                     both by the order above (a NaN key takes part like any other key: behind every number).
+ *   SVO_CROSS_CV      what batchDistance(..., crosscheck = true) of OpenCV 3.2 does, as recalled: only the reverse search
+ *                     runs -- each train row finds its best query, and a query keeps, among the train rows that chose it,
+ *                     the one with the smallest key (strict < over ascending train rows: the lower train row wins a
+ *                     tie).  A train row whose best key is NaN chooses nobody (d < d0 is false).  A query can be paired
+ *                     here although its own best train row is another one: without NaN keys, CV keeps MUTUAL's pairs and adds to them.
+ * The call queues the reverse search (the kernels of svo_knn_match with the roles swapped), for MUTUAL the forward
+ * search, and one pairing kernel; in device mode it waits for nothing.                                                */
+enum { SVO_CROSS_MUTUAL = 0, SVO_CROSS_CV = 1 };
+int svo_match_cross(svo_ctx *ctx, int norm, const void *query, const void *train, int dim, const int *q_offsets,
+                    const int *t_offsets, int nprob, int mode, int *idx, float *dist, int mem);
+/* svo_radius_match: BFMatcher::radiusMatch -- for every query all train rows with dist <= max_distance, compared on the
+ * float that is returned (rooted for the two L2 norms, the count for HAMMING); a NaN dist never passes, a negative
+ * max_distance admits nothing, a NaN max_distance is SVO_ERR_ARG.  Each query's matches are in the order above.
+ * Output is CSR: row_offsets has a block of nq_p + 1 ints per problem, problem p's at row_offsets[q_offsets[p] + p]
+ * (q_offsets[nprob] + nprob ints in all); query i of problem p owns idx / dist [o[i], o[i + 1]), positions in the flat
+ * arrays of `capacity` entries (a problem's first offset is the previous problem's last); train indices are local to
+ * the problem.  row_offsets, idx and dist follow `mem`; *total is a HOST int, the call waits once for it (and once more
+ * for the copies of a host call).  SVO_ERR_CAPACITY when the total exceeds `capacity` or one query has more than
+ * SVO_RADIUS_MAX_PER_QUERY matches (one query's sort is held in LDS: 8192 entries of 8 bytes, two workgroups in a CU's
+ * 160 KB): then row_offsets holds the offsets that would be needed (saturated at INT_MAX), *total their sum, and nothing
+ * else is written.                                                                                                    */
+#define SVO_RADIUS_MAX_PER_QUERY 8192
+int svo_radius_match(svo_ctx *ctx, int norm, const void *query, const void *train, int dim, const int *q_offsets,
+                     const int *t_offsets, int nprob, float max_distance, int *row_offsets, int *idx, float *dist,
+                     int capacity, int *total, int mem);
+/* svo_knn_match_gated: knnMatch with a mask -- svo_knn_match over the allowed (query, train) pairs only, in one of two
+ * forms (exactly one must be given, the other's pointers null):
+ *   mask      bytes, nonzero = allowed: problem p's nq_p x nt_p row-major matrix, the problems' matrices back to back
+ *             (cv::BFMatcher's `mask` argument); follows `mem`.
+ *   gate      no matrix exists: xy_query / xy_train (x, y floats per row of the query / train arrays, following `mem`)
+ *             and *gate (host).  Train row t is a candidate of query q when |y_q - y_t| <= dy_max and
+ *             dx_min <= x_q - x_t <= dx_max -- the subtraction, the absolute value and each comparison a float operation
+ *             of its own, in that order; a NaN anywhere fails.  A rectified pair: dy_max = the row tolerance, dx_min 0,
+ *             dx_max the largest disparity.
+ * A query with fewer than k candidates gets -1 / +inf in the missing slots.  Where every pair is allowed the result is
+ * svo_knn_match's, bit for bit.                                                                                        */
+typedef struct svo_match_gate {
+    float dy_max, dx_min, dx_max;
+} svo_match_gate;
+int svo_knn_match_gated(svo_ctx *ctx, int norm, const void *query, const void *train, int dim, const int *q_offsets,
+                        const int *t_offsets, int nprob, int k, const uint8_t *mask, const float *xy_query,
+                        const float *xy_train, const svo_match_gate *gate, int *idx, float *dist, int mem);
 
 /* ---- loop-closure detection: features ---------------------------------------------------------- */
 /* cv::ORB::create()->detectAndCompute(img, Mat(), kp, desc) of visualSLAM::checkLoopDetectorStatus,

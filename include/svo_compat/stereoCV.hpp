@@ -195,6 +195,14 @@ class StereoProcess {
     // contract; upstream leaves color3dMap alone in this method.  The test table is the library's own unless
     // svo_brief_set_pattern has set OpenCV's.
     bool BRIEF_FLAG = false;
+    // ours, opt-in (off: every method issues the calls it always issued): with BRIEF_FLAG / SIFT_FLAG, CROSS_CHECK_FLAG pairs the
+    // features by svo_match_cross(SVO_CROSS_CV) -- BFMatcher(norm, true).match -- instead of knnMatch(2) + ratio 0.8;
+    // EPIPOLAR_GATE_FLAG restricts stereoTriangulate's candidates to the right features within epipolarRows rows of the left one
+    // and 0 ... maxDisparity columns to its left (svo_knn_match_gated; the pair is taken as rectified)
+    bool CROSS_CHECK_FLAG = false;
+    bool EPIPOLAR_GATE_FLAG = false;
+    float epipolarRows = 2.0f;
+    float maxDisparity = 128.0f;
     int siftFeaturesStereo = 20000, briefBytes = 32;
     std::vector<Point2f> stereoPairs1, stereoPairs2, stereoInliers1, stereoInliers2;
 
@@ -449,8 +457,8 @@ class StereoProcess {
         briefFeaturesBatch(imgs, 2, kps, desc);
         const std::vector<Point2f> xy1 = keypoint_points(kps[0]), xy2 = keypoint_points(kps[1]);
         std::vector<Point2f> pt1, pt2;
-        ratio_match_points(ctx(), SVO_MATCH_L2_U8, desc[0].data(), desc[1].data(), briefBytes, (int)xy1.size(), (int)xy2.size(), fp(xy1),
-                           fp(xy2), pt1, pt2);
+        sparse_match_points(ctx(), SparseMatch{CROSS_CHECK_FLAG, EPIPOLAR_GATE_FLAG, epipolarRows, maxDisparity}, SVO_MATCH_L2_U8,
+                            desc[0].data(), desc[1].data(), briefBytes, (int)xy1.size(), (int)xy2.size(), fp(xy1), fp(xy2), pt1, pt2);
         stereoPairs1 = pt1;
         stereoPairs2 = pt2;
         if (pt1.size() < 8)
@@ -497,8 +505,9 @@ class StereoProcess {
         std::vector<float> desc[2];
         siftFeaturesBatch(imgs, 2, siftFeaturesMono, kps, desc);
         const std::vector<Point2f> xy1 = keypoint_points(kps[0]), xy2 = keypoint_points(kps[1]);
-        ratio_match_points(ctx(), SVO_MATCH_L2_F32, desc[0].data(), desc[1].data(), 128, (int)xy1.size(), (int)xy2.size(), fp(xy1),
-                           fp(xy2), pt1, pt2);
+        // two views of one camera: no epipolar rows to gate by
+        sparse_match_points(ctx(), SparseMatch{CROSS_CHECK_FLAG, false, epipolarRows, maxDisparity}, SVO_MATCH_L2_F32, desc[0].data(),
+                            desc[1].data(), 128, (int)xy1.size(), (int)xy2.size(), fp(xy1), fp(xy2), pt1, pt2);
     }
 #if defined(SVO_WITH_OPENCV) && defined(CV_16SC1)
     static constexpr int kDisp16S = CV_16SC1;

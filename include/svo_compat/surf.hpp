@@ -62,16 +62,17 @@ inline void surf_features_batch(svo_ctx *ctx, const Mat *const *imgs, int n, dou
 
 // SURF on both images (one set of launches), BFMatcher().knnMatch(desc1, desc2, matches, 2), m.distance < 0.8 * n.distance:
 // the points of the surviving pairs, in the order of the left image's key points (ratio_match_points).
+// `how`: the pairing (sparse_match_points); its default is the reference's block.
 inline void surf_ratio_pairs(svo_ctx *ctx, const Mat &im1, const Mat &im2, double hessian, std::vector<Point2f> &pt1,
-                             std::vector<Point2f> &pt2)
+                             std::vector<Point2f> &pt2, const SparseMatch &how = SparseMatch())
 {
     const Mat *imgs[2] = {&im1, &im2};
     std::vector<KeyPoint> kps[2];
     std::vector<float> desc[2];
     surf_features_batch(ctx, imgs, 2, hessian, kps, desc);
     const std::vector<Point2f> xy1 = keypoint_points(kps[0]), xy2 = keypoint_points(kps[1]);
-    ratio_match_points(ctx, SVO_MATCH_L2_F32, desc[0].data(), desc[1].data(), 64, (int)xy1.size(), (int)xy2.size(),
-                       reinterpret_cast<const float *>(xy1.data()), reinterpret_cast<const float *>(xy2.data()), pt1, pt2);
+    sparse_match_points(ctx, how, SVO_MATCH_L2_F32, desc[0].data(), desc[1].data(), 64, (int)xy1.size(), (int)xy2.size(),
+                        reinterpret_cast<const float *>(xy1.data()), reinterpret_cast<const float *>(xy2.data()), pt1, pt2);
 }
 
 }  // namespace svo_compat

@@ -314,6 +314,59 @@ inline void ratio_match_points(svo_ctx *ctx, int norm, const void *desc1, const 
     pt2.resize((size_t)cnt);
 }
 
+// How a sparse branch pairs its features (ours, opt-in: CROSS_CHECK_FLAG / EPIPOLAR_GATE_FLAG of visualSLAM and StereoProcess).
+// Both off: ratio_match_points, the reference's block, call for call.
+//   gate   a rectified pair: train row t is a candidate of query q when |y_q - y_t| <= epipolarRows and
+//          0 <= x_q - x_t <= maxDisparity (svo_knn_match_gated, k 2), then the 0.8 ratio test among the candidates
+//   cross  BFMatcher(norm, true).match as OpenCV 3.2 runs it (svo_match_cross, SVO_CROSS_CV) in place of knnMatch(2) + ratio; the
+//          cross-check takes no mask, so with `gate` as well the pairs outside the band are dropped afterwards
+struct SparseMatch {
+    bool cross = false, gate = false;
+    float epipolarRows = 2.0f, maxDisparity = 128.0f;
+};
+inline void sparse_match_points(svo_ctx *ctx, const SparseMatch &how, int norm, const void *desc1, const void *desc2, int dim, int n1,
+                                int n2, const float *xy1, const float *xy2, std::vector<Point2f> &pt1, std::vector<Point2f> &pt2)
+{
+    if (!how.cross && !how.gate) {
+        ratio_match_points(ctx, norm, desc1, desc2, dim, n1, n2, xy1, xy2, pt1, pt2);
+        return;
+    }
+    pt1.clear();
+    pt2.clear();
+    if (n1 < 1 || n2 < 1)
+        return;
+    const int qo[2] = {0, n1}, to[2] = {0, n2};
+    const svo_match_gate g = {how.epipolarRows, 0.0f, how.maxDisparity};
+    if (how.cross) {
+        std::vector<int> idx((size_t)n1);
+        std::vector<float> dist((size_t)n1);
+        check(svo_match_cross(ctx, norm, desc1, desc2, dim, qo, to, 1, SVO_CROSS_CV, idx.data(), dist.data(), SVO_MEM_HOST));
+        for (int i = 0; i < n1; i++) {
+            if (idx[i] < 0)
+                continue;
+            const float *a = xy1 + 2 * (size_t)i, *b = xy2 + 2 * (size_t)idx[i];
+            if (how.gate) {  // svo_match_gate's test, operation for operation
+                const float dy = a[1] - b[1], ady = dy < 0 ? -dy : dy, dx = a[0] - b[0];
+                if (!(ady <= g.dy_max && dx >= g.dx_min && dx <= g.dx_max))
+                    continue;
+            }
+            pt1.emplace_back(a[0], a[1]);
+            pt2.emplace_back(b[0], b[1]);
+        }
+        return;
+    }
+    std::vector<int> idx((size_t)n1 * 2);
+    std::vector<float> dist((size_t)n1 * 2);
+    check(svo_knn_match_gated(ctx, norm, desc1, desc2, dim, qo, to, 1, 2, nullptr, xy1, xy2, &g, idx.data(), dist.data(), SVO_MEM_HOST));
+    pt1.assign((size_t)n1, Point2f());
+    pt2.assign((size_t)n1, Point2f());
+    int cnt = 0;
+    check(svo_ratio_pairs(ctx, idx.data(), dist.data(), n1, 2, 0.8, xy1, xy2, reinterpret_cast<float *>(pt1.data()),
+                          reinterpret_cast<float *>(pt2.data()), nullptr, &cnt, SVO_MEM_HOST));
+    pt1.resize((size_t)cnt);
+    pt2.resize((size_t)cnt);
+}
+
 // removeDuplicates (include/monoUtils.h:195-213), the body both classes carry: the indices of `fresh`, ascending, that have no point
 // of `base` listed in `mask` within `radius` (norm(p1 - p2) < radius).  The list goes through as it is, repeats and order included;
 // an EMPTY list means no reference point and everything is kept, as upstream's empty loop does -- so the call never gets a null

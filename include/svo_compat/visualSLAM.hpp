@@ -63,6 +63,15 @@ class visualSLAM {
     bool STAR_FLAG = false;
     int starMaxSize = 45;
     int starResponseThreshold = 30;
+    // with DENSE_FLAG == false (ours, opt-in; off: every method issues the calls it always issued): CROSS_CHECK_FLAG pairs the
+    // features of every sparse branch by svo_match_cross(SVO_CROSS_CV) -- BFMatcher(norm, true).match -- instead of knnMatch(2) +
+    // ratio 0.8; EPIPOLAR_GATE_FLAG restricts a left feature's candidates to the right features within epipolarRows rows of it
+    // and 0 ... maxDisparity columns to its left (svo_knn_match_gated; the pair is taken as rectified)
+    bool CROSS_CHECK_FLAG = false;
+    bool EPIPOLAR_GATE_FLAG = false;
+    float epipolarRows = 2.0f;
+    float maxDisparity = 128.0f;
+    SparseMatch sparseMatch() const { return SparseMatch{CROSS_CHECK_FLAG, EPIPOLAR_GATE_FLAG, epipolarRows, maxDisparity}; }
     double focal_x = 7.188560000000e+02, cx = 6.071928000000e+02;
     double focal_y = 7.188560000000e+02, cy = 1.852157000000e+02;
     int gridStep = 30;              // src/triangulation.cpp:89
@@ -213,7 +222,7 @@ class visualSLAM {
         } else if (SURF_FLAG) {
             if (mat_cols(im1) != mat_cols(im2) || mat_rows(im1) != mat_rows(im2) || mat_channels(im1) != mat_channels(im2))
                 throw SvoError(SVO_ERR_ARG, "stereoTriangulate: the two images differ in size");
-            surf_ratio_pairs(ctx_, im1, im2, (double)surfHessian, refPts, trkPts);
+            surf_ratio_pairs(ctx_, im1, im2, (double)surfHessian, refPts, trkPts, sparseMatch());
         } else if (STAR_FLAG) {
             starBriefRatioPairs(im1, im2, refPts, trkPts);  // no FmatThresholding, as the ORB branch beside it
         } else {
@@ -617,7 +626,8 @@ class visualSLAM {
         int n[2] = {0, 0};
         check(svo_orb_extract_batch(ctx_, imgs, 2, mat_cols(im1), mat_rows(im1), mat_channels(im1), &prm, f(kp), nullptr, nullptr,
                                     nullptr, desc.data(), n, SVO_MEM_HOST));
-        ratio_match_points(ctx_, SVO_MATCH_L2_U8, desc.data(), desc.data() + nf * 8, 32, n[0], n[1], f(kp), f(kp) + 2 * nf, pt1, pt2);
+        sparse_match_points(ctx_, sparseMatch(), SVO_MATCH_L2_U8, desc.data(), desc.data() + nf * 8, 32, n[0], n[1], f(kp), f(kp) + 2 * nf, pt1,
+                            pt2);
     }
     // n (1 ... 16) images of one size through one svo_star_detect_batch call.  The capacity grows to what the library asks for, so a
     // call never loses key points.
@@ -693,8 +703,8 @@ class visualSLAM {
                 kxy[2 * dst] = xy[2 * src];
                 kxy[2 * dst + 1] = xy[2 * src + 1];
             }
-        ratio_match_points(ctx_, SVO_MATCH_L2_U8, desc.data(), desc.data() + cap * 32, 32, n_out[0], n_out[1], kxy.data(),
-                           kxy.data() + 2 * cap, pt1, pt2);
+        sparse_match_points(ctx_, sparseMatch(), SVO_MATCH_L2_U8, desc.data(), desc.data() + cap * 32, 32, n_out[0], n_out[1], kxy.data(),
+                            kxy.data() + 2 * cap, pt1, pt2);
     }
     void compact2(const std::vector<uint8_t> &mask, std::vector<Point2f> &a, std::vector<Point2f> &b)
     {

@@ -1690,6 +1690,135 @@ def ratio_pairs(self, idx, dist, xy_query, xy_train, ratio=0.8):
     return p1[:cnt.value].copy(), p2[:cnt.value].copy(), mask[:nq].copy()
 
 
+# ---- cross-check, radius and masked matching (svo_match_cross, svo_radius_match, svo_knn_match_gated) -----------------
+CROSS_MUTUAL, CROSS_CV = 0, 1
+RADIUS_MAX_PER_QUERY = 8192
+
+
+class MatchGate(C.Structure):
+    """``svo_match_gate``: train row t is a candidate of query q when |y_q - y_t| <= dy_max and dx_min <= x_q - x_t <= dx_max."""
+    _fields_ = [("dy_max", C.c_float), ("dx_min", C.c_float), ("dx_max", C.c_float)]
+
+
+def _match_problem(query, train, norm, q_offsets, t_offsets):
+    """the arguments the matching calls share -> (q, t, dim, device?, nq, nt, q_offsets, t_offsets, nprob)"""
+    q, dim = _match_rows(query, norm)
+    t, dim_t = _match_rows(train, norm)
+    assert dim == dim_t, "query and train rows differ in length"
+    dev = _is_device(q)
+    assert dev == _is_device(t), "query and train must live in the same memory"
+    nq, nt = int(q.shape[0]), int(t.shape[0])
+    qo = np.ascontiguousarray([0, nq] if q_offsets is None else q_offsets, np.int32)
+    to = np.ascontiguousarray([0, nt] if t_offsets is None else t_offsets, np.int32)
+    assert len(qo) == len(to) and len(qo) >= 2
+    assert int(qo[-1]) <= nq and int(to[-1]) <= nt, "offsets beyond the arrays"
+    return q, t, dim, dev, nq, nt, qo, to, len(qo) - 1
+
+
+def _same_memory(a, dev, dtype, what):
+    """an auxiliary array of a matching call, contiguous, in the memory of the descriptors"""
+    assert _is_device(a) == dev, f"{what} must live in the memory of the descriptors"
+    if dev:
+        import torch
+
+        return a.to(getattr(torch, dtype)).contiguous()
+    return np.ascontiguousarray(a, getattr(np, dtype))
+
+
+@_ctx_method
+def match_cross(self, query, train, norm=MATCH_L2_U8, mode=CROSS_MUTUAL, q_offsets=None, t_offsets=None):
+    """``svo_match_cross`` (cv::BFMatcher(norm, true).match): -> (idx [nq] int32, dist [nq] float32), -1 / inf for a query without
+    a partner.  ``CROSS_MUTUAL``: i and j are each other's best; ``CROSS_CV``: OpenCV 3.2's reverse-search-only update.  numpy
+    arrays, or device tensors which give device tensors back; offsets as ``knn_match``."""
+    q, t, dim, dev, nq, nt, qo, to, nprob = _match_problem(query, train, norm, q_offsets, t_offsets)
+    if dev:
+        import torch
+
+        idx = torch.full((nq,), -1, dtype=torch.int32, device=q.device)
+        dist = torch.full((nq,), float("inf"), dtype=torch.float32, device=q.device)
+        torch.cuda.synchronize(q.device)
+    else:
+        idx, dist = np.full(nq, -1, np.int32), np.full(nq, np.inf, np.float32)
+    _check(self.lib.svo_match_cross(self._h, int(norm), _ptr(q), _ptr(t), dim, _ptr(qo), _ptr(to), nprob, int(mode), _ptr(idx),
+                                    _ptr(dist), MEM_DEVICE if dev else MEM_HOST))
+    if dev:
+        _check(self.lib.svo_ctx_sync(self._h))
+    return idx, dist
+
+
+@_ctx_method
+def radius_match(self, query, train, max_distance, norm=MATCH_L2_U8, capacity=None, q_offsets=None, t_offsets=None):
+    """``svo_radius_match`` (cv::BFMatcher::radiusMatch) -> (row_offsets, idx, dist): query i of problem p owns
+    ``idx[o[i]:o[i + 1]]`` with ``o = row_offsets[q_offsets[p] + p:]``, sorted by distance, ties to the lower train index.
+    ``capacity`` (entries of idx / dist; default: every pair of one problem) too small, or a query with more than
+    ``RADIUS_MAX_PER_QUERY`` matches, raises ``SvoError`` (``SVO_ERR_CAPACITY``) whose ``row_offsets`` / ``total`` attributes hold
+    what would be needed.  numpy arrays, or device tensors which give device tensors back."""
+    q, t, dim, dev, nq, nt, qo, to, nprob = _match_problem(query, train, norm, q_offsets, t_offsets)
+    if capacity is None:
+        capacity = int(np.sum(np.diff(qo).astype(np.int64) * np.diff(to).astype(np.int64)))
+    capacity = int(capacity)
+    n_off = int(qo[-1]) + nprob
+    total = C.c_int(0)
+    if dev:
+        import torch
+
+        off = torch.zeros(n_off, dtype=torch.int32, device=q.device)
+        idx = torch.full((max(capacity, 1),), -1, dtype=torch.int32, device=q.device)
+        dist = torch.full((max(capacity, 1),), float("inf"), dtype=torch.float32, device=q.device)
+        torch.cuda.synchronize(q.device)
+    else:
+        off = np.zeros(n_off, np.int32)
+        idx, dist = np.full(max(capacity, 1), -1, np.int32), np.full(max(capacity, 1), np.inf, np.float32)
+    rc = self.lib.svo_radius_match(self._h, int(norm), _ptr(q), _ptr(t), dim, _ptr(qo), _ptr(to), nprob, C.c_float(max_distance),
+                                   _ptr(off), _ptr(idx), _ptr(dist), capacity, C.byref(total), MEM_DEVICE if dev else MEM_HOST)
+    if rc == SVO_ERR_CAPACITY and total.value > 0:
+        err = SvoError(rc, load().svo_last_error().decode(errors="replace"))
+        err.row_offsets, err.total = off, total.value
+        raise err
+    _check(rc)
+    return off, idx[:total.value], dist[:total.value]
+
+
+@_ctx_method
+def knn_match_gated(self, query, train, k=2, norm=MATCH_L2_U8, mask=None, gate=None, xy_query=None, xy_train=None, q_offsets=None,
+                    t_offsets=None):
+    """``svo_knn_match_gated`` (knnMatch with a mask): ``knn_match`` over the allowed pairs only.  Either ``mask`` -- nonzero bytes
+    allow; one problem: an nq x nt array, a batch: the problems' matrices flattened back to back -- or ``gate`` = (dy_max,
+    dx_min, dx_max) with the key points ``xy_query`` / ``xy_train`` (n x 2): |y_q - y_t| <= dy_max and dx_min <= x_q - x_t <=
+    dx_max.  numpy arrays, or device tensors which give device tensors back."""
+    assert (mask is None) != (gate is None), "either a mask or a gate"
+    q, t, dim, dev, nq, nt, qo, to, nprob = _match_problem(query, train, norm, q_offsets, t_offsets)
+    m = xq = xt = g = None
+    if mask is not None:
+        m = _same_memory(mask, dev, "uint8", "mask").reshape(-1)
+        need = int(np.sum(np.diff(qo).astype(np.int64) * np.diff(to).astype(np.int64)))
+        assert int(m.shape[0]) == need, "the mask holds nq x nt bytes per problem"
+        if need == 0:  # nothing to read: any address stands for the form
+            m = np.zeros(1, np.uint8) if not dev else m.new_zeros(1)
+    else:
+        xq = _same_memory(xy_query, dev, "float32", "xy_query").reshape(-1, 2)
+        xt = _same_memory(xy_train, dev, "float32", "xy_train").reshape(-1, 2)
+        assert int(xq.shape[0]) == nq and int(xt.shape[0]) == nt, "a key point per descriptor row"
+        if nq == 0 or nt == 0:
+            xq = xq if nq else (np.zeros((1, 2), np.float32) if not dev else xq.new_zeros((1, 2)))
+            xt = xt if nt else (np.zeros((1, 2), np.float32) if not dev else xt.new_zeros((1, 2)))
+        g = gate if isinstance(gate, MatchGate) else MatchGate(*(float(v) for v in gate))
+    if dev:
+        import torch
+
+        idx = torch.full((nq, k), -1, dtype=torch.int32, device=q.device)
+        dist = torch.full((nq, k), float("inf"), dtype=torch.float32, device=q.device)
+        torch.cuda.synchronize(q.device)
+    else:
+        idx, dist = np.full((nq, k), -1, np.int32), np.full((nq, k), np.inf, np.float32)
+    _check(self.lib.svo_knn_match_gated(self._h, int(norm), _ptr(q), _ptr(t), dim, _ptr(qo), _ptr(to), nprob, int(k), _ptr(m),
+                                        _ptr(xq), _ptr(xt), C.byref(g) if g is not None else None, _ptr(idx), _ptr(dist),
+                                        MEM_DEVICE if dev else MEM_HOST))
+    if dev:
+        _check(self.lib.svo_ctx_sync(self._h))
+    return idx, dist
+
+
 @_ctx_method
 def pnp_ransac(self, obj, img, K4, iterations=100, reproj_err=1.0, confidence=0.99, seed=0):
     obj = np.ascontiguousarray(obj, np.float32).reshape(-1, 3)
