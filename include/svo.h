@@ -177,6 +177,34 @@ int svo_compact(svo_ctx *ctx, const uint8_t *mask, int n, const float *in_a, int
 int svo_fransac(svo_ctx *ctx, const float *p1, const float *p2, int n, double threshold,
                 double confidence, int max_iters, uint64_t seed, uint8_t *mask, double *F9,
                 int *inlier_count, int *iters_run, int mem);
+/* The batch form the lock-step front-ends queue: 1 <= k <= 16 independent problems in ONE launch sequence, with the
+ * order-preserving compaction of up to three payload arrays by each fresh mask riding along (no launch of its own).
+ * DEVICE pointers throughout, asynchronous on the context's stream.  Two problems or more run the single-wave build, one
+ * problem the lone-chunk build svo_fransac runs.
+ *   cap        capacity of p1 / p2 / mask / payload; the mask's cap bytes are all written (zero from the live count on)
+ *   d_n        live count (device int, clamped to cap), or NULL: cap pairs
+ *   F9, inlier_count, iters_run   optional, as in svo_fransac
+ *   payload_in[a] / payload_out[a] / payload_stride[a]   rows of payload_stride[a] floats, cap of them; the rows with
+ *              mask == 1 go to payload_out[a] in order.  payload_in[0] == NULL: no compaction.  Outputs must not overlap
+ *              inputs.  payload_count (optional): the number of rows kept
+ *   gate       optional device int: with *gate == 0 the problem's outputs are left untouched */
+typedef struct svo_fransac_problem {
+    const float *p1, *p2;
+    int cap;
+    const int *d_n;
+    double threshold, confidence;
+    int max_iters;
+    uint64_t seed;
+    uint8_t *mask;
+    double *F9;
+    int *inlier_count, *iters_run;
+    const float *payload_in[3];
+    float *payload_out[3];
+    int payload_stride[3];
+    int *payload_count;
+    const int *gate;
+} svo_fransac_problem;
+int svo_fransac_batch(svo_ctx *ctx, int k, const svo_fransac_problem *problems);
 
 /* ---- stereo triangulation: src/triangulation.cpp:142-160 ------------------------------------ */
 /* P1 = K[I|0], P2 = K[I|(-b,0,0)^T] (3x4 row-major doubles, HOST memory always). */

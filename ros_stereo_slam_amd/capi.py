@@ -282,6 +282,37 @@ def fransac(self, p1, p2, threshold, confidence=0.99, max_iters=1000, seed=0):
     return cnt.value, mask, F.reshape(3, 3), iters.value
 
 
+class FransacProblem(C.Structure):
+    """``svo_fransac_problem``: one problem of ``svo_fransac_batch``; every pointer is a device address."""
+    _fields_ = [("p1", C.c_void_p), ("p2", C.c_void_p), ("cap", C.c_int), ("d_n", C.c_void_p),
+                ("threshold", C.c_double), ("confidence", C.c_double), ("max_iters", C.c_int), ("seed", C.c_uint64),
+                ("mask", C.c_void_p), ("F9", C.c_void_p), ("inlier_count", C.c_void_p), ("iters_run", C.c_void_p),
+                ("payload_in", C.c_void_p * 3), ("payload_out", C.c_void_p * 3), ("payload_stride", C.c_int * 3),
+                ("payload_count", C.c_void_p), ("gate", C.c_void_p)]
+
+
+@_ctx_method
+def fransac_batch(self, problems):
+    """``svo_fransac_batch``: up to 16 F-matrix RANSAC problems in one launch sequence, each with the compaction of up to
+    three payload arrays by its fresh mask.  ``problems``: dicts of device tensors (or raw addresses) --
+    ``p1, p2, cap, threshold, mask`` and optionally ``d_n, confidence, max_iters, seed, F9, inlier_count, iters_run,
+    payload`` (a list of up to three ``(in, stride, out)``), ``payload_count, gate``.  Asynchronous on the ctx stream."""
+    k = len(problems)
+    arr = (FransacProblem * max(k, 1))()
+    for q, p in zip(arr, problems):
+        q.p1, q.p2, q.cap, q.d_n = _ptr(p["p1"]), _ptr(p["p2"]), int(p["cap"]), _ptr(p.get("d_n"))
+        q.threshold, q.confidence = float(p["threshold"]), float(p.get("confidence", 0.99))
+        q.max_iters, q.seed = int(p.get("max_iters", 1000)), int(p.get("seed", 0))
+        q.mask, q.F9 = _ptr(p["mask"]), _ptr(p.get("F9"))
+        q.inlier_count, q.iters_run = _ptr(p.get("inlier_count")), _ptr(p.get("iters_run"))
+        payload = list(p.get("payload", ()))
+        assert len(payload) <= 3
+        for a, (src, stride, dst) in enumerate(payload):
+            q.payload_in[a], q.payload_stride[a], q.payload_out[a] = _ptr(src), int(stride), _ptr(dst)
+        q.payload_count, q.gate = _ptr(p.get("payload_count")), _ptr(p.get("gate"))
+    _check(self.lib.svo_fransac_batch(self._h, k, arr))
+
+
 def stereo_projections(fx, fy, cx, cy, baseline):
     P1, P2 = np.zeros((3, 4)), np.zeros((3, 4))
     _check(load().svo_stereo_projections(C.c_double(fx), C.c_double(fy), C.c_double(cx), C.c_double(cy),

@@ -9,15 +9,30 @@
 //     solve   lane 0: counter-based 7-sample (collinear samples re-drawn), 7x9 Gauss-Jordan in
 //             LDS, cubic det(l*F1 + (1-l)*F2) = 0, up to three unit-norm models (LDS + HBM);
 //     score   all lanes, model after model: the N correspondences strided over the 64 lanes,
-//             symmetric epipolar distance in f64, inlier count reduced with DPP;
-//     finish  the LAST wave to finish (ticket counter) replays the SEQUENTIAL loop over the
+//             symmetric epipolar distance in f64, the inlier count from the ballots of `error <= thr`;
+//             a first phase that has a successor also KEEPS those ballots, one bit plane per
+//             (iteration, model) in the workspace (FrJob::planes);
+//     replay  the LAST workgroup to finish (ticket counter) replays the SEQUENTIAL loop over the
 //             counts (first-best-wins, adaptive iteration bound), so the answer equals the serial
-//             algorithm's, and -- once the loop has ended -- writes the mask of the winning model,
-//             the model and the counts.
-// Two phases (iterations [0,64) and [64,max)): the second launch (64 waves per problem) returns at
-// once when the adaptive bound was reached in the first, which is the common case at VO inlier
-// ratios (0.99 confidence, 85% inliers -> 12 iterations).  (Until round 2 this was five launches:
-// solve, score, solve, score, mask -- each waiting its turn beside the tracking launches.)
+//             algorithm's, and -- once the loop has ended -- writes the model and the counts;
+//     finish  the mask of the winning model and the order-preserving compaction of the payload
+//             arrays by it.
+// Two phases (iterations [0,64) and [64,max)), a launch each.  Who finishes:
+//   * the loop ended in the first phase (the common case at VO inlier ratios: 0.99 confidence, 85%
+//     inliers -> 12 iterations) and a launch follows: the first phase's last workgroup marks the
+//     state "finish pending" (RansacState::pad) and leaves; ALL workgroups of the second launch
+//     -- which had nothing to do in this case -- share the finish (fr_wide_finish): blocks of 64
+//     consecutive pairs, a pair per lane, `kept` and the number of kept pairs before it read from
+//     the winner's bit plane alone.  No error is evaluated again, no ticket is taken and no
+//     workgroup waits for another;
+//   * everything else -- the loop runs on into the second phase, a call of at most 64 iterations
+//     (one launch), fewer than 15 pairs (fr_small_case), a launch in which a workgroup found the
+//     gate closed -- the workgroup with the last ticket finishes alone, evaluating the winner's
+//     errors again (the tail of fr_ransac_kernel).
+// The payload's outputs must not overlap its inputs, in either finish (rows are moved by
+// independent lanes and, in the wide finish, by independent workgroups).
+// (Until round 2 this was five launches: solve, score, solve, score, mask -- each waiting its turn
+// beside the tracking launches.)
 #include "ransac_common.hip.h"
 #include "svo_internal.h"
 
@@ -42,6 +57,10 @@ struct FrJob {
     RansacState *st;
     double *Fm;
     int *nmodels, *counts;
+    // the first phase's ballots of `error <= thr`: plane (it * 3 + model) of plane_words 64-bit words; pair i is bit
+    // (i % 256) / 4 of word (i / 256) * 4 + i % 4 -- (step, wave, q) of the scoring pass, in either build
+    unsigned long long *planes;
+    int plane_words;
     unsigned *ticket;
     uint8_t *mask;
     double *Fbest;
@@ -484,6 +503,93 @@ __device__ void fr_small_case(const FrJob &job, int n, bool due, double *sA, dou
     }
 }
 
+constexpr int FINISH_PENDING = 1;  // RansacState::pad: the loop has ended, mask and compaction are the next launch's
+
+// The finish of a problem whose loop ended in the first phase, by ALL waves of the launch that follows (file header):
+// wave w of the launch takes the blocks w, w + waves, ... of 64 consecutive pairs of [0, n_host), a pair per lane.
+// `kept` and the number of kept pairs before a pair come from the winner's bit plane alone: the popcounts of the
+// earlier 256-pair steps' words, plus, inside the own step, the earlier lanes' four pairs and the own lane's earlier q.
+// Words of steps at or above n were never written and are never used: a pair at or above n is not kept.
+template <int NW> __device__ void fr_wide_finish(const FrJob &job, const RansacState &s, int n)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n_host = job.n_host;
+    const bool have = s.best_iter >= 0 && s.best_count > 0;
+    const unsigned long long *__restrict__ plane =
+        job.planes + (size_t)((have ? s.best_iter : 0) * 3 + (have ? s.best_model : 0)) * job.plane_words;
+    uint8_t *__restrict__ mask = job.mask;
+    const bool compacting = job.c_in[0] != nullptr;
+    if (compacting && job.c_count && blockIdx.x == 0 && threadIdx.x == 0)
+        *job.c_count = have ? s.best_count : 0;
+    for (int blk = (int)blockIdx.x * NW + wave; blk * 64 < n_host; blk += (int)gridDim.x * NW) {
+        const int i = blk * 64 + lane;
+        bool keep = false;
+        int pos = 0;
+        if (have && blk * 64 < n) {  // wave-uniform
+            const int w0 = (blk >> 2) * 4;  // the own step's first word
+            int earlier = 0;
+            for (int w = lane; w < w0; w += 64)
+                earlier += __popcll(plane[w]);
+            earlier = wave_sum_dpp(earlier);
+            const int l = (blk & 3) * 16 + (lane >> 2), q = lane & 3;  // the scoring lane and its q that judged pair i
+            const unsigned long long below = (1ull << l) - 1ull;
+            int inside = 0;
+#pragma unroll
+            for (int qq = 0; qq < 4; qq++) {
+                const unsigned long long word = plane[w0 + qq];
+                inside += __popcll(word & below) + ((qq < q) ? (int)((word >> l) & 1ull) : 0);
+                keep = qq == q ? ((word >> l) & 1ull) != 0 : keep;
+            }
+            keep = keep && i < n;
+            pos = earlier + inside;
+        }
+        if (i < n_host)
+            mask[i] = keep ? 1 : 0;
+        if (compacting && keep) {  // the rows' loads first, then their stores
+            float2 v2[3];
+            float v3[3][3];
+            bool pair_ok[3];
+#pragma unroll
+            for (int r = 0; r < 3; r++) {
+                const float *in = job.c_in[r];
+                const int stn = job.c_stride[r];
+                pair_ok[r] = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(job.c_out[r])) & 7) == 0;
+                if (in && stn == 2) {
+                    if (pair_ok[r])
+                        v2[r] = reinterpret_cast<const float2 *>(in)[i];
+                    else
+                        v2[r] = make_float2(in[2 * (size_t)i], in[2 * (size_t)i + 1]);
+                } else if (in && stn == 3) {
+#pragma unroll
+                    for (int k = 0; k < 3; k++)
+                        v3[r][k] = in[3 * (size_t)i + k];
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 3; r++) {
+                const float *in = job.c_in[r];
+                float *out = job.c_out[r];
+                const int stn = job.c_stride[r];
+                if (!in)
+                    continue;
+                if (stn == 2) {
+                    if (pair_ok[r])
+                        reinterpret_cast<float2 *>(out)[pos] = v2[r];
+                    else
+                        out[2 * (size_t)pos] = v2[r].x, out[2 * (size_t)pos + 1] = v2[r].y;
+                } else if (stn == 3) {
+#pragma unroll
+                    for (int k = 0; k < 3; k++)
+                        out[3 * (size_t)pos + k] = v3[r][k];
+                } else {
+                    for (int k = 0; k < stn; k++)
+                        out[(size_t)pos * stn + k] = in[(size_t)i * stn + k];
+                }
+            }
+        }
+    }
+}
+
 // One phase of the RANSAC loop: iterations [it0, min(it1_cap, max_iters)), one wave per iteration (see the
 // file header).  `final_phase`: no launch follows, so the last wave finishes the problem whatever the state.
 // LEAN: the lock-step groups -- single-wave workgroups capped at 96 VGPRs (with spills), so that a wave starts beside
@@ -491,7 +597,9 @@ __device__ void fr_small_case(const FrJob &job, int n, bool due, double *sA, dou
 // iterations would leave 15 of 16 SIMDs idle: FOUR waves per iteration (wave 0 solves, all four share the scoring
 // pass, and the finishing workgroup's four waves share the mask / compaction pass), 128-VGPR build.
 // TAIL: the instantiation the LAST launch of a call uses.  It also carries cv::findFundamentalMat's behaviour below 15
-// pairs (fr_small_case), so that the kernel of the first 64 iterations -- the one on every frame's path -- stays as it was.
+// pairs (fr_small_case), so that the kernel of the first 64 iterations -- the one on every frame's path -- stays as it was,
+// and the wide finish of a problem whose loop ended in the first phase (fr_wide_finish: every wave of the launch, in both
+// builds -- the bit plane's layout does not depend on the number of waves that scored).
 template <bool LEAN, bool TAIL>
 __global__ __launch_bounds__(LEAN ? 64 : 256, LEAN ? 5 : 4) void fr_ransac_kernel(FrBatchN<LEAN ? SVO_LK_MAX_JOBS : 1> batch, int it0, int it1_cap,
                                                                                    int final_phase)
@@ -533,8 +641,16 @@ __global__ __launch_bounds__(LEAN ? 64 : 256, LEAN ? 5 : 4) void fr_ransac_kerne
             fr_small_case<NW>(job, n, due, sA, sV, sPerm, sF, &s_last, &s_all_due);
         return;
     }
-    if (it0 > 0 && st->done)  // the loop ended in an earlier phase (the same answer in every wave of the launch)
+    if (it0 > 0 && st->done) {  // the loop ended in an earlier phase (the same answer in every wave of the launch)
+        if (TAIL && st->pad == FINISH_PENDING)  // ... whose last workgroup left mask and compaction to this launch's waves
+            fr_wide_finish<NW>(job, *st, n);
         return;
+    }
+    // a first phase with a successor keeps the ballots of its scoring pass: should the loop end here, the successor's waves
+    // finish from the winner's
+    const bool keep_planes = !TAIL && it0 == 0 && !final_phase;
+    unsigned long long *__restrict__ planes = job.planes;
+    const int plane_words = job.plane_words;
     const bool vec_ok = ((reinterpret_cast<uintptr_t>(p1) | reinterpret_cast<uintptr_t>(p2)) & 15) == 0;
     for (int it = it0 + (int)blockIdx.x; due && it < it1; it += gridDim.x) {
         if (wave == 0) {
@@ -555,11 +671,15 @@ __global__ __launch_bounds__(LEAN ? 64 : 256, LEAN ? 5 : 4) void fr_ransac_kerne
         // of its loads (nothing else to switch to), so a lane takes FOUR consecutive pairs per step with 16-byte
         // loads and requests the next step's before it uses this step's; the model being evaluated sits in
         // scalar registers.
+        // The ballots of `inlier` give the counts (a wave-uniform sum, no reduction afterwards) and, with `keep_planes`,
+        // the bit plane the wide finish reads: word (step, wave, q), bit lane (FrJob::planes).  Every wave takes every
+        // step up to n, so a step's four words are written whenever one of its pairs exists.
         int c0 = 0, c1 = 0, c2 = 0;
         if (nm > 0) {
             Quad cur, nxt;
             load_quad(cur, p1, p2, pt0, n, vec_ok);
-            for (int base = pt0; base < n; base += STEP) {
+            for (int start = wave * 256; start < n; start += STEP) {
+                const int base = start + 4 * lane;
                 if (base + STEP < n)
                     load_quad(nxt, p1, p2, base + STEP, n, vec_ok);
                 for (int k = 0; k < nm; k++) {
@@ -568,18 +688,22 @@ __global__ __launch_bounds__(LEAN ? 64 : 256, LEAN ? 5 : 4) void fr_ransac_kerne
                     for (int i = 0; i < 9; i++)
                         F[i] = uniform_f64(sF[k * 9 + i]);
                     int c = 0;
+                    unsigned long long word = 0;  // lane q keeps the ballot of the lanes' q-th pairs
 #pragma unroll
-                    for (int q = 0; q < 4; q++)
-                        c += (base + q < n && f_error(F, cur.x1[q], cur.y1[q], cur.x2[q], cur.y2[q]) <= thr) ? 1 : 0;
+                    for (int q = 0; q < 4; q++) {
+                        const unsigned long long bal =
+                            __ballot(base + q < n && f_error(F, cur.x1[q], cur.y1[q], cur.x2[q], cur.y2[q]) <= thr);
+                        c += __popcll(bal);
+                        word = lane == q ? bal : word;
+                    }
+                    if (keep_planes && lane < 4)
+                        planes[(size_t)(it * 3 + k) * plane_words + (start >> 6) + lane] = word;
                     c0 += k == 0 ? c : 0;
                     c1 += k == 1 ? c : 0;
                     c2 += k == 2 ? c : 0;
                 }
                 cur = nxt;
             }
-            c0 = wave_sum_dpp(c0);
-            c1 = nm > 1 ? wave_sum_dpp(c1) : 0;
-            c2 = nm > 2 ? wave_sum_dpp(c2) : 0;
         }
         if (NW > 1) {
             if (lane == 0) {
@@ -631,7 +755,8 @@ __global__ __launch_bounds__(LEAN ? 64 : 256, LEAN ? 5 : 4) void fr_ransac_kerne
     }
     if (threadIdx.x == 0) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // other waves' counts, not this CU's stale lines
-        const RansacState r = ransac_replay<3>(st, it0 == 0 ? 1 : 0, it1, max_iters, n, job.confidence, nmodels, counts, M);
+        RansacState r = ransac_replay<3>(st, it0 == 0 ? 1 : 0, it1, max_iters, n, job.confidence, nmodels, counts, M);
+        r.pad = keep_planes && r.done ? FINISH_PENDING : 0;  // every workgroup was due: the winner's plane is whole
         *st = r;
         s_state = r;
     }
@@ -655,6 +780,8 @@ __global__ __launch_bounds__(LEAN ? 64 : 256, LEAN ? 5 : 4) void fr_ransac_kerne
             for (int k = 0; k < 9; k++)
                 job.Fbest[k] = F[k];
     }
+    if (s.pad == FINISH_PENDING)
+        return;  // mask and compaction: the next launch's waves, from the winner's bit plane (fr_wide_finish)
     const bool compacting = job.c_in[0] != nullptr;
     __shared__ int s_kept[NW];
     int pos0 = 0;
@@ -732,9 +859,15 @@ int svo_launch_fransac_batch(svo_ctx *ctx, int n_jobs, const svo_fransac_job *jo
     }
     const int it_ws = it_max < 304 ? 304 : it_max;  // the least-median branch runs 300 iterations whatever max_iters says
     const size_t f_stride = (size_t)it_ws * 30, i_stride = ((size_t)it_ws * 4 + 32 + 15) / 16 * 16;
+    // the first phase's bit planes (FrJob::planes), behind the models in w_a: they live from the first launch to the second,
+    // as Fm does; a call of one launch keeps none
+    const int plane_words = it_max > PHASE_A ? (cap_max + 255) / 256 * 4 : 0;
+    const size_t p_stride = (size_t)PHASE_A * 3 * plane_words;
     int rc;
-    if ((rc = ctx->w_a.ensure(f_stride * sizeof(double) * n_jobs)) || (rc = ctx->w_b.ensure(i_stride * sizeof(int) * n_jobs)))
+    if ((rc = ctx->w_a.ensure((f_stride * sizeof(double) + p_stride * sizeof(unsigned long long)) * n_jobs)) ||
+        (rc = ctx->w_b.ensure(i_stride * sizeof(int) * n_jobs)))
         return rc;
+    unsigned long long *const planes0 = reinterpret_cast<unsigned long long *>(ctx->w_a.as<double>() + f_stride * n_jobs);
     FrBatch batch;
     int nb = 0;
     for (int k = 0; k < n_jobs; k++) {
@@ -757,6 +890,8 @@ int svo_launch_fransac_batch(svo_ctx *ctx, int n_jobs, const svo_fransac_job *jo
         j.counts = j.nmodels + it_ws;
         j.Fm = ctx->w_a.as<double>() + f_stride * nb;
         j.med = j.Fm + (size_t)it_ws * 27;
+        j.planes = planes0 + p_stride * nb;
+        j.plane_words = plane_words;
         j.cv_small = h.cv_small ? 1 : 0;
         j.ticket = ctx->d_tickets + nb;  // slots 0..15 (16..31: pnp.hip)
         j.mask = h.mask;
@@ -879,6 +1014,44 @@ extern "C" int svo_fransac(svo_ctx *ctx, const float *p1, const float *p2, int n
                            int *inlier_count, int *iters_run, int mem)
 {
     return svo_fransac_ex(ctx, p1, p2, n, threshold, confidence, max_iters, seed, mask, F9, inlier_count, iters_run, mem, true);
+}
+
+// svo_launch_fransac_batch with its optional compaction, as the lock-step front-ends queue it (device pointers)
+extern "C" int svo_fransac_batch(svo_ctx *ctx, int k, const svo_fransac_problem *problems)
+{
+    SVO_CHECK_ARG(ctx && problems && k >= 1 && k <= SVO_LK_MAX_JOBS);
+    svo_fransac_job jobs[SVO_LK_MAX_JOBS];
+    svo_compact_job payload[SVO_LK_MAX_JOBS];
+    for (int a = 0; a < k; a++) {
+        const svo_fransac_problem &p = problems[a];
+        SVO_CHECK_ARG(p.p1 && p.p2 && p.mask && p.cap > 0 && p.threshold > 0 && p.max_iters > 0);
+        svo_compact_job &c = payload[a];
+        c = svo_compact_job();
+        for (int r = 0; r < 3; r++) {
+            SVO_CHECK_ARG(!p.payload_in[r] || (p.payload_out[r] && p.payload_stride[r] >= 1));
+            c.in[r] = p.payload_in[r];
+            c.out[r] = p.payload_out[r];
+            c.stride[r] = p.payload_stride[r];
+        }
+        c.d_count = p.payload_count;
+        svo_fransac_job &j = jobs[a];
+        j = svo_fransac_job();
+        j.p1 = p.p1;
+        j.p2 = p.p2;
+        j.cap = p.cap;
+        j.d_n = p.d_n;
+        j.threshold = p.threshold;
+        j.confidence = p.confidence;
+        j.max_iters = p.max_iters;
+        j.seed = p.seed;
+        j.mask = p.mask;
+        j.d_F = p.F9;
+        j.d_count = p.inlier_count;
+        j.d_iters = p.iters_run;
+        j.then_compact = p.payload_in[0] ? &c : nullptr;
+        j.gate = p.gate;
+    }
+    return svo_launch_fransac_batch(ctx, k, jobs);
 }
 
 // cv_small = false: a RANSAC at any count >= 7 (the loop detector's geometric check)

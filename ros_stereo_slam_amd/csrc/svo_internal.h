@@ -332,7 +332,7 @@ struct svo_fransac_job {  // host-side description of one F-matrix RANSAC proble
     double *d_F;
     int *d_count, *d_iters;
     // optional: the compaction by the fresh mask (mask / cap / d_n of this job are used, the struct's own are
-    // ignored), done by the wave that writes the mask -- no launch of its own
+    // ignored), done by the waves that write the mask -- no launch of its own; the outputs must not overlap the inputs
     const svo_compact_job *then_compact = nullptr;
     const int *gate = nullptr;  // optional: every wave leaves at once when *gate == 0
     int gate_stride = 0;        // diagnostics only (svo_selftest_fransac_gate): workgroup b reads gate[b * gate_stride]
