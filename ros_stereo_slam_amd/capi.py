@@ -83,7 +83,66 @@ def _ptr(a):
     return C.c_void_p(int(a))
 
 
-class Pyramid:
+def _is_device(a) -> bool:
+    return hasattr(a, "is_cuda") and bool(a.is_cuda)
+
+
+def _mem_of(dev) -> int:
+    return MEM_DEVICE if dev else MEM_HOST
+
+
+def _image_shape(im):
+    h, w = im.shape[:2]
+    return w, h, (1 if im.ndim == 2 else im.shape[2])
+
+
+def _make_params(cls, default_fn_name, overrides, *before):
+    """A ``cls`` that the library's ``default_fn_name(*before, &p)`` filled, then the overrides by field name."""
+    p = cls()
+    getattr(load(), default_fn_name)(*before, C.byref(p))
+    for k, v in overrides.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def _as_params(cls, maker, value):
+    """``value`` when it is a ``cls``; otherwise ``maker``'s struct with the overrides of a dict (None: the defaults)."""
+    return value if isinstance(value, cls) else maker(**(value or {}))
+
+
+def _known_fields(cls, c_name, names):
+    """The parameter structs that refuse an unknown field with a TypeError rather than an assertion."""
+    for k in names:
+        if k not in dict(cls._fields_):
+            raise TypeError(f"{c_name} has no field {k}")
+
+
+class _Handle:
+    """A library object a context owns: ``close()`` destroys it once, and only while the context still has its handle.  A
+    subclass names the destroy function and says whether it is called as ``destroy(ctx, handle)`` or ``destroy(handle)``."""
+    _destroy = None
+    _destroy_takes_ctx = False
+
+    def close(self):
+        if self._h and self.ctx._h:
+            destroy = getattr(self.ctx.lib, self._destroy)
+            if self._destroy_takes_ctx:
+                destroy(self.ctx._h, self._h)
+            else:
+                destroy(self._h)
+        self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Pyramid(_Handle):
+    _destroy, _destroy_takes_ctx = "svo_pyramid_destroy", True
+
     def __init__(self, ctx: "Context", w: int, h: int, c: int, levels: int = 4, want_deriv: bool = True):
         """``want_deriv=False``: a pyramid without Scharr derivative levels (``svo_pyramid_create2``), as the front-end keeps
         for its right images; the tracker derives them when such a pyramid becomes its first image after all."""
@@ -135,17 +194,6 @@ class Pyramid:
         _check(self.ctx.lib.svo_pyramid_get_derivative_level(self.ctx._h, self._h, l, _ptr(out), MEM_HOST, C.byref(w),
                                                              C.byref(h)))
         return out
-
-    def close(self):
-        if self._h and self.ctx._h:
-            self.ctx.lib.svo_pyramid_destroy(self.ctx._h, self._h)
-        self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Context:
@@ -445,8 +493,7 @@ def orb_extract(self, img, n_features=500, fast_threshold=20):
     if not isinstance(img, np.ndarray):      # a device tensor (H, W[, C]) uint8: the outputs come back through device buffers
         import torch
 
-        h, w = img.shape[:2]
-        c = 1 if img.ndim == 2 else img.shape[2]
+        w, h, c = _image_shape(img)
         dev = img.device
         t_xy = torch.zeros((n_features, 2), dtype=torch.float32, device=dev)
         t_oct = torch.zeros(n_features, dtype=torch.int32, device=dev)
@@ -461,8 +508,7 @@ def orb_extract(self, img, n_features=500, fast_threshold=20):
         return (t_xy[:k].cpu().numpy(), t_oct[:k].cpu().numpy(), t_resp[:k].cpu().numpy(), t_d[:k].cpu().numpy(),
                 t_desc[:k].cpu().numpy().view(np.uint32))
     img = np.ascontiguousarray(img, np.uint8)
-    h, w = img.shape[:2]
-    c = 1 if img.ndim == 2 else img.shape[2]
+    w, h, c = _image_shape(img)
     xy, octv = np.zeros((n_features, 2), np.float32), np.zeros(n_features, np.int32)
     resp, d = np.zeros(n_features, np.float32), np.zeros((n_features, 2), np.float32)
     desc = np.zeros((n_features, 8), np.uint32)
@@ -482,12 +528,7 @@ ORB_SHAPE_OCTAVES3, ORB_SHAPE_CV = 0, 1
 
 
 def orb_params(**overrides) -> OrbParams:
-    p = OrbParams()
-    load().svo_orb_default_params(C.byref(p))
-    for k, v in overrides.items():
-        assert hasattr(p, k), k
-        setattr(p, k, v)
-    return p
+    return _make_params(OrbParams, "svo_orb_default_params", overrides)
 
 
 @_ctx_method
@@ -514,8 +555,7 @@ def orb_extract_batch_padded(self, images, out=None, **params):
         return (np.zeros(0, np.int32), np.zeros((0, nf, 2), np.float32), np.zeros((0, nf), np.int32), np.zeros((0, nf), np.float32),
                 np.zeros((0, nf, 2), np.float32), np.zeros((0, nf, 8), np.uint32))
     first = images[0]
-    h, w = first.shape[:2]
-    c = 1 if first.ndim == 2 else first.shape[2]
+    w, h, c = _image_shape(first)
     n = (C.c_int * nimg)()
     e = nimg * nf
     if not isinstance(first, np.ndarray):
@@ -580,12 +620,7 @@ SGBM_MODE_SGBM = 0
 
 
 def sgbm_params(**overrides) -> SgbmParams:
-    p = SgbmParams()
-    load().svo_sgbm_default_params(C.byref(p))
-    for k, v in overrides.items():
-        assert hasattr(p, k), k
-        setattr(p, k, v)
-    return p
+    return _make_params(SgbmParams, "svo_sgbm_default_params", overrides)
 
 
 def stereo_rectify_q(fx, fy, cx, cy, tx, w, h) -> np.ndarray:
@@ -594,10 +629,6 @@ def stereo_rectify_q(fx, fy, cx, cy, tx, w, h) -> np.ndarray:
     _check(load().svo_stereo_rectify_q(C.c_double(fx), C.c_double(fy), C.c_double(cx), C.c_double(cy), C.c_double(tx),
                                        int(w), int(h), _ptr(Q)))
     return Q.reshape(4, 4)
-
-
-def _is_device(a) -> bool:
-    return hasattr(a, "is_cuda") and bool(a.is_cuda)
 
 
 @_ctx_method
@@ -671,16 +702,11 @@ def sgbm_right_params(left: SgbmParams) -> SgbmParams:
 
 def wls_params(sgbm: SgbmParams | None = None, **overrides) -> WlsParams:
     """``svo_wls_default_params`` for a left matcher (default: the reference's), then the overrides."""
-    p = WlsParams()
-    load().svo_wls_default_params(C.byref(sgbm if sgbm is not None else sgbm_params()), C.byref(p))
-    for k, v in overrides.items():
-        assert hasattr(p, k), k
-        setattr(p, k, v)
-    return p
+    return _make_params(WlsParams, "svo_wls_default_params", overrides, C.byref(sgbm if sgbm is not None else sgbm_params()))
 
 
 def _wls_prm(sgbm: SgbmParams | None, wls) -> WlsParams:
-    return wls if isinstance(wls, WlsParams) else wls_params(sgbm, **(wls or {}))
+    return _as_params(WlsParams, lambda **overrides: wls_params(sgbm, **overrides), wls)
 
 
 @_ctx_method
@@ -783,21 +809,84 @@ class SiftParams(C.Structure):
 
 
 def sift_params(**overrides) -> SiftParams:
-    p = SiftParams()
-    load().svo_sift_default_params(C.byref(p))
-    for k, v in overrides.items():
-        assert hasattr(p, k), k
-        setattr(p, k, v)
-    return p
+    return _make_params(SiftParams, "svo_sift_default_params", overrides)
 
 
 def _sift_prm(params) -> SiftParams:
-    return params if isinstance(params, SiftParams) else sift_params(**(params or {}))
+    return _as_params(SiftParams, sift_params, params)
 
 
-def _image_shape(im):
-    h, w = im.shape[:2]
-    return w, h, (1 if im.ndim == 2 else im.shape[2])
+# ---- the batched detectors' shared call: svo_{sift,surf}_extract_batch, svo_fast_{detect,anms}_batch, svo_star_detect_batch ----
+def _column_layout(spec, e):
+    """Where the output columns of a batched detector lie on the device.  ``spec``: [(name, np.float32 or np.int32, trailing
+    width)] in the order of the entry point's arguments; ``e``: entries per column (images x capacity).  The float32 columns lie
+    back to back in one buffer and the int32 columns in another -> ({name: (dtype, byte offset in its buffer, width)}, bytes
+    of the float buffer, bytes of the int buffer).  The pointers handed to the library and the views of what came back are both
+    taken from this."""
+    cols, size = {}, {np.float32: 0, np.int32: 0}
+    for name, dtype, width in spec:
+        cols[name] = (dtype, size[dtype], width)
+        size[dtype] += 4 * e * width
+    return cols, size[np.float32], size[np.int32]
+
+
+def _batch_images(images):
+    """images of one batch, where the first one lives -> (the images made contiguous, their pointer array, device?)"""
+    dev = _is_device(images[0])
+    images = [im.contiguous() for im in images] if dev else [np.ascontiguousarray(im, np.uint8) for im in images]
+    return images, (C.c_void_p * max(len(images), 1))(*[_ptr(im).value for im in images]), dev
+
+
+def _raise_with_counts(self, rc, n, nimg, prefix=None):
+    """Raise the SvoError of ``rc`` with the per-image counts in ``needed`` (and what did fit in ``prefix``)."""
+    err = SvoError(rc, self.lib.svo_last_error().decode(errors="replace"))
+    err.needed = list(n[:nimg])
+    if prefix is not None:
+        err.prefix = prefix
+    raise err
+
+
+def _batch_call(self, fn, images, spec, cap, pre_args, post_args=(), accept=(SVO_OK,)):
+    """``fn(ctx, image pointers, nimg, w, h, c, *pre_args, a pointer per column of spec, *post_args, counts, mem)`` on host arrays
+    or device tensors.  Host: one zeroed array per column.  Device: one zeroed float32 buffer and, if ``spec`` has int32 columns,
+    one int32 buffer (``_column_layout``), one ``torch.cuda.synchronize`` before the call, then ``svo_ctx_sync`` and one copy down
+    per buffer.  -> ({name: host array [nimg, cap(, width)]}, counts [nimg], rc); an ``rc`` outside ``accept`` raises with the
+    counts before anything is waited for."""
+    nimg, e = len(images), len(images) * cap
+    w, h, c = _image_shape(images[0])
+    images, ptrs, dev = _batch_images(images)
+    n = (C.c_int * max(nimg, 1))()
+    cols, fbytes, ibytes = _column_layout(spec, e)
+    shape = lambda width: (nimg, cap) + ((width,) if width > 1 else ())
+    if dev:
+        import torch
+
+        bufs = {np.float32: torch.zeros(fbytes // 4, dtype=torch.float32, device=images[0].device)}
+        if ibytes:
+            bufs[np.int32] = torch.zeros(ibytes // 4, dtype=torch.int32, device=images[0].device)
+        torch.cuda.synchronize(images[0].device)
+        outs = [C.c_void_p(bufs[dtype].data_ptr() + off) for dtype, off, _ in cols.values()]
+    else:
+        host = {name: np.zeros(shape(width), dtype) for name, (dtype, _, width) in cols.items()}
+        outs = [_ptr(a) for a in host.values()]
+    rc = fn(self._h, ptrs, nimg, w, h, c, *pre_args, *outs, *post_args, n, _mem_of(dev))
+    if rc not in accept:
+        _raise_with_counts(self, rc, n, nimg)
+    if dev:
+        _check(self.lib.svo_ctx_sync(self._h))
+        flat = {dtype: b.cpu().numpy().view(np.uint8) for dtype, b in bufs.items()}
+        host = {name: flat[dtype][off:off + 4 * e * width].view(dtype).reshape(shape(width))
+                for name, (dtype, off, width) in cols.items()}
+    return host, list(n[:nimg]), rc
+
+
+def _cut(columns, counts):
+    """padded [nimg, cap, ...] columns (None stays None) -> per image, a tuple of copies of its first ``counts[i]`` rows"""
+    return [tuple(None if a is None else a[i, :k].copy() for a in columns) for i, k in enumerate(counts)]
+
+
+_SIFT_COLUMNS = [("xy", np.float32, 2), ("size", np.float32, 1), ("angle", np.float32, 1), ("response", np.float32, 1),
+                 ("octave", np.int32, 1), ("desc", np.float32, 128)]
 
 
 @_ctx_method
@@ -807,40 +896,10 @@ def sift_extract(self, images, params=None, cap=20000, descriptors=True):
     or None), host arrays in the recipe's order.  More than ``cap`` key points in an image: SvoError(SVO_ERR_CAPACITY) whose
     ``needed`` lists the counts."""
     prm = _sift_prm(params)
-    nimg = len(images)
-    w, h, c = _image_shape(images[0])
-    n = (C.c_int * max(nimg, 1))()
-    e = nimg * cap
-    dev = _is_device(images[0])
-    if dev:
-        import torch
-
-        images = [im.contiguous() for im in images]
-        fb = torch.zeros(e * (5 + (128 if descriptors else 0)), dtype=torch.float32, device=images[0].device)
-        ob = torch.zeros(e, dtype=torch.int32, device=images[0].device)
-        torch.cuda.synchronize(images[0].device)
-        base = fb.data_ptr()
-        args = [C.c_void_p(base + 4 * k * e) for k in (0, 2, 3, 4)] + [_ptr(ob), C.c_void_p(base + 20 * e if descriptors else 0)]
-    else:
-        images = [np.ascontiguousarray(im, np.uint8) for im in images]
-        xy, size, angle = np.zeros((nimg, cap, 2), np.float32), np.zeros((nimg, cap), np.float32), np.zeros((nimg, cap), np.float32)
-        resp, octv = np.zeros((nimg, cap), np.float32), np.zeros((nimg, cap), np.int32)
-        desc = np.zeros((nimg, cap, 128), np.float32) if descriptors else None
-        args = [_ptr(xy), _ptr(size), _ptr(angle), _ptr(resp), _ptr(octv), _ptr(desc)]
-    ptrs = (C.c_void_p * max(nimg, 1))(*[_ptr(im).value for im in images])
-    rc = self.lib.svo_sift_extract_batch(self._h, ptrs, nimg, w, h, c, C.byref(prm), cap, *args, n, MEM_DEVICE if dev else MEM_HOST)
-    if rc != SVO_OK:
-        err = SvoError(rc, self.lib.svo_last_error().decode(errors="replace"))
-        err.needed = list(n[:nimg])
-        raise err
-    if dev:
-        _check(self.lib.svo_ctx_sync(self._h))
-        hb, octv = fb.cpu().numpy(), ob.cpu().numpy().reshape(nimg, cap)
-        xy, size = hb[:2 * e].reshape(nimg, cap, 2), hb[2 * e:3 * e].reshape(nimg, cap)
-        angle, resp = hb[3 * e:4 * e].reshape(nimg, cap), hb[4 * e:5 * e].reshape(nimg, cap)
-        desc = hb[5 * e:].reshape(nimg, cap, 128) if descriptors else None
-    return [(xy[i, :n[i]].copy(), size[i, :n[i]].copy(), angle[i, :n[i]].copy(), resp[i, :n[i]].copy(), octv[i, :n[i]].copy(),
-             desc[i, :n[i]].copy() if descriptors else None) for i in range(nimg)]
+    # without descriptors the column is not allocated and the library gets a null pointer in its place
+    spec, no_desc = (_SIFT_COLUMNS, ()) if descriptors else (_SIFT_COLUMNS[:-1], (None,))
+    col, n, _ = _batch_call(self, self.lib.svo_sift_extract_batch, images, spec, cap, (C.byref(prm), cap), no_desc)
+    return _cut([*col.values(), *no_desc], n)
 
 
 @_ctx_method
@@ -884,52 +943,33 @@ class FastParams(C.Structure):
 
 
 def fast_params(**overrides) -> FastParams:
-    p = FastParams()
-    load().svo_fast_default_params(C.byref(p))
-    for k, v in overrides.items():
-        assert hasattr(p, k), k
-        setattr(p, k, v)
-    return p
+    return _make_params(FastParams, "svo_fast_default_params", overrides)
+
+
+_FAST_COLUMNS = [("xy", np.float32, 2), ("response", np.float32, 1)]
 
 
 def _fast_call(self, images, prm, cap, keep, score):
     """Both FAST entry points: per image (xy [n, 2], response [n][, score [h, w]]) as host arrays."""
-    nimg = len(images)
     w, h, c = _image_shape(images[0])
     if cap is None:
         cap = max((w - 6) * (h - 6), 1)          # no image has more key points than interior pixels
-    n = (C.c_int * max(nimg, 1))()
-    e = nimg * cap
-    dev = _is_device(images[0])
-    if dev:
-        import torch
+    if keep is not None:
+        col, n, _ = _batch_call(self, self.lib.svo_fast_anms_batch, images, _FAST_COLUMNS, cap, (C.byref(prm), keep, cap))
+        return _cut(col.values(), n)
+    sb = None
+    if score:                                    # a [nimg, h, w] uint8 plane of its own, where the images live
+        if _is_device(images[0]):
+            import torch
 
-        images = [im.contiguous() for im in images]
-        fb = torch.zeros(e * 3, dtype=torch.float32, device=images[0].device)
-        sb = torch.zeros((nimg, h, w), dtype=torch.uint8, device=images[0].device) if score else None
-        torch.cuda.synchronize(images[0].device)
-        args = [C.c_void_p(fb.data_ptr()), C.c_void_p(fb.data_ptr() + 8 * e)]
-    else:
-        images = [np.ascontiguousarray(im, np.uint8) for im in images]
-        xy, resp = np.zeros((nimg, cap, 2), np.float32), np.zeros((nimg, cap), np.float32)
-        sb = np.zeros((nimg, h, w), np.uint8) if score else None
-        args = [_ptr(xy), _ptr(resp)]
-    ptrs = (C.c_void_p * max(nimg, 1))(*[_ptr(im).value for im in images])
-    mem = MEM_DEVICE if dev else MEM_HOST
-    if keep is None:
-        rc = self.lib.svo_fast_detect_batch(self._h, ptrs, nimg, w, h, c, C.byref(prm), cap, *args, _ptr(sb), n, mem)
-    else:
-        rc = self.lib.svo_fast_anms_batch(self._h, ptrs, nimg, w, h, c, C.byref(prm), keep, cap, *args, n, mem)
-    if rc != SVO_OK:
-        err = SvoError(rc, self.lib.svo_last_error().decode(errors="replace"))
-        err.needed = list(n[:nimg])
-        raise err
-    if dev:
-        _check(self.lib.svo_ctx_sync(self._h))
-        hb = fb.cpu().numpy()
-        xy, resp = hb[:2 * e].reshape(nimg, cap, 2), hb[2 * e:].reshape(nimg, cap)
-        sb = sb.cpu().numpy() if score else None
-    return [(xy[i, :n[i]].copy(), resp[i, :n[i]].copy()) + ((sb[i].copy(),) if score else ()) for i in range(nimg)]
+            sb = torch.zeros((len(images), h, w), dtype=torch.uint8, device=images[0].device)
+        else:
+            sb = np.zeros((len(images), h, w), np.uint8)
+    col, n, _ = _batch_call(self, self.lib.svo_fast_detect_batch, images, _FAST_COLUMNS, cap, (C.byref(prm), cap), (_ptr(sb),))
+    if not score:
+        return _cut(col.values(), n)
+    sb = sb.cpu().numpy() if _is_device(sb) else sb
+    return [kp + (sb[i].copy(),) for i, kp in enumerate(_cut(col.values(), n))]
 
 
 @_ctx_method
@@ -956,16 +996,11 @@ class StarParams(C.Structure):
 
 
 def star_params(**overrides) -> StarParams:
-    p = StarParams()
-    load().svo_star_default_params(C.byref(p))
-    for k, v in overrides.items():
-        assert hasattr(p, k), k
-        setattr(p, k, v)
-    return p
+    return _make_params(StarParams, "svo_star_default_params", overrides)
 
 
 def _star_prm(params) -> StarParams:
-    return params if isinstance(params, StarParams) else star_params(**(params or {}))
+    return _as_params(StarParams, star_params, params)
 
 
 def star_layout(w, h, max_size=45):
@@ -988,6 +1023,9 @@ def _star_images(images, mem):
     return images, dev
 
 
+_STAR_COLUMNS = [("xy", np.float32, 2), ("size", np.float32, 1), ("response", np.float32, 1)]
+
+
 @_ctx_method
 def star_detect(self, images, prm=None, cap=None, mem=None):
     """``svo_star_detect_batch``: the Star (CenSurE) detector on 1 ... 16 images of one size (host arrays or device tensors; ``mem``
@@ -995,33 +1033,12 @@ def star_detect(self, images, prm=None, cap=None, mem=None):
     maximum before its minimum, tiles in row-major order.  More than ``cap`` key points in an image:
     SvoError(SVO_ERR_CAPACITY) whose ``needed`` lists the counts."""
     prm = _star_prm(prm)
-    nimg = len(images)
     w, h, c = _image_shape(images[0])
     if cap is None:
         cap = max(2 * w * h, 1)                  # a pixel is at most a maximum and a minimum
-    n = (C.c_int * max(nimg, 1))()
-    e = nimg * cap
-    images, dev = _star_images(images, mem)
-    if dev:
-        import torch
-
-        fb = torch.zeros(e * 4, dtype=torch.float32, device=images[0].device)
-        torch.cuda.synchronize(images[0].device)
-        args = [C.c_void_p(fb.data_ptr() + 4 * k * e) for k in (0, 2, 3)]
-    else:
-        xy, size, resp = np.zeros((nimg, cap, 2), np.float32), np.zeros((nimg, cap), np.float32), np.zeros((nimg, cap), np.float32)
-        args = [_ptr(xy), _ptr(size), _ptr(resp)]
-    ptrs = (C.c_void_p * max(nimg, 1))(*[_ptr(im).value for im in images])
-    rc = self.lib.svo_star_detect_batch(self._h, ptrs, nimg, w, h, c, C.byref(prm), cap, *args, n, MEM_DEVICE if dev else MEM_HOST)
-    if rc != SVO_OK:
-        err = SvoError(rc, self.lib.svo_last_error().decode(errors="replace"))
-        err.needed = list(n[:nimg])
-        raise err
-    if dev:
-        _check(self.lib.svo_ctx_sync(self._h))
-        hb = fb.cpu().numpy()
-        xy, size, resp = hb[:2 * e].reshape(nimg, cap, 2), hb[2 * e:3 * e].reshape(nimg, cap), hb[3 * e:].reshape(nimg, cap)
-    return [(xy[i, :n[i]].copy(), size[i, :n[i]].copy(), resp[i, :n[i]].copy()) for i in range(nimg)]
+    images, _ = _star_images(images, mem)
+    col, n, _ = _batch_call(self, self.lib.svo_star_detect_batch, images, _STAR_COLUMNS, cap, (C.byref(prm), cap))
+    return _cut(col.values(), n)
 
 
 @_ctx_method
@@ -1040,7 +1057,7 @@ def star_responses(self, image, prm=None, mem=None):
     else:
         resp, size = np.zeros((h, w), np.float32), np.zeros((h, w), np.int16)
     _check(self.lib.svo_star_responses(self._h, _ptr(img), w, h, c, C.byref(prm), _ptr(resp), _ptr(size), C.byref(border),
-                                       MEM_DEVICE if dev else MEM_HOST))
+                                       _mem_of(dev)))
     if dev:
         _check(self.lib.svo_ctx_sync(self._h))
         resp, size = resp.cpu().numpy(), size.cpu().numpy()
@@ -1078,12 +1095,11 @@ def brief_describe(self, images, xy_list, bytes=32):
     n_out = (C.c_int * max(nimg, 1))()
     cap = max([1] + [int(len(xy)) for xy in xy_list])
     nb = int(bytes)
-    dev = _is_device(images[0])
+    images, ptrs, dev = _batch_images(images)
     if dev:
         import torch
 
         device = images[0].device
-        images = [im.contiguous() for im in images]
         xy = torch.zeros((nimg, cap, 2), dtype=torch.float32, device=device)
         for i, p in enumerate(xy_list):
             if len(p):
@@ -1092,19 +1108,17 @@ def brief_describe(self, images, xy_list, bytes=32):
         desc = torch.zeros((nimg, cap, max(nb, 1)), dtype=torch.uint8, device=device)
         torch.cuda.synchronize(device)
     else:
-        images = [np.ascontiguousarray(im, np.uint8) for im in images]
         xy = np.zeros((nimg, cap, 2), np.float32)
         for i, p in enumerate(xy_list):
             if len(p):
                 xy[i, :len(p)] = np.asarray(p, np.float32).reshape(-1, 2)
         kept, desc = np.zeros((nimg, cap), np.int32), np.zeros((nimg, cap, max(nb, 1)), np.uint8)
-    ptrs = (C.c_void_p * max(nimg, 1))(*[_ptr(im).value for im in images])
     _check(self.lib.svo_brief_describe_batch(self._h, ptrs, nimg, w, h, c, nb, _ptr(xy), n_in, cap, _ptr(kept), _ptr(desc), n_out,
-                                             MEM_DEVICE if dev else MEM_HOST))
+                                             _mem_of(dev)))
     if dev:
         _check(self.lib.svo_ctx_sync(self._h))
         kept, desc = kept.cpu().numpy(), desc.cpu().numpy()
-    return [(desc[i, :n_out[i]].copy(), kept[i, :n_out[i]].copy()) for i in range(nimg)]
+    return _cut((desc, kept), n_out[:nimg])
 
 
 @_ctx_method
@@ -1124,16 +1138,15 @@ class SurfParams(C.Structure):
 
 
 def surf_params(**overrides) -> SurfParams:
-    p = SurfParams()
-    load().svo_surf_default_params(C.byref(p))
-    for k, v in overrides.items():
-        assert hasattr(p, k), k
-        setattr(p, k, v)
-    return p
+    return _make_params(SurfParams, "svo_surf_default_params", overrides)
 
 
 def _surf_prm(params) -> SurfParams:
-    return params if isinstance(params, SurfParams) else surf_params(**(params or {}))
+    return _as_params(SurfParams, surf_params, params)
+
+
+_SURF_COLUMNS = [("xy", np.float32, 2), ("size", np.float32, 1), ("angle", np.float32, 1), ("response", np.float32, 1),
+                 ("octave", np.int32, 1), ("laplacian", np.int32, 1), ("desc", np.float32, 64)]
 
 
 @_ctx_method
@@ -1143,47 +1156,13 @@ def surf_extract(self, images, params=None, cap=20000, descriptors=True):
     None), host arrays in the recipe's order.  More than ``cap`` key points in an image: SvoError(SVO_ERR_CAPACITY) whose
     ``needed`` lists the counts and whose ``prefix`` holds the first ``cap`` key points of every image."""
     prm = _surf_prm(params)
-    nimg = len(images)
-    w, h, c = _image_shape(images[0])
-    n = (C.c_int * max(nimg, 1))()
-    e = nimg * cap
-    dev = _is_device(images[0])
-    if dev:
-        import torch
-
-        images = [im.contiguous() for im in images]
-        fb = torch.zeros(e * (5 + (64 if descriptors else 0)), dtype=torch.float32, device=images[0].device)
-        ob = torch.zeros(2 * e, dtype=torch.int32, device=images[0].device)
-        torch.cuda.synchronize(images[0].device)
-        base, ibase = fb.data_ptr(), ob.data_ptr()
-        args = [C.c_void_p(base + 4 * k * e) for k in (0, 2, 3, 4)] + [C.c_void_p(ibase), C.c_void_p(ibase + 4 * e),
-                                                                    C.c_void_p(base + 20 * e if descriptors else 0)]
-    else:
-        images = [np.ascontiguousarray(im, np.uint8) for im in images]
-        xy, size, angle = np.zeros((nimg, cap, 2), np.float32), np.zeros((nimg, cap), np.float32), np.zeros((nimg, cap), np.float32)
-        resp, octv, lap = np.zeros((nimg, cap), np.float32), np.zeros((nimg, cap), np.int32), np.zeros((nimg, cap), np.int32)
-        desc = np.zeros((nimg, cap, 64), np.float32) if descriptors else None
-        args = [_ptr(xy), _ptr(size), _ptr(angle), _ptr(resp), _ptr(octv), _ptr(lap), _ptr(desc)]
-    ptrs = (C.c_void_p * max(nimg, 1))(*[_ptr(im).value for im in images])
-    rc = self.lib.svo_surf_extract_batch(self._h, ptrs, nimg, w, h, c, C.byref(prm), cap, *args, n, MEM_DEVICE if dev else MEM_HOST)
-    if rc not in (SVO_OK, SVO_ERR_CAPACITY):
-        raise SvoError(rc, self.lib.svo_last_error().decode(errors="replace"))
-    msg = self.lib.svo_last_error().decode(errors="replace") if rc else ""
-    if dev:
-        _check(self.lib.svo_ctx_sync(self._h))
-        hb, ib = fb.cpu().numpy(), ob.cpu().numpy()
-        octv, lap = ib[:e].reshape(nimg, cap), ib[e:].reshape(nimg, cap)
-        xy, size = hb[:2 * e].reshape(nimg, cap, 2), hb[2 * e:3 * e].reshape(nimg, cap)
-        angle, resp = hb[3 * e:4 * e].reshape(nimg, cap), hb[4 * e:5 * e].reshape(nimg, cap)
-        desc = hb[5 * e:].reshape(nimg, cap, 64) if descriptors else None
-    m = [min(n[i], cap) for i in range(nimg)]
-    out = [(xy[i, :m[i]].copy(), size[i, :m[i]].copy(), angle[i, :m[i]].copy(), resp[i, :m[i]].copy(), octv[i, :m[i]].copy(),
-            lap[i, :m[i]].copy(), desc[i, :m[i]].copy() if descriptors else None) for i in range(nimg)]
+    # without descriptors the column is not allocated and the library gets a null pointer in its place
+    spec, no_desc = (_SURF_COLUMNS, ()) if descriptors else (_SURF_COLUMNS[:-1], (None,))
+    col, n, rc = _batch_call(self, self.lib.svo_surf_extract_batch, images, spec, cap, (C.byref(prm), cap), no_desc,
+                             accept=(SVO_OK, SVO_ERR_CAPACITY))
+    out = _cut([*col.values(), *no_desc], [min(k, cap) for k in n])      # over capacity: the first ``cap`` key points were written
     if rc != SVO_OK:
-        err = SvoError(rc, msg)
-        err.needed = list(n[:nimg])
-        err.prefix = out
-        raise err
+        _raise_with_counts(self, rc, n, len(images), prefix=out)
     return out
 
 
@@ -1367,8 +1346,9 @@ def undistort_points_host(xy, K, D, R=None, P=None):
     return out
 
 
-class RectifyMap:
+class RectifyMap(_Handle):
     """A fixed-point rectify map on the device (``svo_rectify_map``): ``Context.rectify_map`` / ``rectify_map_from_float``."""
+    _destroy, _destroy_takes_ctx = "svo_rectify_map_destroy", True
 
     def __init__(self, ctx, handle, size, src_size):
         self.ctx, self._h, self.size, self.src_size = ctx, handle, tuple(size), tuple(src_size)
@@ -1380,17 +1360,6 @@ class RectifyMap:
         xy, frac = np.zeros((h, w, 2), np.int16), np.zeros((h, w), np.uint16)
         _check(self.ctx.lib.svo_rectify_map_get(self.ctx._h, self._h, _ptr(xy), _ptr(frac), MEM_HOST))
         return xy, frac
-
-    def close(self):
-        if self._h and self.ctx._h:
-            self.ctx.lib.svo_rectify_map_destroy(self.ctx._h, self._h)
-        self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 @_ctx_method
@@ -1424,7 +1393,7 @@ def rectify_map_from_float(self, mapx, mapy, src_size):
     hh, ww = mx.shape
     h = C.c_void_p()
     _check(self.lib.svo_rectify_map_from_float(self._h, _ptr(mx), _ptr(my), int(ww), int(hh), int(src_size[0]), int(src_size[1]),
-                                               MEM_DEVICE if dev else MEM_HOST, C.byref(h)))
+                                               _mem_of(dev), C.byref(h)))
     return RectifyMap(self, h, (ww, hh), src_size)
 
 
@@ -1472,7 +1441,7 @@ def remap(self, map, images, border_value=0, mem=None):
         torch.cuda.synchronize(a.device)
     else:
         out = np.zeros(oshape, np.uint8)
-    _check(self.lib.svo_remap_batch(self._h, map._h, _ptr(a), n, c, int(border_value), _ptr(out), MEM_DEVICE if dev else MEM_HOST))
+    _check(self.lib.svo_remap_batch(self._h, map._h, _ptr(a), n, c, int(border_value), _ptr(out), _mem_of(dev)))
     return out
 
 
@@ -1493,7 +1462,7 @@ def rectify_pairs(self, map_left, map_right, lefts, rights, border_value=0, mem=
     else:
         ol, orr = np.zeros(oshape, np.uint8), np.zeros(oshape, np.uint8)
     _check(self.lib.svo_rectify_pairs(self._h, map_left._h, map_right._h, _ptr(a), _ptr(b), n, c, int(border_value), _ptr(ol),
-                                      _ptr(orr), MEM_DEVICE if dev else MEM_HOST))
+                                      _ptr(orr), _mem_of(dev)))
     return ol, orr
 
 
@@ -1515,7 +1484,7 @@ def undistort_points(self, xy, K, D, R=None, P=None, mem=None):
         pts = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
         out = np.zeros_like(pts)
     _check(self.lib.svo_undistort_points(self._h, _ptr(pts), int(pts.shape[0]), _ptr(K), _ptr(D), nD, _ptr(_opt_matrix(R, (3, 3))),
-                                         _ptr(_opt_matrix(P, (3, 4))), _ptr(out), MEM_DEVICE if dev else MEM_HOST))
+                                         _ptr(_opt_matrix(P, (3, 4))), _ptr(out), _mem_of(dev)))
     return out
 
 
@@ -1771,7 +1740,7 @@ def match_cross(self, query, train, norm=MATCH_L2_U8, mode=CROSS_MUTUAL, q_offse
     else:
         idx, dist = np.full(nq, -1, np.int32), np.full(nq, np.inf, np.float32)
     _check(self.lib.svo_match_cross(self._h, int(norm), _ptr(q), _ptr(t), dim, _ptr(qo), _ptr(to), nprob, int(mode), _ptr(idx),
-                                    _ptr(dist), MEM_DEVICE if dev else MEM_HOST))
+                                    _ptr(dist), _mem_of(dev)))
     if dev:
         _check(self.lib.svo_ctx_sync(self._h))
     return idx, dist
@@ -1801,7 +1770,7 @@ def radius_match(self, query, train, max_distance, norm=MATCH_L2_U8, capacity=No
         off = np.zeros(n_off, np.int32)
         idx, dist = np.full(max(capacity, 1), -1, np.int32), np.full(max(capacity, 1), np.inf, np.float32)
     rc = self.lib.svo_radius_match(self._h, int(norm), _ptr(q), _ptr(t), dim, _ptr(qo), _ptr(to), nprob, C.c_float(max_distance),
-                                   _ptr(off), _ptr(idx), _ptr(dist), capacity, C.byref(total), MEM_DEVICE if dev else MEM_HOST)
+                                   _ptr(off), _ptr(idx), _ptr(dist), capacity, C.byref(total), _mem_of(dev))
     if rc == SVO_ERR_CAPACITY and total.value > 0:
         err = SvoError(rc, load().svo_last_error().decode(errors="replace"))
         err.row_offsets, err.total = off, total.value
@@ -1844,7 +1813,7 @@ def knn_match_gated(self, query, train, k=2, norm=MATCH_L2_U8, mask=None, gate=N
         idx, dist = np.full((nq, k), -1, np.int32), np.full((nq, k), np.inf, np.float32)
     _check(self.lib.svo_knn_match_gated(self._h, int(norm), _ptr(q), _ptr(t), dim, _ptr(qo), _ptr(to), nprob, int(k), _ptr(m),
                                         _ptr(xq), _ptr(xt), C.byref(g) if g is not None else None, _ptr(idx), _ptr(dist),
-                                        MEM_DEVICE if dev else MEM_HOST))
+                                        _mem_of(dev)))
     if dev:
         _check(self.lib.svo_ctx_sync(self._h))
     return idx, dist
@@ -1913,13 +1882,8 @@ class ba_window_params(C.Structure):
 
     @classmethod
     def default(cls, **kw):
-        p = cls()
-        load().svo_ba_window_default_params(C.byref(p))
-        for k, v in kw.items():
-            if k not in dict(cls._fields_):
-                raise TypeError(f"svo_ba_window_params has no field {k}")
-            setattr(p, k, v)
-        return p
+        _known_fields(cls, "svo_ba_window_params", kw)
+        return _make_params(cls, "svo_ba_window_default_params", kw)
 
 
 @_ctx_method
@@ -1928,10 +1892,7 @@ def ba_window(self, poses, fixed, pts3d, obs_start, obs_pose, obs_uvr, params=No
     per pose, world -> camera; ``fixed``: one byte per pose; the observations CSR by point.  ``pts3d``, ``obs_start``, ``obs_pose``
     and ``obs_uvr`` follow ``mem`` (device: tensors or addresses, with ``obs_start`` readable for its sizes only through the
     library); ``params``: a ``ba_window_params`` or a dict of its fields."""
-    if params is None:
-        params = ba_window_params.default()
-    elif isinstance(params, dict):
-        params = ba_window_params.default(**params)
+    params = _as_params(ba_window_params, ba_window_params.default, params)
     P = np.array(poses, np.float64).reshape(-1, 12).copy()
     fx = np.ascontiguousarray(fixed, np.uint8).reshape(-1)
     assert fx.shape[0] == P.shape[0]
@@ -1959,18 +1920,16 @@ class VoParams(C.Structure):
                 ("pnp_retry_below", C.c_int), ("pnp_lost_below", C.c_int)]
 
 
-class VisualOdometry:
+class VisualOdometry(_Handle):
     """The front-end frame loop on one GPU (``svo_vo``), mirroring visualSLAM::initSequence
     (src/VisualSLAM.cpp:11-169).  Images: numpy (H, W, C) uint8 or device tensors."""
+    _destroy = "svo_vo_destroy"
 
     def __init__(self, ctx: Context, w, h, c, grid_step=30, anms_keep=0, keyframe_min_inliers=200, seed=0,
                  K4=None, baseline=None, policy=0, pnp_retry_below=None, pnp_lost_below=None):
         self.ctx = ctx
-        self.prm = VoParams()
-        ctx.lib.svo_vo_default_params(C.byref(self.prm))
-        self.prm.grid_step, self.prm.anms_keep = grid_step, anms_keep
-        self.prm.keyframe_min_inliers, self.prm.seed = keyframe_min_inliers, seed
-        self.prm.policy = policy
+        self.prm = _make_params(VoParams, "svo_vo_default_params", dict(
+            grid_step=grid_step, anms_keep=anms_keep, keyframe_min_inliers=keyframe_min_inliers, seed=seed, policy=policy))
         if pnp_retry_below is not None:
             self.prm.pnp_retry_below = pnp_retry_below
         if pnp_lost_below is not None:
@@ -2074,17 +2033,6 @@ class VisualOdometry:
         n = C.c_int()
         _check(self.ctx.lib.svo_vo_get_reference(self._h, _ptr(a), _ptr(b), cap, C.byref(n), MEM_HOST))
         return a[:n.value], b[:n.value]
-
-    def close(self):
-        if self._h and self.ctx._h:
-            self.ctx.lib.svo_vo_destroy(self._h)
-        self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---- data formats either side of the path (host code in libsvo_hip.so, no GPU needed) -----------
@@ -2264,16 +2212,13 @@ LC_STATUS = ("LOOP_DETECTED", "CLOSE_MATCHES_ONLY", "NO_DB_RESULTS", "LOW_NSS_FA
              "NO_TEMPORAL_CONSISTENCY", "NO_GEOMETRICAL_CONSISTENCY")
 
 
-class LoopDetector:
+class LoopDetector(_Handle):
     """checkLoopDetectorStatus's detector (src/optimizationStuff.cpp:49-64; ``svo_lc``)."""
+    _destroy = "svo_lc_destroy"     # waits for the queued work
 
     def __init__(self, ctx: "Context", w: int, h: int, c: int, **overrides):
         self.ctx = ctx
-        self.prm = LcParams()
-        ctx.lib.svo_lc_default_params(C.byref(self.prm))
-        for k, v in overrides.items():
-            assert hasattr(self.prm, k), k
-            setattr(self.prm, k, v)
+        self.prm = _make_params(LcParams, "svo_lc_default_params", overrides)
         self._h = C.c_void_p()
         # the images of submitted frames, oldest first: (entry of the submission's last frame, the images) -- the queued work
         # reads them, so each stays referenced until collect / collect_batch / collect_ex has passed that entry
@@ -2383,21 +2328,14 @@ class LoopDetector:
         return self.ctx.lib.svo_lc_size(self._h)
 
     def close(self):
-        if self._h and self.ctx._h:
-            self.ctx.lib.svo_lc_destroy(self._h)     # waits for the queued work
-        self._h = C.c_void_p()
+        super().close()
         self._keep_images.clear()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
-
-class Vocabulary:
+class Vocabulary(_Handle):
     """DBoW2's OrbVocabulary on the GPU (``svo_voc``): ``train`` (src/bagOfWordsDetector.cpp:46-56) or ``from_arrays``
     (a vocabulary read from a file, ros_stereo_slam_amd/vocabulary.py)."""
+    _destroy = "svo_voc_destroy"
 
     def __init__(self, ctx: "Context", handle):
         self.ctx, self._h = ctx, handle
@@ -2449,21 +2387,11 @@ class Vocabulary:
         _check(self.ctx.lib.svo_voc_bow(self._h, _ptr(desc), n, int(levelsup), _ptr(w), _ptr(v), C.byref(m), _ptr(node)))
         return w[:m.value].copy(), v[:m.value].copy(), node[:n].copy()
 
-    def close(self):
-        if self._h and self.ctx._h:
-            self.ctx.lib.svo_voc_destroy(self._h)
-        self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class KeyframeMap:
+class KeyframeMap(_Handle):
     """keyFrameHistory / mapHistory in HBM and visualSLAM::updateOdometry on it
     (src/optimizationStuff.cpp:17-47; ``svo_map``)."""
+    _destroy = "svo_map_destroy"
 
     def __init__(self, ctx: "Context"):
         self.ctx = ctx
@@ -2511,17 +2439,6 @@ class KeyframeMap:
                                                C.byref(npts), C.byref(nkf), MEM_HOST))
         return xyz[:npts.value], counts[:nkf.value]
 
-    def close(self):
-        if self._h and self.ctx._h:
-            self.ctx.lib.svo_map_destroy(self._h)
-        self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 INFO_TRIU = np.triu_indices(6)
 
@@ -2549,13 +2466,8 @@ class ClosureParams(C.Structure):
 
 
 def closure_params(**overrides) -> ClosureParams:
-    p = ClosureParams()
-    load().svo_closure_default_params(C.byref(p))
-    for k, v in overrides.items():
-        if not hasattr(p, k):
-            raise TypeError(f"svo_closure_params has no field {k}")
-        setattr(p, k, v)
-    return p
+    _known_fields(ClosureParams, "svo_closure_params", overrides)
+    return _make_params(ClosureParams, "svo_closure_default_params", overrides)
 
 
 @_ctx_method
@@ -2588,9 +2500,10 @@ def measure_closure(self, newest, matched, xy, xyz, K4, size=None, **params):
     return rc, (meas if rc == SVO_OK else None), ntrk.value, ninl.value
 
 
-class PoseGraph:
+class PoseGraph(_Handle):
     """SE3 pose graph on the GPU (``svo_posegraph``), mirroring globalPoseGraph
     (include/poseGraph.h:36-179).  Poses: tx ty tz qx qy qz qw."""
+    _destroy = "svo_pg_destroy"
 
     def __init__(self, ctx: Context):
         self.ctx = ctx
@@ -2701,17 +2614,6 @@ class PoseGraph:
     def write_g2o(self, path):
         _check(self.ctx.lib.svo_pg_write_g2o(self._h, os.fspath(path).encode()))
 
-    def close(self):
-        if self._h and self.ctx._h:
-            self.ctx.lib.svo_pg_destroy(self._h)
-        self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # ---- point-to-plane ICP between clouds and the information of the edge it yields (csrc/cloud.hip) ------------------
 class IcpParams(C.Structure):
@@ -2719,13 +2621,8 @@ class IcpParams(C.Structure):
 
 
 def icp_params(**overrides) -> IcpParams:
-    p = IcpParams()
-    load().svo_icp_default_params(C.byref(p))
-    for k, v in overrides.items():
-        if not hasattr(p, k):
-            raise TypeError(f"svo_icp_params has no field {k}")
-        setattr(p, k, v)
-    return p
+    _known_fields(IcpParams, "svo_icp_params", overrides)
+    return _make_params(IcpParams, "svo_icp_default_params", overrides)
 
 
 def _cloud_arg(xyz):
@@ -2745,8 +2642,9 @@ def _T16(T):
     return np.ascontiguousarray(np.eye(4) if T is None else T, np.float64).reshape(16)
 
 
-class Cloud:
+class Cloud(_Handle):
     """A resident target cloud with its search index (``svo_cloud``): n x 3 float32 points, host array or device tensor."""
+    _destroy = "svo_cloud_destroy"
 
     def __init__(self, ctx: Context, xyz):
         self.ctx = ctx
@@ -2781,17 +2679,6 @@ class Cloud:
     def estimate_normals(self, knn: int = 30):
         _check(self.ctx.lib.svo_cloud_estimate_normals(self._h, int(knn)))
         return self
-
-    def close(self):
-        if self._h and self.ctx._h:
-            self.ctx.lib.svo_cloud_destroy(self._h)
-        self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 @_ctx_method
