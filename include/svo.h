@@ -438,6 +438,42 @@ int svo_sgbm_wls_compute(svo_ctx *ctx, const svo_sgbm_params *sgbm, const svo_wl
                          const uint8_t *right, int w, int h, int c, int n_pairs, int16_t *filtered, int16_t *disp_left,
                          int16_t *disp_right, float *confidence, int mem);
 
+/* ---- block matching: cv::StereoBM, the dense matcher for frame rate ----
+ * StereoBM::create(0, 21) + compute(left, right, disp): XSOBEL pre-filter, a block_size x block_size sum of absolute
+ * differences per pixel and disparity, texture and uniqueness tests, sub-pixel winner, then validateDisparity
+ * (disp12_max_diff >= 0) and filterSpeckles (speckle_window_size > 0, speckle_range >= 0); no median.  The output has
+ * svo_sgbm_compute's format, so svo_stereo_reproject and svo_wls_filter take it as it is.  The recipe, point by point
+ * (B1..B11, each marked recalled or ours): tests/bm_numpy.py; all integer, and the results are
+ * bit-identical to that restatement.  Not built: PREFILTER_NORMALIZED_RESPONSE, roi1 / roi2, CV_32F output.             */
+enum { SVO_BM_PREFILTER_NORMALIZED_RESPONSE = 0, SVO_BM_PREFILTER_XSOBEL = 1 };
+typedef struct svo_bm_params {
+    int pre_filter_type, pre_filter_size, pre_filter_cap, block_size, min_disparity, num_disparities,
+        texture_threshold, uniqueness_ratio, speckle_window_size, speckle_range, disp12_max_diff;
+} svo_bm_params;
+/* StereoBM::create(0, 21)'s values (B1): XSOBEL, 9, 31, 21, 0, 64, 10, 15, 0, 0, -1                                     */
+void svo_bm_default_params(svo_bm_params *p);
+/* Arguments and output as svo_sgbm_compute's (invalid = (min_disparity - 1) * 16).  SVO_ERR_ARG, with the output
+ * untouched: n_pairs outside 1..16, c not 1 or 3, num_disparities not a positive multiple of 16 up to 256, an even
+ * block_size or one outside 5..255 or above min(w, h), pre_filter_cap outside 1..63, an even pre_filter_size or one
+ * outside 5..255 (carried and checked; XSOBEL does not use it), a pre-filter type other than XSOBEL, a negative
+ * texture_threshold or uniqueness_ratio, |min_disparity| above 2^20.  SVO_ERR_CAPACITY: block_size above 31, w > 2048,
+ * 2^30 or more pixel x disparity cells (n_pairs x h x w x num_disparities) per call.  A disparity range that leaves no
+ * band (B3) is no error: every pixel is invalid.                                                                       */
+int svo_bm_compute(svo_ctx *ctx, const svo_bm_params *p, const uint8_t *left, const uint8_t *right,
+                   int w, int h, int c, int n_pairs, int16_t *disp, int mem);
+/* createRightMatcher(matcher), BM case (B11); run it as svo_bm_compute(ctx, right_params, RIGHT, LEFT, ...)             */
+void svo_bm_right_matcher_params(const svo_bm_params *left, svo_bm_params *right);
+/* createDisparityWLSFilter(matcher), BM case (B11): svo_wls_default_params' values with the radius ceil(0.33 * block)   */
+void svo_wls_default_params_bm(const svo_bm_params *left, svo_wls_params *out);
+/* svo_sgbm_wls_compute with the block matcher in the SGBM matcher's place (one body serves both).  Refusals are those of
+ * svo_bm_compute and svo_wls_filter, with every output untouched.                                                       */
+int svo_bm_wls_compute(svo_ctx *ctx, const svo_bm_params *bm, const svo_wls_params *wls, const uint8_t *left,
+                       const uint8_t *right, int w, int h, int c, int n_pairs, int16_t *filtered, int16_t *disp_left,
+                       int16_t *disp_right, float *confidence, int mem);
+/* stage access for tests: the XSOBEL pre-filter (B2) of one h x w x c image (c = 3: grey first) with ftzero = cap -> out:
+ * h x w bytes.  SVO_ERR_ARG: c not 1 or 3, cap outside 1..63, w or h below 1; SVO_ERR_CAPACITY: w > 2048 or 2^30 pixels.  */
+int svo_bm_prefilter(svo_ctx *ctx, const uint8_t *image, int w, int h, int c, int cap, uint8_t *out, int mem);
+
 /* ---- SIFT: detection and descriptors of OpenCV 3.2's xfeatures2d::SIFT (src/StereoCV.cpp:64-88, 123-147) ----
  * The reference pairs features by SIFT::create(N) -> detect / compute -> convertTo(CV_32F) -> BFMatcher().knnMatch(2) -> ratio
  * 0.8 -> findFundamentalMat; svo_sift_extract_batch produces the features, svo_knn_match (SVO_MATCH_L2_F32, dim 128) and

@@ -59,6 +59,10 @@ class StereoProcess {
         Mat disp(lImg.rows, lImg.cols, kDisp16S);
         if (disp.elemSize() != 2)
             throw std::runtime_error("stereoMatch: this Mat type has no 16-bit elements");
+        if (BM_FLAG) {
+            bmMatch(disp);
+            return disp;
+        }
         if (WLS_FLAG) {
             wlsMatch(prm, disp);
             return disp;
@@ -74,6 +78,21 @@ class StereoProcess {
     bool WLS_FLAG = false;
     double lambda = 400, sigma = 0.4;
     Mat confidenceMap;
+    // BM_FLAG = true (opt-in): stereoMatch matches with cv::StereoBM's block matcher (svo_bm_compute; with WLS_FLAG also set,
+    // svo_bm_wls_compute) in StereoSGBM's place: the same output format at a fraction of the cost.  bmParams: the disparity
+    // range and the speckle filter of the reference's SGBM call (1, 96; 3000, 5), every other field StereoBM::create(0, 21)'s.
+    bool BM_FLAG = false;
+    svo_bm_params bmParams = bm_defaults();
+    static svo_bm_params bm_defaults()
+    {
+        svo_bm_params p;
+        svo_bm_default_params(&p);
+        p.min_disparity = 1;
+        p.num_disparities = 96;
+        p.speckle_window_size = 3000;
+        p.speckle_range = 5;
+        return p;
+    }
 
     // src/StereoCV.cpp:227-250: Q from stereoRectify, reprojectImageTo3D, points with Z > 5 or Z <= 0.01 skipped,
     // (X, -Y, Z) and lImg's B, G, R as floats in row-major order
@@ -483,6 +502,23 @@ class StereoProcess {
         svo_pyramid_destroy(ctx(), p);
         check(rc);
         tri3dPoints = out3d;
+    }
+    void bmMatch(Mat &disp)
+    {
+        int16_t *out = reinterpret_cast<int16_t *>(disp.data);
+        if (!WLS_FLAG) {
+            check(svo_bm_compute(ctx(), &bmParams, lImg.data, rImg.data, lImg.cols, lImg.rows, 3, 1, out, SVO_MEM_HOST));
+            return;
+        }
+        svo_wls_params wls;
+        svo_wls_default_params_bm(&bmParams, &wls);
+        wls.lambda = lambda;
+        wls.sigma_color = sigma;
+        confidenceMap = Mat(lImg.rows, lImg.cols, kConf32F);
+        if (confidenceMap.elemSize() != 4)
+            throw std::runtime_error("stereoMatch: this Mat type has no 32-bit float elements");
+        check(svo_bm_wls_compute(ctx(), &bmParams, &wls, lImg.data, rImg.data, lImg.cols, lImg.rows, 3, 1, out, nullptr, nullptr,
+                                 reinterpret_cast<float *>(confidenceMap.data), SVO_MEM_HOST));
     }
     void wlsMatch(const svo_sgbm_params &prm, Mat &disp)
     {

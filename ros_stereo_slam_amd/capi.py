@@ -788,6 +788,116 @@ def sgbm_wls(self, left, right, wls=None, want_maps=True, want_confidence=True, 
     return tuple(a[0] if single and a is not None else a for a in res)
 
 
+class BmParams(C.Structure):
+    """``svo_bm_params``: cv::StereoBM's parameters (defaults: ``StereoBM::create(0, 21)``)."""
+    _fields_ = [(n, C.c_int) for n in ("pre_filter_type", "pre_filter_size", "pre_filter_cap", "block_size", "min_disparity",
+                                       "num_disparities", "texture_threshold", "uniqueness_ratio", "speckle_window_size",
+                                       "speckle_range", "disp12_max_diff")]
+
+
+BM_PREFILTER_NORMALIZED_RESPONSE, BM_PREFILTER_XSOBEL = 0, 1
+
+
+def bm_params(**overrides) -> BmParams:
+    return _make_params(BmParams, "svo_bm_default_params", overrides)
+
+
+def bm_right_params(left: BmParams) -> BmParams:
+    """``svo_bm_right_matcher_params``: createRightMatcher(matcher)'s parameters; run as ``ctx.bm(right, left, ...)``."""
+    r = BmParams()
+    load().svo_bm_right_matcher_params(C.byref(left), C.byref(r))
+    return r
+
+
+def wls_params_bm(bm: BmParams | None = None, **overrides) -> WlsParams:
+    """``svo_wls_default_params_bm`` for a left block matcher (default: ``bm_params()``), then the overrides."""
+    return _make_params(WlsParams, "svo_wls_default_params_bm", overrides, C.byref(bm if bm is not None else bm_params()))
+
+
+def _stereo_pairs(left, right):
+    """The image arguments of the dense matchers: one pair (h x w or h x w x c) or a batch (n x h x w x c), numpy arrays or
+    device tensors (both sides alike) -> (left, right, n, h, w, c, single, on the device, maker of an output of n x h x w)."""
+    dev = _is_device(left)
+    assert dev == _is_device(right), "left and right must live in the same memory"
+    shape = tuple(left.shape)
+    assert tuple(right.shape) == shape
+    single = len(shape) in (2, 3)   # a batch is always n x h x w x c
+    if len(shape) == 2:
+        n, h, w, c = 1, shape[0], shape[1], 1
+    elif len(shape) == 3:
+        n, (h, w, c) = 1, shape
+    else:
+        n, h, w, c = shape
+    if dev:
+        import torch
+
+        names = {np.int16: torch.int16, np.float32: torch.float32, np.uint8: torch.uint8}
+        mk = lambda dt: torch.empty((n, h, w), dtype=names[dt], device=left.device)
+        lt, rt = left.contiguous(), right.contiguous()
+        torch.cuda.synchronize(left.device)
+    else:
+        mk = lambda dt: np.empty((n, h, w), dt)
+        lt, rt = np.ascontiguousarray(left, np.uint8), np.ascontiguousarray(right, np.uint8)
+    return lt, rt, n, h, w, c, single, dev, mk
+
+
+def _bm_prm(params) -> BmParams:
+    prm = params.pop("params", None)
+    return _as_params(BmParams, bm_params, prm) if prm is not None else bm_params(**params)
+
+
+@_ctx_method
+def bm(self, left, right, **params):
+    """``svo_bm_compute`` (cv::StereoBM): images as ``sgbm`` takes them -> int16 disparities x 16 of the same leading shape, a
+    numpy array for host inputs and a device tensor for device inputs.  ``params``: fields of ``svo_bm_params``, or
+    ``params=`` a BmParams."""
+    prm = _bm_prm(params)
+    lt, rt, n, h, w, c, single, dev, mk = _stereo_pairs(left, right)
+    out = mk(np.int16)
+    _check(self.lib.svo_bm_compute(self._h, C.byref(prm), _ptr(lt), _ptr(rt), w, h, c, n, _ptr(out), _mem_of(dev)))
+    if dev:
+        _check(self.lib.svo_ctx_sync(self._h))
+    return out[0] if single else out
+
+
+@_ctx_method
+def bm_wls(self, left, right, wls=None, want_maps=True, want_confidence=True, **params):
+    """``svo_bm_wls_compute``: both block matchers and the filter on one pair or a batch -> (filtered, disp_left, disp_right,
+    confidence) as ``sgbm_wls`` returns them.  ``wls``: a WlsParams or a dict of overrides of ``wls_params_bm`` for these
+    matcher parameters."""
+    bp = _bm_prm(params)
+    prm = _as_params(WlsParams, lambda **overrides: wls_params_bm(bp, **overrides), wls)
+    lt, rt, n, h, w, c, single, dev, mk = _stereo_pairs(left, right)
+    out = mk(np.int16)
+    dl, dr = (mk(np.int16), mk(np.int16)) if want_maps else (None, None)
+    conf = mk(np.float32) if want_confidence else None
+    _check(self.lib.svo_bm_wls_compute(self._h, C.byref(bp), C.byref(prm), _ptr(lt), _ptr(rt), w, h, c, n, _ptr(out), _ptr(dl),
+                                       _ptr(dr), _ptr(conf), _mem_of(dev)))
+    if dev:
+        _check(self.lib.svo_ctx_sync(self._h))
+    return tuple(a[0] if single and a is not None else a for a in (out, dl, dr, conf))
+
+
+@_ctx_method
+def bm_prefilter(self, image, cap=31):
+    """``svo_bm_prefilter``: the XSOBEL pre-filter of one h x w (x c) image (numpy array or device tensor) -> uint8 h x w."""
+    dev = _is_device(image)
+    w, h, c = _image_shape(image)
+    if dev:
+        import torch
+
+        img = image.contiguous()
+        out = torch.empty((h, w), dtype=torch.uint8, device=image.device)
+        torch.cuda.synchronize(image.device)
+    else:
+        img = np.ascontiguousarray(image, np.uint8)
+        out = np.empty((h, w), np.uint8)
+    _check(self.lib.svo_bm_prefilter(self._h, _ptr(img), w, h, c, int(cap), _ptr(out), _mem_of(dev)))
+    if dev:
+        _check(self.lib.svo_ctx_sync(self._h))
+    return out
+
+
 MATH_FN = {"sin": 0, "cos": 1, "acos": 2, "cbrt": 3, "log": 4, "exp": 5}
 MATH_EXP = MATH_FN["exp"]
 

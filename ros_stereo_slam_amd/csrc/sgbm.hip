@@ -568,6 +568,20 @@ int sgbm_check(const svo_sgbm_params *p, int w, int h)
 
 }  // namespace
 
+// the five launches of filterSpeckles; the caller checks hipGetLastError
+int svo_launch_speckle(hipStream_t st, int16_t *disp, int *parent, int *sizes, int w, int h, int n_pairs, int new_val,
+                       int max_diff, int max_size)
+{
+    const int total = n_pairs * w * h;
+    const unsigned nb = (unsigned)((total + 255) / 256);
+    hipLaunchKernelGGL(speckle_init_kernel, dim3(nb), dim3(256), 0, st, disp, parent, sizes, total, new_val);
+    hipLaunchKernelGGL(speckle_link_kernel, dim3(nb), dim3(256), 0, st, disp, parent, w, h, total, new_val, max_diff);
+    hipLaunchKernelGGL(speckle_compress_kernel, dim3(nb), dim3(256), 0, st, parent, total);
+    hipLaunchKernelGGL(speckle_count_kernel, dim3(nb), dim3(256), 0, st, parent, sizes, total);
+    hipLaunchKernelGGL(speckle_apply_kernel, dim3(nb), dim3(256), 0, st, disp, parent, sizes, total, new_val, max_size);
+    return SVO_OK;
+}
+
 extern "C" {
 
 void svo_sgbm_default_params(svo_sgbm_params *p)
@@ -660,15 +674,9 @@ int svo_sgbm_compute(svo_ctx *ctx, const svo_sgbm_params *p, const uint8_t *left
     }
     const unsigned nb = (unsigned)((npix + 255) / 256);
     hipLaunchKernelGGL(sgbm_median_kernel, dim3(nb), dim3(256), 0, st, raw, dout, w, h, n_pairs);
-    if (p->speckle_window_size > 0) {
-        const int nv = (g.minD - 1) * 16, md = 16 * p->speckle_range, total = (int)npix;
-        hipLaunchKernelGGL(speckle_init_kernel, dim3(nb), dim3(256), 0, st, dout, parent, sizes, total, nv);
-        hipLaunchKernelGGL(speckle_link_kernel, dim3(nb), dim3(256), 0, st, dout, parent, w, h, total, nv, md);
-        hipLaunchKernelGGL(speckle_compress_kernel, dim3(nb), dim3(256), 0, st, parent, total);
-        hipLaunchKernelGGL(speckle_count_kernel, dim3(nb), dim3(256), 0, st, parent, sizes, total);
-        hipLaunchKernelGGL(speckle_apply_kernel, dim3(nb), dim3(256), 0, st, dout, parent, sizes, total, nv,
+    if (p->speckle_window_size > 0)
+        svo_launch_speckle(st, dout, parent, sizes, w, h, n_pairs, (g.minD - 1) * 16, 16 * p->speckle_range,
                            p->speckle_window_size);
-    }
     SVO_HIP(hipGetLastError());
     if (mem == SVO_MEM_HOST) {
         SVO_HIP(hipMemcpyAsync(disp, dout, npix * 2, hipMemcpyDeviceToHost, st));

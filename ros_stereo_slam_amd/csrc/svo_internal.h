@@ -189,6 +189,8 @@ struct svo_ctx {
     hipEvent_t up_ev[3] = {nullptr, nullptr, nullptr}, use_ev[3] = {nullptr, nullptr, nullptr};
     // sgbm.hip: the dense matcher's cost volume and path planes, its per-pixel work arrays, the reprojection's staging
     DevBuf sgbm_cost, sgbm_misc, sgbm_rp;
+    // bm.hip: the pre-filtered images, the per-pixel minimum SAD and the speckle filter's arrays (layout: bm_plan.hip.h)
+    DevBuf bm_work;
     // sor_grid.hip: the large-cloud outlier removal's keys, sorted points, boxes and radix histograms
     DevBuf sor_grid;
     // cloud.hip: the staged source, the moved source in double, correspondences, partial sums and device states of one
@@ -397,6 +399,10 @@ int svo_orb_cv_batch(const svo_orb_cv *o);
 int svo_orb_cv_launch(svo_orb_cv *o, const uint8_t *const *d_images, int n_images, int cap_out, float *d_xy, int *d_oct,
                       float *d_resp, float *d_dir, uint32_t *d_desc, int *d_n, hipStream_t st);
 void svo_orb_default_pattern(int8_t *pat);
+// sgbm.hip: filterSpeckles(disp, new_val, max_size, max_diff) in place on n_pairs maps of h x w, back to back on the device;
+// parent / sizes: n_pairs * w * h ints each
+int svo_launch_speckle(hipStream_t st, int16_t *disp, int *parent, int *sizes, int w, int h, int n_pairs, int new_val,
+                       int max_diff, int max_size);
 // sor.hip
 int svo_launch_sor(svo_ctx *ctx, const float *xyz, const float *color, int cap, int mean_k, double stddev_mul,
                    float z_limit, float *xyz_out, float *color_out, int *d_count, float *d_mean_dist, int *d_pass);

@@ -18,6 +18,7 @@
 //                       input disparity outside (W6)
 // The two planes share a, b, c and t of a line: one lane computes them once and sweeps both.
 #include "svo_internal.h"
+#include "bm_plan.hip.h"
 
 #include <cfloat>
 #include <cmath>
@@ -422,6 +423,63 @@ int wls_run(svo_ctx *ctx, const svo_wls_params *p, const WlsGeom &g, int n, cons
     return SVO_OK;
 }
 
+// The chain of svo_sgbm_wls_compute and svo_bm_wls_compute: the left matcher, the right matcher `rp` on the swapped images (only
+// when the filter or the caller wants its map), the grey guide, the filter.  compute: svo_sgbm_compute or svo_bm_compute.
+template <class Params, class Compute>
+int wls_matcher_chain(svo_ctx *ctx, const Params *sp, const Params &rp_in, Compute compute, const svo_wls_params *wp, const WlsGeom &g,
+                      bool want_right, const uint8_t *left, const uint8_t *right, int w, int h, int c, int n_pairs,
+                      int16_t *filtered, int16_t *disp_left, int16_t *disp_right, float *confidence, int mem)
+{
+    const Params rp = rp_in;
+    int rc;
+    SVO_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t npix = (size_t)n_pairs * g.img, img_bytes = npix * c;
+    const uint8_t *dleft = left, *dright = right;
+    const bool host = mem == SVO_MEM_HOST;
+    // the matchers' maps and the grey guide stay on the device between the passes: [left map | right map | filtered |
+    // confidence | grey]
+    const size_t plane = ((npix * 2 + 255) / 256) * 256;
+    if ((rc = ctx->wls_maps.ensure(plane * 3 + npix * 4 + 256 + npix)))
+        return rc;
+    uint8_t *mb = ctx->wls_maps.as<uint8_t>();
+    int16_t *m_l = reinterpret_cast<int16_t *>(mb), *m_r = reinterpret_cast<int16_t *>(mb + plane),
+            *m_f = reinterpret_cast<int16_t *>(mb + 2 * plane);
+    float *m_c = reinterpret_cast<float *>(mb + 3 * plane);
+    uint8_t *m_g = mb + 3 * plane + ((npix * 4 + 255) / 256) * 256;
+    if (host) {
+        if ((rc = ctx->s_a.ensure(img_bytes)) || (rc = ctx->s_b.ensure(img_bytes)))
+            return rc;
+        SVO_HIP(hipMemcpyAsync(ctx->s_a.p, left, img_bytes, hipMemcpyHostToDevice, st));
+        SVO_HIP(hipMemcpyAsync(ctx->s_b.p, right, img_bytes, hipMemcpyHostToDevice, st));
+        dleft = ctx->s_a.as<uint8_t>();
+        dright = ctx->s_b.as<uint8_t>();
+    }
+    // every output is written at the end, from the maps kept here: a refusal on the way leaves them untouched
+    if ((rc = compute(ctx, sp, dleft, dright, w, h, c, n_pairs, m_l, SVO_MEM_DEVICE)))
+        return rc;
+    if (want_right && (rc = compute(ctx, &rp, dright, dleft, w, h, c, n_pairs, m_r, SVO_MEM_DEVICE)))
+        return rc;
+    const uint8_t *guide = dleft;
+    if (c == 3) {
+        hipLaunchKernelGGL(wls_grey_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, dleft, m_g, npix);
+        guide = m_g;
+    }
+    if ((rc = wls_run(ctx, wp, g, n_pairs, m_l, m_r, guide, m_f, confidence ? m_c : nullptr)))
+        return rc;
+    const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    SVO_HIP(hipMemcpyAsync(filtered, m_f, npix * 2, kind, st));
+    if (disp_left)
+        SVO_HIP(hipMemcpyAsync(disp_left, m_l, npix * 2, kind, st));
+    if (disp_right)
+        SVO_HIP(hipMemcpyAsync(disp_right, m_r, npix * 2, kind, st));
+    if (confidence)
+        SVO_HIP(hipMemcpyAsync(confidence, m_c, npix * 4, kind, st));
+    if (host)
+        SVO_HIP(hipStreamSynchronize(st));
+    return SVO_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -503,52 +561,59 @@ int svo_sgbm_wls_compute(svo_ctx *ctx, const svo_sgbm_params *sp, const svo_wls_
     svo_sgbm_right_matcher_params(sp, &rp);
     const bool want_right = wp->use_confidence || disp_right;
     SVO_CHECK_ARG(!want_right || w > rp.num_disparities + rp.min_disparity);   // what the right matcher would refuse
-    SVO_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const size_t npix = (size_t)n_pairs * g.img, img_bytes = npix * c;
-    const uint8_t *dleft = left, *dright = right;
-    const bool host = mem == SVO_MEM_HOST;
-    // the matchers' maps and the grey guide stay on the device between the passes: [left map | right map | filtered |
-    // confidence | grey]
-    const size_t plane = ((npix * 2 + 255) / 256) * 256;
-    if ((rc = ctx->wls_maps.ensure(plane * 3 + npix * 4 + 256 + npix)))
+    return wls_matcher_chain(ctx, sp, rp, svo_sgbm_compute, wp, g, want_right, left, right, w, h, c, n_pairs, filtered, disp_left,
+                             disp_right, confidence, mem);
+}
+
+void svo_bm_right_matcher_params(const svo_bm_params *left, svo_bm_params *right)
+{
+    if (!left || !right)
+        return;
+    const svo_bm_params l = *left;
+    *right = l;
+    right->min_disparity = -(l.min_disparity + l.num_disparities) + 1;
+    right->texture_threshold = 0;
+    right->uniqueness_ratio = 0;
+    right->disp12_max_diff = 1000000;
+    right->speckle_window_size = 0;
+    right->speckle_range = 0;
+}
+
+void svo_wls_default_params_bm(const svo_bm_params *left, svo_wls_params *out)
+{
+    if (!left || !out)
+        return;
+    svo_sgbm_params range;   // the ROI and the other values are the SGBM case's, formed from the range and the block alone
+    svo_sgbm_default_params(&range);
+    range.min_disparity = left->min_disparity;
+    range.num_disparities = left->num_disparities;
+    range.block_size = left->block_size;
+    svo_wls_default_params(&range, out);
+    out->depth_discontinuity_radius = left->block_size > 0 ? (int)((33ll * left->block_size + 99) / 100) : 0;   // ceil(0.33 * block)
+}
+
+int svo_bm_wls_compute(svo_ctx *ctx, const svo_bm_params *bp, const svo_wls_params *wp, const uint8_t *left, const uint8_t *right,
+                       int w, int h, int c, int n_pairs, int16_t *filtered, int16_t *disp_left, int16_t *disp_right,
+                       float *confidence, int mem)
+{
+    WlsGeom g;
+    int rc;
+    SVO_CHECK_ARG(bp != nullptr);
+    if ((rc = wls_check(wp, w, h, 1, n_pairs, &g)))   // the guide is the grey left image
         return rc;
-    uint8_t *mb = ctx->wls_maps.as<uint8_t>();
-    int16_t *m_l = reinterpret_cast<int16_t *>(mb), *m_r = reinterpret_cast<int16_t *>(mb + plane),
-            *m_f = reinterpret_cast<int16_t *>(mb + 2 * plane);
-    float *m_c = reinterpret_cast<float *>(mb + 3 * plane);
-    uint8_t *m_g = mb + 3 * plane + ((npix * 4 + 255) / 256) * 256;
-    if (host) {
-        if ((rc = ctx->s_a.ensure(img_bytes)) || (rc = ctx->s_b.ensure(img_bytes)))
-            return rc;
-        SVO_HIP(hipMemcpyAsync(ctx->s_a.p, left, img_bytes, hipMemcpyHostToDevice, st));
-        SVO_HIP(hipMemcpyAsync(ctx->s_b.p, right, img_bytes, hipMemcpyHostToDevice, st));
-        dleft = ctx->s_a.as<uint8_t>();
-        dright = ctx->s_b.as<uint8_t>();
+    const char *why = nullptr;
+    if ((rc = bm_plan::check(bp, w, h, c, n_pairs, &why))) {   // the matcher's refusals, before anything is touched
+        svo_set_error("svo_bm_wls_compute: %s", why);
+        return rc == 1 ? SVO_ERR_ARG : SVO_ERR_CAPACITY;
     }
-    // every output is written at the end, from the maps kept here: a refusal on the way leaves them untouched
-    if ((rc = svo_sgbm_compute(ctx, sp, dleft, dright, w, h, c, n_pairs, m_l, SVO_MEM_DEVICE)))
-        return rc;
-    if (want_right && (rc = svo_sgbm_compute(ctx, &rp, dright, dleft, w, h, c, n_pairs, m_r, SVO_MEM_DEVICE)))
-        return rc;
-    const uint8_t *guide = dleft;
-    if (c == 3) {
-        hipLaunchKernelGGL(wls_grey_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, dleft, m_g, npix);
-        guide = m_g;
-    }
-    if ((rc = wls_run(ctx, wp, g, n_pairs, m_l, m_r, guide, m_f, confidence ? m_c : nullptr)))
-        return rc;
-    const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    SVO_HIP(hipMemcpyAsync(filtered, m_f, npix * 2, kind, st));
-    if (disp_left)
-        SVO_HIP(hipMemcpyAsync(disp_left, m_l, npix * 2, kind, st));
-    if (disp_right)
-        SVO_HIP(hipMemcpyAsync(disp_right, m_r, npix * 2, kind, st));
-    if (confidence)
-        SVO_HIP(hipMemcpyAsync(confidence, m_c, npix * 4, kind, st));
-    if (host)
-        SVO_HIP(hipStreamSynchronize(st));
-    return SVO_OK;
+    SVO_CHECK_ARG(ctx && left && right && filtered);
+    SVO_CHECK_ARG(mem == SVO_MEM_HOST || mem == SVO_MEM_DEVICE);
+    // the right matcher refuses what the left one does (the same sizes and block; an empty band is no refusal), and the left
+    // one runs first, into the chain's own maps
+    svo_bm_params rp;
+    svo_bm_right_matcher_params(bp, &rp);
+    return wls_matcher_chain(ctx, bp, rp, svo_bm_compute, wp, g, wp->use_confidence || disp_right, left, right, w, h, c, n_pairs,
+                             filtered, disp_left, disp_right, confidence, mem);
 }
 
 }  // extern "C"
