@@ -99,6 +99,12 @@ int svo_math_eval(svo_ctx *ctx, int fn, const double *x, int n, double *y, int m
  * build the lock-step groups use (two jobs), else the lone-chunk build.  The mask's contents are unspecified. */
 int svo_selftest_fransac_gate(svo_ctx *ctx, const float *d_p1, const float *d_p2, int n, double threshold,
                               uint64_t seed, int lean, uint8_t *d_mask, unsigned *tickets_after);
+/* svo_selftest_scan: the workgroup prefix scan under every ordered compaction of the library (csrc/scan_ops.hip.h), run by
+ * ONE workgroup: d_out[0..n) = the exclusive prefix sums of d_in[0..n), *d_total = the sum.  kind selects the workgroup size
+ * and the element type.  Device pointers of that type; d_out == d_in is allowed; n <= 2^24.  Returns after the launch has
+ * finished. */
+enum { SVO_SCAN_256_INT = 0, SVO_SCAN_1024_UINT = 1, SVO_SCAN_1024_U64 = 2 };
+int svo_selftest_scan(svo_ctx *ctx, int kind, const void *d_in, int n, void *d_out, void *d_total);
 
 /* ---- image pyramid ----------------------------------------------------------------------- */
 /* Replaces the pyramid cv::calcOpticalFlowPyrLK rebuilds on every call

@@ -912,6 +912,17 @@ def math_eval(self, fn: str, x) -> np.ndarray:
     return y
 
 
+SCAN_KINDS = {"256_int": (0, "int32"), "1024_uint": (1, "uint32"), "1024_u64": (2, "uint64")}
+
+
+@_ctx_method
+def selftest_scan(self, kind: str, d_in, n: int, d_out, d_total) -> None:
+    """svo_selftest_scan: ``d_out[:n]`` = the exclusive prefix sums of ``d_in[:n]`` and ``d_total[0]`` their sum, by one
+    workgroup of csrc/scan_ops.hip.h's block scan.  Device arrays of SCAN_KINDS[kind]'s element size; ``d_out`` may be
+    ``d_in``."""
+    _check(self.lib.svo_selftest_scan(self._h, SCAN_KINDS[kind][0], _ptr(d_in), int(n), _ptr(d_out), _ptr(d_total)))
+
+
 class SiftParams(C.Structure):
     """``svo_sift_params``: cv::xfeatures2d::SIFT::create's arguments (n_features 0 = all)."""
     _fields_ = [("n_features", C.c_int), ("n_octave_layers", C.c_int), ("contrast_threshold", C.c_double),

@@ -12,6 +12,7 @@
 #include <cfloat>
 
 #include "svo_internal.h"
+#include "scan_ops.hip.h"
 #include "wave_ops.hip.h"
 
 namespace {
@@ -241,29 +242,15 @@ template <int NJ> __global__ __launch_bounds__(GATHER_T) void anms_gather_kernel
     int *__restrict__ out_idx = job.out_idx;
     int *__restrict__ d_count = job.d_count;
     __shared__ int s_wave[GATHER_T / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     const int per = (n + GATHER_T - 1) / GATHER_T;
     const int b = t * per, e = min(b + per, n);
     int cnt = 0;
     for (int i = b; i < e; i++)
         cnt += radius_sq[i] >= decision ? 1 : 0;
-    // exclusive prefix of the threads' counts: shuffles inside a wave, the wave totals through LDS -- one barrier
-    int incl = cnt;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(incl, off, 64);
-        incl += lane >= off ? o : 0;
-    }
-    if (lane == 63)
-        s_wave[wave] = incl;
-    __syncthreads();
-    int pos = incl - cnt, total = 0;
-#pragma unroll
-    for (int w2 = 0; w2 < GATHER_T / 64; w2++) {
-        const int wt = s_wave[w2];
-        pos += w2 < wave ? wt : 0;
-        total += wt;
-    }
+    // exclusive prefix of the threads' counts (scan_ops.hip.h): shuffles inside a wave, the wave totals through LDS -- one barrier
+    int total;
+    int pos = svo::block_excl_scan<GATHER_T>(cnt, s_wave, &total);
     if (t == 0)
         *d_count = total;
     for (int i = b; i < e; i++)

@@ -9,8 +9,8 @@
 // one, and oracle/bow.c is its CPU twin (every integer and every double of it is compared bit for bit).
 //
 // Mapping
-//   training      one workgroup per tree node and level: kmeans++ seeding (block scans over the node's Hamming
-//                 distances), Lloyd steps with the majority vote per bit (FORB::meanValue) -- a wave holds 64 descriptors
+//   training      one workgroup per tree node and level: kmeans++ seeding (scan_ops.hip.h's block scans over the node's
+//                 Hamming distances), Lloyd steps with the majority vote per bit (FORB::meanValue) -- a wave holds 64 descriptors
 //                 in registers and broadcasts them lane by lane, thread t owns bit t of every cluster's counters --,
 //                 assignment by v_xor + v_bcnt, a stable partition of the node's descriptors into its children.  All of
 //                 it is integer arithmetic: the tree equals the oracle's bit for bit.  The host only walks the levels.
@@ -26,6 +26,7 @@
 
 #include "svo_internal.h"
 #include "ransac_common.hip.h"
+#include "scan_ops.hip.h"
 
 using svo::rng_u32;
 
@@ -124,24 +125,13 @@ __global__ __launch_bounds__(256) void voc_cluster_kernel(const uint32_t *__rest
             int f = n - 1;
             for (int base = 0; base < n; base += 256) {
                 const int i = base + t;
-                long long v = i < n ? md[i] : 0, incl = v;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const long long u = __shfl_up(incl, o, 64);
-                    if (lane >= o)
-                        incl += u;
-                }
-                if (lane == 63)
-                    s_wsum[wave] = incl;
+                const long long v = i < n ? md[i] : 0;
                 if (t == 0)
-                    s_pick = 1 << 30;
-                __syncthreads();
-                long long before = running;
-                for (int w = 0; w < wave; w++)
-                    before += s_wsum[w];
-                if (i < n && before + incl >= cut)
+                    s_pick = 1 << 30;  // the scan's barrier stands between this and the bids
+                long long total;
+                const long long before = running + svo::block_excl_scan<256>(v, s_wsum, &total);
+                if (i < n && before + v >= cut)
                     atomicMin(&s_pick, i);
-                const long long total = s_wsum[0] + s_wsum[1] + s_wsum[2] + s_wsum[3];
                 __syncthreads();
                 const int pick = s_pick;
                 __syncthreads();
@@ -272,7 +262,7 @@ __global__ __launch_bounds__(256) void voc_cluster_kernel(const uint32_t *__rest
             if (lane == 0)
                 s_wtot[wave][c] = __popcll(bal);
             if (a == c)
-                before = __popcll(bal & ((1ull << lane) - 1ull));
+                before = svo::lanes_below(bal);
         }
         __syncthreads();
         if (a >= 0) {
@@ -409,7 +399,7 @@ __global__ __launch_bounds__(BOW_VEC_T) void bow_vector_kernel(const int *__rest
     int *s_key = reinterpret_cast<int *>(s_acc + cap4), *s_sw = s_key + cap4;   // s_key: 16-byte aligned (cap4 is a multiple of 4)
     __shared__ int s_wave[BOW_VEC_T / 64], s_nv;
     __shared__ double s_norm;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     {   // blockIdx.x = the frame of a batch: n_host slots per frame, consecutive database rows
         const size_t g = blockIdx.x;
         word += g * n_host;
@@ -462,15 +452,8 @@ __global__ __launch_bounds__(BOW_VEC_T) void bow_vector_kernel(const int *__rest
         const int r = r0 + t;
         const bool first = r < nv && (r == 0 || s_sw[r] != s_sw[r - 1]);
         const unsigned long long b = __ballot(first);
-        if (lane == 0)
-            s_wave[wave] = __popcll(b);
-        __syncthreads();
-        int u = before + __popcll(b & ((1ull << lane) - 1ull)), tot = 0;
-#pragma unroll
-        for (int w2 = 0; w2 < BOW_VEC_T / 64; w2++) {
-            u += w2 < wave ? s_wave[w2] : 0;
-            tot += s_wave[w2];
-        }
+        int tot;
+        const int u = before + svo::waves_before<BOW_VEC_T>((int)__popcll(b), s_wave, &tot) + svo::lanes_below(b);
         if (first) {
             double acc = s_sx[r];
             for (int q = r + 1; q < nv && s_sw[q] == s_sw[r]; q++)

@@ -17,6 +17,7 @@
 
 #include "svo_internal.h"
 #include "brief_pattern.hip.h"
+#include "scan_ops.hip.h"
 
 namespace {
 

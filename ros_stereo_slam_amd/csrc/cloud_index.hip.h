@@ -4,6 +4,7 @@
 // of a point to a box.  Every kernel here has internal linkage: each of the two translation units carries its own copy.
 #pragma once
 #include "svo_internal.h"
+#include "scan_ops.hip.h"
 #include "wave_ops.hip.h"
 
 namespace {
@@ -31,7 +32,7 @@ __global__ __launch_bounds__(RS_THREADS) void radix_hist_kernel(const uint64_t *
                                                                 int nblk, unsigned *__restrict__ hist)
 {
     __shared__ unsigned h[256];
-    const int tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x;
     h[tid] = 0;
     __syncthreads();
     const int base = blockIdx.x * RS_TILE;
@@ -40,32 +41,25 @@ __global__ __launch_bounds__(RS_THREADS) void radix_hist_kernel(const uint64_t *
         const bool valid = i < n;
         const unsigned d = valid ? (unsigned)(keys[i] >> shift) & 255u : 0u;
         const unsigned long long peers = match_digit(valid, d);
-        if (valid && (peers & ((1ull << lane) - 1ull)) == 0)  // the lowest lane of its digit adds for all of them
+        if (valid && svo::lanes_below(peers) == 0)  // the lowest lane of its digit adds for all of them
             atomicAdd(&h[d], (unsigned)__popcll(peers));
     }
     __syncthreads();
     hist[tid * nblk + blockIdx.x] = h[tid];
 }
 
-// exclusive scan of total (= 256 x nblk, digit-major) counts in place, one workgroup
+// exclusive scan of total (= 256 x nblk, digit-major) counts in place, one workgroup: `per` counts a thread, the block scan of
+// scan_ops.hip.h over the threads' sums, the counts again
 __global__ __launch_bounds__(1024) void radix_scan_kernel(unsigned *__restrict__ h, int total)
 {
-    __shared__ unsigned part[1024];
+    __shared__ unsigned s_wave[16];
     const int tid = threadIdx.x;
     const int per = (total + 1023) / 1024;
     const int s = tid * per, e = min(s + per, total);
     unsigned sum = 0;
     for (int j = s; j < e; j++)
         sum += h[j];
-    part[tid] = sum;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const unsigned v = tid >= off ? part[tid - off] : 0u;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    unsigned run = part[tid] - sum;
+    unsigned run = svo::block_excl_scan<1024>(sum, s_wave, (unsigned *)nullptr);
     for (int j = s; j < e; j++) {
         const unsigned t = h[j];
         h[j] = run;
@@ -81,7 +75,7 @@ __global__ __launch_bounds__(RS_THREADS) void radix_scatter_kernel(const uint64_
 {
     __shared__ unsigned run[256];
     __shared__ unsigned wcnt[RS_THREADS / 64][256];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x, w = tid >> 6;
     run[tid] = hist[tid * nblk + blockIdx.x];
 #pragma unroll
     for (int q = 0; q < RS_THREADS / 64; q++)
@@ -94,7 +88,7 @@ __global__ __launch_bounds__(RS_THREADS) void radix_scatter_kernel(const uint64_
         const uint64_t key = valid ? kin[i] : 0ull;
         const unsigned d = (unsigned)(key >> shift) & 255u;
         const unsigned long long peers = match_digit(valid, d);
-        const int rank = __popcll(peers & ((1ull << lane) - 1ull));
+        const int rank = svo::lanes_below(peers);
         if (valid && rank == 0)
             wcnt[w][d] = (unsigned)__popcll(peers);
         __syncthreads();

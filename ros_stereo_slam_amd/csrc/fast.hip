@@ -13,13 +13,15 @@
 //                         score 0) and, when asked for, the public score plane
 //   fast_compact_kernel   <false>: a wavefront counts the key points among its 1024 consecutive pixels of the row-major plane (ballot +
 //                         popcount) and, for retainBest, adds their scores to the image's 256-bin histogram
-//   fast_scan_kernel      one workgroup per image: exclusive scan of the wavefronts' counts, the total, the cut of retainBest
+//   fast_scan_kernel      one workgroup per image: exclusive scan of the wavefronts' counts (scan_ops.hip.h), the total, the cut of
+//                         retainBest
 //   fast_compact_kernel   <true>: the same walk again, each key point written at offset + rank inside the wavefront
 // No atomic decides a position: the order of the output is the order of the pixels.  With retainBest the count / scan pair runs a
 // second time with the cut applied.  The chained call hands the lists to anms.hip's launches without leaving the device.
 #include "svo_internal.h"
 
 #include "fast_plan.hip.h"
+#include "scan_ops.hip.h"
 
 namespace {
 
@@ -209,7 +211,7 @@ __global__ __launch_bounds__(64 * WAVES) void fast_compact_kernel(const uint8_t 
             }
             const unsigned long long m = __ballot(v != 0);
             if (SCATTER) {
-                const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+                const int pos = base + svo::lanes_below(m);
                 if (v && pos < cap) {
                     oxy[pos] = make_float2((float)x, (float)y);
                     if (orp)
@@ -236,36 +238,10 @@ __global__ __launch_bounds__(256) void fast_scan_kernel(const int *span_count, i
                                                         int max_keypoints, int *cut)
 {
     __shared__ int s_wave[4];
-    const int img = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int *__restrict__ cnt = span_count + (size_t)img * spans;
-    int *__restrict__ off = span_offset + (size_t)img * spans;
-    int carry = 0;
-    for (int b = 0; b < spans; b += 256) {
-        const int i = b + t;
-        const int v = i < spans ? cnt[i] : 0;
-        int incl = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_up(incl, o, 64);
-            incl += lane >= o ? u : 0;
-        }
-        if (lane == 63)
-            s_wave[wave] = incl;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int wt = s_wave[k];
-            before += k < wave ? wt : 0;
-            total += wt;
-        }
-        if (i < spans)
-            off[i] = carry + before + incl - v;
-        carry += total;
-        __syncthreads();
-    }
-    if (t == 0) {
-        counts[img] = carry;
+    const int img = blockIdx.x;
+    const int total = svo::block_scan_counts<256>(span_count + (size_t)img * spans, span_offset + (size_t)img * spans, spans, s_wave);
+    if (threadIdx.x == 0) {
+        counts[img] = total;
         if (hist)
             cut[img] = retain_cut(hist + img * 256, max_keypoints);
     }

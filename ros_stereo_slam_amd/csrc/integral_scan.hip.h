@@ -1,6 +1,7 @@
 // integral_scan.hip.h -- the batched int32 integral image of 8-bit images (grey, or BGR through svo_bgr2gray): (h + 1) x (w + 1),
 // zero first row and column; blockIdx.y = image of the batch.  Shared by brief.hip and surf.hip; each includes it inside its own
-// unnamed namespace, after feature_batch.hip.h.  Integer sums: exact, no order dependence.
+// unnamed namespace, after feature_batch.hip.h, and includes scan_ops.hip.h (the row scan's block scan) at file scope before that.
+// Integer sums: exact, no order dependence.
 #pragma once
 
 // the largest entry is at most 255 w h
@@ -13,8 +14,8 @@ inline long long integral_img_stride(int w, int h) { return (((long long)(w + 1)
 __global__ __launch_bounds__(256) void integral_row_scan_kernel(ImageBatch im, int w, int h, int c, int *__restrict__ sum_all,
                                                              long long img_stride)
 {
-    __shared__ int wave_total[4];
-    const int y = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ int s_wave[4];
+    const int y = blockIdx.x;
     const uint8_t *__restrict__ row = im.img[blockIdx.y] + (size_t)y * w * c;
     int *__restrict__ out = sum_all + blockIdx.y * img_stride + (size_t)(y + 1) * (w + 1);
     if (threadIdx.x == 0)
@@ -28,23 +29,10 @@ __global__ __launch_bounds__(256) void integral_row_scan_kernel(ImageBatch im, i
         int v = 0;
         if (x < w)
             v = c == 1 ? (int)row[x] : svo_bgr2gray(row[3 * x], row[3 * x + 1], row[3 * x + 2]);
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(v, o);
-            if (lane >= o)
-                v += t;
-        }
-        if (lane == 63)
-            wave_total[wave] = v;
-        __syncthreads();
-        int before = carry, all = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            before += k < wave ? wave_total[k] : 0;
-            all += wave_total[k];
-        }
+        int all;
+        const int before = svo::block_excl_scan<256>(v, s_wave, &all);
         if (x < w)
-            out[x + 1] = v + before;
+            out[x + 1] = carry + before + v;   // the inclusive sum
         carry += all;
         __syncthreads();
     }

@@ -27,11 +27,13 @@
 //                        train row bid for its query with a 64-bit atomicMin of (key << 32 | train row) and cross_finish_kernel
 //                        writes the winners; cross_mutual_kernel looks a query's best train row up in the reverse lists.
 //   svo_radius_match     SEARCH_COUNT counts the keys up to the radius' largest key per query and split, radius_scan_kernel
-//                        turns the counts into positions, SEARCH_WRITE stores (key << 32 | train row) entries there and
-//                        radius_sort_kernel sorts one query's entries in LDS and writes idx / dist.
+//                        turns the counts into positions (the block scan of scan_ops.hip.h), SEARCH_WRITE stores
+//                        (key << 32 | train row) entries there and radius_sort_kernel sorts one query's entries in LDS and
+//                        writes idx / dist.
 #include <cmath>
 
 #include "match_plan.hip.h"
+#include "scan_ops.hip.h"
 #include "svo_internal.h"
 
 namespace {
@@ -385,7 +387,7 @@ __global__ __launch_bounds__(SCAN_T) void radius_scan_kernel(MatchBatch b, int n
                                                              int *__restrict__ row_start, int *__restrict__ row_offsets,
                                                              int capacity, int *__restrict__ scal)
 {
-    __shared__ unsigned long long sc[SCAN_T];
+    __shared__ unsigned long long s_wave[SCAN_T / 64];
     __shared__ int longest;
     const int tid = threadIdx.x;
     if (tid == 0)
@@ -404,22 +406,16 @@ __global__ __launch_bounds__(SCAN_T) void radius_scan_kernel(MatchBatch b, int n
                     n += v;  // at most the train rows of the problem
                 }
             }
-            __syncthreads();  // sc of the previous round has been read
-            sc[tid] = (unsigned long long)n;
-            __syncthreads();
-            for (int off = 1; off < SCAN_T; off <<= 1) {
-                const unsigned long long v = tid >= off ? sc[tid - off] : 0ull;
-                __syncthreads();
-                sc[tid] += v;
-                __syncthreads();
-            }
+            __syncthreads();  // s_wave of the previous round has been read
+            unsigned long long total;
+            const unsigned long long before = svo::block_excl_scan<SCAN_T>((unsigned long long)n, s_wave, &total);
             if (i < pr.nq) {
-                const int start = match_plan::saturate(carry + sc[tid] - (unsigned long long)n);
+                const int start = match_plan::saturate(carry + before);
                 row_start[pr.q0 + i] = start;
                 row_offsets[pr.q0 + i + p] = start;
                 atomicMax(&longest, n);
             }
-            carry += sc[SCAN_T - 1];
+            carry += total;
         }
         if (tid == 0)
             row_offsets[pr.q0 + pr.nq + p] = match_plan::saturate(carry);

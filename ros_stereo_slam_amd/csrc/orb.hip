@@ -15,6 +15,7 @@
 //   fast_harris      thread per pixel: 16-pixel ring -> two 16-bit masks -> nine-contiguous test by
 //                    shifts; corners get their Harris response
 //   nms + strip count, strip scan, candidate write: order-preserving multi-workgroup compaction
+//                    (the scans and ranks are scan_ops.hip.h's)
 //   select           one workgroup: k-th largest response by a 32-step bitwise search over the
 //                    candidates, ties at the cut in raster order, ballot-scan write
 //   describe         ONE WAVEFRONT PER KEYPOINT: disc moments reduced with DPP, the 256 tests 64 at
@@ -23,6 +24,7 @@
 #include <vector>
 
 #include "svo_internal.h"
+#include "scan_ops.hip.h"
 #include "wave_ops.hip.h"
 
 namespace {
@@ -163,23 +165,18 @@ __global__ __launch_bounds__(STRIP) void nms_count_kernel(OrbLevels L, const flo
     }
     if (idx < w * h)
         keep[idx] = k ? 1 : 0;
-    const unsigned long long bal = __ballot(k);
-    if ((threadIdx.x & 63) == 0)
-        s_w[threadIdx.x >> 6] = __popcll(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int i = 0; i < 16; i++)
-            s += s_w[i];
-        strip_count[blockIdx.x] = s;
-    }
+    int total;
+    svo::waves_before<STRIP>((int)__popcll(__ballot(k)), s_w, &total);
+    if (threadIdx.x == 0)
+        strip_count[blockIdx.x] = total;
 }
 
-// exclusive scan of the strip counts (one workgroup; n_strips <= a few thousand)
+// exclusive scan of the strip counts (one workgroup; n_strips <= a few thousand): `per` strips a thread, a block scan of the
+// threads' sums, the strips again
 __global__ __launch_bounds__(1024) void strip_scan_kernel(OrbLevels L, const int *__restrict__ cnt_all,
                                                           int *__restrict__ off_all, int *__restrict__ totals)
 {
-    __shared__ int s_part[1024];
+    __shared__ int s_w[16];
     const int l = blockIdx.x, n = (L.w[l] * L.h[l] + STRIP - 1) / STRIP;
     const int *__restrict__ cnt = cnt_all + L.strip_off[l];
     int *__restrict__ off = off_all + L.strip_off[l];
@@ -194,19 +191,10 @@ __global__ __launch_bounds__(1024) void strip_scan_kernel(OrbLevels L, const int
     int s = 0;
     for (int i = t * per; i < (t + 1) * per && i < n; i++)
         s += cnt[i];
-    s_part[t] = s;
-    __syncthreads();
-    if (t == 0) {
-        int acc = 0;
-        for (int i = 0; i < 1024; i++) {
-            const int v = s_part[i];
-            s_part[i] = acc;
-            acc += v;
-        }
-        *total = acc;
-    }
-    __syncthreads();
-    int acc = s_part[t];
+    int all;
+    int acc = svo::block_excl_scan<1024>(s, s_w, &all);
+    if (t == 0)
+        *total = all;
     for (int i = t * per; i < (t + 1) * per && i < n; i++) {
         off[i] = acc;
         acc += cnt[i];
@@ -227,17 +215,11 @@ __global__ __launch_bounds__(STRIP) void cand_write_kernel(OrbLevels L, const ui
     int *__restrict__ cand_idx = cand_idx_all + L.cand_off[l];
     float *__restrict__ cand_resp = cand_resp_all + L.cand_off[l];
     const int idx = blockIdx.x * STRIP + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool k = idx < n_pix && keep[idx];
     const unsigned long long bal = __ballot(k);
-    if (lane == 0)
-        s_w[wave] = __popcll(bal);
-    __syncthreads();
-    int base = off[blockIdx.x];
-    for (int i = 0; i < wave; i++)
-        base += s_w[i];
+    const int base = off[blockIdx.x] + svo::waves_before<STRIP>((int)__popcll(bal), s_w, (int *)nullptr);
     if (k) {
-        const int pos = base + __popcll(bal & ((1ull << lane) - 1ull));
+        const int pos = base + svo::lanes_below(bal);
         if (pos < cap) {
             cand_idx[pos] = idx;
             cand_resp[pos] = R[idx];
@@ -335,27 +317,12 @@ __global__ __launch_bounds__(1024) void select_kernel(OrbLevels L, const int *__
         const bool tie = i < nc && nc > want && key == thr;
         // ties first get their running rank (raster order), the first `ties_allowed` are kept
         const unsigned long long tb = __ballot(tie);
-        if (lane == 0)
-            s_red[wave] = __popcll(tb);
-        __syncthreads();
-        int tie_rank = s_ties + __popcll(tb & ((1ull << lane) - 1ull));
-        int tie_total = 0;
-        for (int w2 = 0; w2 < 16; w2++) {
-            tie_rank += w2 < wave ? s_red[w2] : 0;
-            tie_total += s_red[w2];
-        }
+        int tie_total, kept_total;
+        const int tie_rank = s_ties + svo::waves_before<1024>((int)__popcll(tb), s_red, &tie_total) + svo::lanes_below(tb);
         const bool keep = above || (tie && tie_rank < ties_allowed);
-        __syncthreads();
+        __syncthreads();  // s_red is read
         const unsigned long long kb = __ballot(keep);
-        if (lane == 0)
-            s_red[wave] = __popcll(kb);
-        __syncthreads();
-        int pos = s_base + __popcll(kb & ((1ull << lane) - 1ull));
-        int kept_total = 0;
-        for (int w2 = 0; w2 < 16; w2++) {
-            pos += w2 < wave ? s_red[w2] : 0;
-            kept_total += s_red[w2];
-        }
+        const int pos = s_base + svo::waves_before<1024>((int)__popcll(kb), s_red, &kept_total) + svo::lanes_below(kb);
         if (keep) {
             sel_idx[pos] = cand_idx[i];
             sel_resp[pos] = cand_resp[i];

@@ -12,8 +12,8 @@
 //   2. extrema: one lane per DoG pixel; a lane that finds a 26-neighbour extremum runs the sub-pixel refinement itself and
 //      marks the cell its refinement ENDS in (a byte map over layer x row x column).  What a key point carries depends on
 //      that cell only, so several starts that end in one cell write the same byte: removeDuplicated without a sort.
-//   3. an ordered compaction of the byte map (block sums, scan of the sums, emit) lists the cells in (octave, layer, row,
-//      column) order -- the output order of the recipe falls out of the scan.
+//   3. an ordered compaction of the byte map (block sums, scan of the sums, emit; the block scans are scan_ops.hip.h's) lists
+//      the cells in (octave, layer, row, column) order -- the output order of the recipe falls out of the scan.
 //   4. orientation: one wavefront per cell; the 36-bin histogram in LDS, peaks by ballot, in bin order.
 //   5. a second ordered compaction expands the peaks, a radix selection on the response bits finds retainBest's threshold,
 //      a third compaction keeps responses at or above it and writes the public fields (halved for the doubled octave).
@@ -24,6 +24,8 @@
 
 #include "svo_internal.h"
 #include "fast_atan2.hip.h"
+#include "scan_ops.hip.h"
+#include "wave_ops.hip.h"
 
 namespace {
 
@@ -269,28 +271,10 @@ __global__ __launch_bounds__(256) void sift_extrema_kernel(SiftGeom g, int o, co
     }
 }
 
-// ---- 3. ordered compaction: block sums, scan of the sums, emit ----
-__device__ __forceinline__ unsigned block_excl_scan(unsigned v, unsigned *sh, unsigned *total)
-{
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int off = 1; off < SCAN_T; off <<= 1) {
-        const unsigned a = t >= off ? sh[t - off] : 0u;
-        __syncthreads();
-        sh[t] += a;
-        __syncthreads();
-    }
-    const unsigned incl = sh[t];
-    if (total)
-        *total = sh[SCAN_T - 1];
-    __syncthreads();
-    return incl - v;
-}
-
+// ---- 3. ordered compaction: block sums, scan of the sums, emit (the block scans are scan_ops.hip.h's) ----
 template <class In> __global__ __launch_bounds__(SCAN_T) void scan_sums_kernel(In in, unsigned *__restrict__ bsum, int nblk)
 {
-    __shared__ unsigned sh[SCAN_T];
+    __shared__ unsigned s_wave[SCAN_T / 64];
     const int img = blockIdx.y, n = in.count(img);
     const int base = blockIdx.x * SCAN_BLOCK + threadIdx.x * SCAN_ITEMS;
     unsigned s = 0;
@@ -298,7 +282,7 @@ template <class In> __global__ __launch_bounds__(SCAN_T) void scan_sums_kernel(I
         if (base + k < n)
             s += in.get(img, base + k);
     unsigned total;
-    block_excl_scan(s, sh, &total);
+    svo::waves_before<SCAN_T>(svo::wave_sum(s), s_wave, &total);   // only the block's total
     if (threadIdx.x == 0)
         bsum[(size_t)img * nblk + blockIdx.x] = total;
 }
@@ -306,14 +290,14 @@ template <class In> __global__ __launch_bounds__(SCAN_T) void scan_sums_kernel(I
 // one workgroup per image: the block sums become exclusive offsets, the total goes to total[img]
 __global__ __launch_bounds__(SCAN_T) void scan_offsets_kernel(unsigned *__restrict__ bsum, int nblk, int *__restrict__ total)
 {
-    __shared__ unsigned sh[SCAN_T];
+    __shared__ unsigned s_wave[SCAN_T / 64];
     unsigned *b = bsum + (size_t)blockIdx.x * nblk;
     const int per = (nblk + SCAN_T - 1) / SCAN_T, lo = threadIdx.x * per, hi = lo + per < nblk ? lo + per : nblk;
     unsigned s = 0;
     for (int i = lo; i < hi; i++)
         s += b[i];
     unsigned tot;
-    unsigned run = block_excl_scan(s, sh, &tot);
+    unsigned run = svo::block_excl_scan<SCAN_T>(s, s_wave, &tot);
     for (int i = lo; i < hi; i++) {
         const unsigned v = b[i];
         b[i] = run;
@@ -326,7 +310,7 @@ __global__ __launch_bounds__(SCAN_T) void scan_offsets_kernel(unsigned *__restri
 template <class In, class Emit>
 __global__ __launch_bounds__(SCAN_T) void scan_emit_kernel(In in, const unsigned *__restrict__ bsum, int nblk, Emit emit)
 {
-    __shared__ unsigned sh[SCAN_T];
+    __shared__ unsigned s_wave[SCAN_T / 64];
     const int img = blockIdx.y, n = in.count(img);
     const int base = blockIdx.x * SCAN_BLOCK + threadIdx.x * SCAN_ITEMS;
     unsigned v[SCAN_ITEMS], s = 0;
@@ -334,7 +318,7 @@ __global__ __launch_bounds__(SCAN_T) void scan_emit_kernel(In in, const unsigned
         v[k] = base + k < n ? in.get(img, base + k) : 0u;
         s += v[k];
     }
-    unsigned pos = block_excl_scan(s, sh, nullptr) + bsum[(size_t)img * nblk + blockIdx.x];
+    unsigned pos = svo::block_excl_scan<SCAN_T>(s, s_wave, (unsigned *)nullptr) + bsum[(size_t)img * nblk + blockIdx.x];
     for (int k = 0; k < SCAN_ITEMS; k++)
         if (v[k]) {
             emit(img, base + k, pos, v[k]);
@@ -511,7 +495,7 @@ __global__ __launch_bounds__(64) void sift_orient_kernel(SiftGeom g, const float
     }
     const unsigned long long m = __ballot(peak);
     if (peak) {
-        const int rank = __popcll(m & ((1ull << lane) - 1ull));
+        const int rank = svo::lanes_below(m);
         if (rank < SIFT_MAXPEAK)
             kp.ang[slot * SIFT_MAXPEAK + rank] = ang;
     }

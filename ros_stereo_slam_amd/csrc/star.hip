@@ -15,13 +15,15 @@
 //   star_response_kernel                    a lane per pixel: the star sums the patterns in use need, then the patterns
 //   star_tile_kernel                        a lane per suppression tile: extrema, neighbourhood, size and line tests; a word per
 //                                           tile, and the wavefront's key-point count (ballot + popcount)
-//   star_scan_kernel                        one workgroup per image: exclusive scan of the wavefronts' counts, the total
+//   star_scan_kernel                        one workgroup per image: exclusive scan of the wavefronts' counts (scan_ops.hip.h),
+//                                           the total
 //   star_scatter_kernel                     the tiles again: each key point written at offset + rank inside the wavefront
 // No atomic decides a position: the order of the output is the order of the tiles.
 #include <utility>
 
 #include "svo_internal.h"
 
+#include "scan_ops.hip.h"
 #include "star_plan.hip.h"
 
 namespace {
@@ -293,36 +295,11 @@ __global__ __launch_bounds__(256) void star_scan_kernel(const int *__restrict__ 
                                                         int *__restrict__ counts)
 {
     __shared__ int s_wave[4];
-    const int img = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int *__restrict__ cnt = span_count + (size_t)img * spans;
-    int *__restrict__ off = span_offset + (size_t)img * spans;
-    int carry = 0;
-    for (unsigned b = 0; b < spans; b += 256) {
-        const unsigned i = b + t;
-        const int v = i < spans ? cnt[i] : 0;
-        int incl = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_up(incl, o, 64);
-            incl += lane >= o ? u : 0;
-        }
-        if (lane == 63)
-            s_wave[wave] = incl;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int wt = s_wave[k];
-            before += k < wave ? wt : 0;
-            total += wt;
-        }
-        if (i < spans)
-            off[i] = carry + before + incl - v;
-        carry += total;
-        __syncthreads();
-    }
-    if (t == 0)
-        counts[img] = carry;
+    const int img = blockIdx.x;
+    // spans <= 2^22: w, h <= 16384 and 64 tiles of at least a pixel per span
+    const int total = svo::block_scan_counts<256>(span_count + (size_t)img * spans, span_offset + (size_t)img * spans, (int)spans, s_wave);
+    if (threadIdx.x == 0)
+        counts[img] = total;
 }
 
 // the tiles again: a key point goes to the wavefront's offset + the key points of the lanes below; a tile's maximum before its minimum
@@ -332,14 +309,12 @@ __global__ __launch_bounds__(256) void star_scatter_kernel(const unsigned *__res
                                                            float *xy, float *ksize, float *kresp)
 {
     const unsigned ti = blockIdx.x * 256u + threadIdx.x;
-    const int lane = threadIdx.x & 63;
     const size_t px = (size_t)a.w * a.h;
     const unsigned word = ti < a.tiles ? tile_all[blockIdx.y * (size_t)a.tiles + ti] : 0u;
     const unsigned long long m1 = __ballot((word & 0x10000u) != 0), m2 = __ballot((word & 0x20000u) != 0);
     if (!(word & 0x30000u))
         return;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    int pos = span_offset_all[blockIdx.y * (size_t)spans + (ti >> 6)] + __popcll(m1 & below) + __popcll(m2 & below);
+    int pos = span_offset_all[blockIdx.y * (size_t)spans + (ti >> 6)] + svo::lanes_below(m1) + svo::lanes_below(m2);
     const int step = a.delta + 1;
     const int ty = ti / (unsigned)a.tiles_x, tx = ti - (unsigned)ty * a.tiles_x;
     const int x0 = a.border + tx * step, y0 = a.border + ty * step;

@@ -25,6 +25,7 @@
 
 #include "svo_internal.h"
 #include "fast_atan2.hip.h"
+#include "scan_ops.hip.h"
 
 namespace {
 
@@ -233,7 +234,7 @@ __global__ __launch_bounds__(256) void surf_maxima_kernel(const float *__restric
         base = atomicAdd(count_all + b, __popcll(m));
     base = __shfl(base, __ffsll((long long)m) - 1);
     if (found) {
-        const int at = base + __popcll(m & ((1ull << lane) - 1));
+        const int at = base + svo::lanes_below(m);
         if (at < SURF_MAXCAND) {
             const size_t q = (size_t)b * SURF_MAXCAND + at;
             ka_all[q] = make_float4(val0, ksize, ky, kx);
@@ -349,7 +350,7 @@ __global__ __launch_bounds__(256) void surf_orientation_kernel(const int *__rest
                 }
                 const float wgt = wt.ori[ai + SURF_ORI_RADIUS] * wt.ori[aj + SURF_ORI_RADIUS];
                 const float vx = (float)dx * wgt, vy = (float)dy * wgt;
-                const int at = nangle + __popcll(m & ((1ull << lane) - 1));
+                const int at = nangle + svo::lanes_below(m);
                 X[wave][at] = vx;
                 Y[wave][at] = vy;
                 A[wave][at] = surf_round(fast_atan2_deg(vy, vx));

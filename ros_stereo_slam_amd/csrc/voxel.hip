@@ -12,7 +12,7 @@
 //   3. radix_sort_pairs of (key, index): stable, so a cell's points stand in ascending input index afterwards -- the order
 //      the definition sums in.
 //   4. voxel_head_count_kernel, voxel_scan_blocks_kernel, voxel_rows_kernel: a sorted position whose key differs from its
-//      predecessor's heads a voxel; the scan of the heads is the output row of every position.  The last of the three also
+//      predecessor's heads a voxel; the scan of the heads (scan_ops.hip.h) is the output row of every position.  The last also
 //      gathers the points (and colours) into voxel order through the sorted index, writes the segment starts and scatters
 //      the trace (point_voxel).
 //   5. voxel_mean_kernel: ONE WAVE PER VOXEL.  The wave loads 64 consecutive gathered rows at a time (contiguous floats:
@@ -164,32 +164,19 @@ __global__ __launch_bounds__(vp::BLOCK) void voxel_head_count_kernel(const uint6
     int cnt = 0;
     for (int r = 0; r < vp::TILE / vp::BLOCK; r++)
         cnt += voxel_head(keys, base + r * vp::BLOCK + tid, m) ? 1 : 0;
-    cnt = svo::wave_sum_dpp(cnt);
-    if ((tid & 63) == 0)
-        s_cnt[tid >> 6] = cnt;
-    __syncthreads();
+    int total;
+    svo::waves_before<vp::BLOCK>(svo::wave_sum_dpp(cnt), s_cnt, &total);
     if (tid == 0)
-        blk[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        blk[blockIdx.x] = total;
 }
 
 // exclusive scan of the nblk <= 1024 tile counts in place, one workgroup; *n_out = their total
 __global__ __launch_bounds__(1024) void voxel_scan_blocks_kernel(int *__restrict__ blk, int nblk, int *__restrict__ n_out)
 {
-    __shared__ int s[1024];
-    const int tid = threadIdx.x;
-    const int own = tid < nblk ? blk[tid] : 0;
-    s[tid] = own;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int v = tid >= off ? s[tid - off] : 0;
-        __syncthreads();
-        s[tid] += v;
-        __syncthreads();
-    }
-    if (tid < nblk)
-        blk[tid] = s[tid] - own;
-    if (tid == 1023)
-        *n_out = s[1023];
+    __shared__ int s_wave[16];
+    const int total = svo::block_scan_counts<1024>(blk, blk, nblk, s_wave);   // one chunk
+    if (threadIdx.x == 0)
+        *n_out = total;
 }
 
 // Every sorted position's output row (the inclusive scan of the heads, minus one), in tile order as the radix scatter ranks:
@@ -202,7 +189,7 @@ __global__ __launch_bounds__(vp::BLOCK) void voxel_rows_kernel(const uint64_t *_
                                                                int *__restrict__ point_voxel)
 {
     __shared__ int s_w[4];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x;
     const int c = color ? 6 : 3;
     const int base = blockIdx.x * vp::TILE;
     int run = blk[blockIdx.x];
@@ -210,16 +197,10 @@ __global__ __launch_bounds__(vp::BLOCK) void voxel_rows_kernel(const uint64_t *_
         const int i = base + r * vp::BLOCK + tid;
         const bool head = voxel_head(keys, i, m);
         const unsigned long long bal = __ballot(head);
-        if (lane == 0)
-            s_w[w] = __popcll(bal);
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            before += q < w ? s_w[q] : 0;
-            total += s_w[q];
-        }
-        const int row = run + before + __popcll(bal & ((2ull << lane) - 1ull)) - 1;  // heads up to and including i, minus one
+        int total;
+        const int before = svo::waves_before<vp::BLOCK>((int)__popcll(bal), s_w, &total);
+        // heads up to and INCLUDING i, minus one: the inclusive count is the lanes below plus the lane's own bit
+        const int row = run + before + svo::lanes_below(bal) + (head ? 1 : 0) - 1;
         if (i < n) {
             const int j = vals[i];
             if (i < m) {

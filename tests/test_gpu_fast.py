@@ -122,6 +122,19 @@ def test_tile_seams(ctx):
             assert len(exp[0]) > 0, (w, h)
 
 
+def test_more_spans_than_one_chunk_of_the_scan(ctx):
+    """520 x 512 = 260 spans of 1024 pixels: the scan of the span counts (256 a chunk) takes a second chunk, whose offsets start from
+    the first one's carry; with a budget the count / scan pair runs twice.  Key points lie on both sides of the seam."""
+    w, h = 520, 512
+    assert w * h == 260 * SPAN and 260 > 256
+    img = ff.noise(w, h, 600)
+    for t, nonmax, budget in ((1, True, 0), (10, True, 500)):
+        exp = fn.fast_detect(img, t, nonmax, budget)
+        past = exp[0][:, 1] * w + exp[0][:, 0] >= 256 * SPAN
+        assert past.any() and not past.all()
+        same(ctx.fast_detect([img], t, nonmax, budget)[0], exp, (t, nonmax, budget))
+
+
 # ------------------------------------------------------------------------------------------------------------- capacity
 def raw_detect(ctx, imgs, prm, cap, guard=64):
     """The C call on host arrays with a guard band behind xy and response -> (rc, n, xy, resp) with the bands attached."""

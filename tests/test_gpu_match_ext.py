@@ -121,6 +121,21 @@ def test_radius_equals_the_restatement(ctx, norm):
     assert nonempty > 50
 
 
+def test_radius_with_more_queries_than_one_chunk_of_the_row_scan(ctx):
+    """1025 queries against 8 train rows: the scan of the rows' counts (1024 a chunk) takes a second chunk, whose one row starts at
+    the first chunk's carry.  Train row j is (10 j, 0, 0, 0), query i is (x_i, 0, 0, 0), the radius 12: a row has 0 ... 3 matches."""
+    rng = np.random.default_rng(300)
+    t = np.zeros((8, 4), np.uint8)
+    t[:, 0] = 10 * np.arange(8)
+    q = np.zeros((1025, 4), np.uint8)
+    q[:, 0] = rng.integers(0, 256, 1025)
+    q[-1, 0] = 40                                                   # the row of the second chunk has matches of its own
+    want = mx.radius_match(q, t, 12.0, norm=mn.L2_U8)
+    counts = np.diff(want[0])
+    assert counts.min() == 0 and counts.max() == 3 and set(counts) == {0, 1, 2, 3} and want[0][1024] > 0 and counts[1024] == 3
+    same_csr(ctx.radius_match(q, t, 12.0, norm=mn.L2_U8), want, "1025 x 8")
+
+
 @NORMS
 def test_gated_equals_the_restatement(ctx, norm):
     rng = np.random.default_rng(300 + norm)

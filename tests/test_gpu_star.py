@@ -109,6 +109,21 @@ def test_tile_columns_256_and_257(ctx):
     assert total > 0
 
 
+def test_more_spans_than_one_chunk_of_the_scan(ctx):
+    """The default parameters (csrc/star_plan.hip.h: border 69, tiles of 3 x 3 pixels, 64 tiles a span) on 523 x 522: 129 x 128 =
+    16 512 tiles, the smallest count above the 256 x 64 = 16 384 that one chunk of the span scan holds (128 x 128 is the 16 384
+    itself, 522 x 522) -- 258 spans, so the offsets of the last two start from the first chunk's carry."""
+    w, h = 523, 522
+    assert sn.layout(w, h, 45) == (9, 13, 69)
+    tx, ty = -(-(w - 2 * 69) // 3), -(-(h - 2 * 69) // 3)
+    assert (tx, ty) == (129, 128) and tx * ty > 256 * 64 >= (tx - 1) * ty
+    img = smooth(w, h, 60)
+    exp = want(img, {})
+    tile = ((exp[0][:, 1].astype(int) - 69) // 3) * tx + (exp[0][:, 0].astype(int) - 69) // 3
+    assert (tile >= 256 * 64).any() and (tile < 256 * 64).any()
+    same(ctx.star_detect([img], {})[0], exp, "523x522")
+
+
 @pytest.mark.parametrize("nonmax", [1, 3, 5, 7])
 def test_suppression_sizes(ctx, nonmax):
     n = 0

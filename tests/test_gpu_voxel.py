@@ -109,6 +109,17 @@ def test_one_voxel_at_the_chunk_seams(ctx, n):
     check_against_restatement(ctx, xyz, vf.colours(n, 3), 1.0, combos=[(True, True, False), (False, True, True)])
 
 
+def test_more_tiles_than_one_wave_of_the_tile_scan(ctx):
+    """64 x 4096 + 1 points, one per voxel along a line: 65 tiles whose head counts are all non-zero, so the scan of the tile counts
+    passes a wave's total on to the next wave"""
+    n = 64 * 4096 + 1
+    xyz = np.zeros((n, 3), np.float32)
+    xyz[:, 0] = np.arange(n, dtype=np.float32)
+    exp = vn.voxel_downsample(xyz, 1.0)
+    assert len(exp[0]) == n and np.array_equal(exp[2], np.arange(n))
+    check_against_restatement(ctx, xyz, None, 1.0, expected={False: exp[:4]}, combos=[(False, True, False), (False, False, True)])
+
+
 def test_wrapper_returns_the_same(ctx):
     import torch
 
