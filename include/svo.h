@@ -659,6 +659,43 @@ int svo_recover_pose(svo_ctx *ctx, const double *E9, const float *p1, const floa
  * largest magnitude positive, and u3 = u1 x u2, v3 = v1 x v2 (det +1).  Host only.                 */
 int svo_decompose_essential(const double *E9, double *R1, double *R2, double *t);
 
+/* ---- planar two-view geometry: cv::findHomography (RANSAC), cv::decomposeHomographyMat and the pose they give ---- */
+/* The minimal solver on nsamples independent 4-samples: x1 / x2 nsamples x 4 x 2 doubles, x2 ~ H x1.  checkSubset first
+ * (no three of the four points collinear in either image, every triple turning the same way in both), then the 8 x 8
+ * system with h8 = 1 in normalised coordinates.  H_out: nsamples x 9, row-major, h8 = 1; ok: nsamples ints, 0 for a
+ * rejected or singular sample, whose slot is zero.  Arrays follow `mem`.  The solver's choices: DESIGN.md section 10r. */
+int svo_homography_4pt(svo_ctx *ctx, const double *x1, const double *x2, int nsamples, double *H_out, int *ok, int mem);
+/* cv::findHomography(p1, p2, RANSAC, threshold, mask, max_iters, confidence) for nprob (1..16) problems: problem k is
+ * pairs offsets[k] .. offsets[k+1]-1 of p1 / p2 (float x, y pixels); offsets (nprob + 1 ints) are HOST memory always.
+ * OpenCV's defaults: threshold 3.0, max_iters 2000 (here 1..20000), confidence 0.995.  4-samples are drawn like
+ * svo_pnp_ransac's, keyed by (seed, iteration); a sample that checkSubset rejects is drawn again at most 8 times, after
+ * which its iteration scores no model.  The float forward transfer error is tested against threshold^2; first-best-wins
+ * with the adaptive bound.  The winner is refitted over its inliers (normalised DLT) and polished by at most ten
+ * Levenberg-Marquardt steps on h0 .. h7 in double.  mask: a byte per pair (1 = inlier), the loop's, not recomputed after
+ * the polish.  Per problem (optional, following `mem`): H_out 9 doubles (h8 = 1), inlier_count, iters_run.  Below four
+ * pairs, or when every sample is rejected: count 0, mask zero, H_out zero.  Exactly four: the minimal solution, mask all
+ * ones, iters_run 0.  A batch gives the same bits as its problems one call at a time.                                */
+int svo_find_homography(svo_ctx *ctx, const float *p1, const float *p2, const int *offsets, int nprob, double threshold,
+                        double confidence, int max_iters, uint64_t seed, uint8_t *mask, double *H_out, int *inlier_count,
+                        int *iters_run, int mem);
+/* cv::decomposeHomographyMat.  Hn = K^-1 H K (K4 = fx, fy, cx, cy) with det Hn > 0, scaled so that its middle singular
+ * value is 1; then Hn = R + t n^T.  Up to four (R, t / d, n) with det R = +1 and |n| = 1 in the order (Ra, ta, na),
+ * (Ra, -ta, -na), (Rb, tb, nb), (Rb, -tb, -nb): of (t, n) and (-t, -n) the first has nz > 0 (nz = 0: ny > 0, then
+ * nx > 0); `a` is the solution whose first normal is the larger by (nz, ny, nx).  When the largest and smallest
+ * eigenvalues of Hn^T Hn differ by at most 1e-8 (a pure rotation): one solution, t = 0, n = (0, 0, 1).  R: 4 x 9,
+ * t, n: 4 x 3 (unused slots zero); *nsol: 0 (singular H), 1 or 4.  Host only.                                        */
+int svo_decompose_homography(const double *H9, const double *K4, double *R, double *t, double *n, int *nsol);
+/* The pose of a plane-induced homography for nprob (1..16) problems laid out as svo_find_homography's; H9: nprob x 9,
+ * K4: nprob x 4 (host memory).  Each candidate of svo_decompose_homography is scored by svo_recover_pose's test:
+ * every pair is triangulated with [R | t / |t|]; it counts when Q2 Q3 > 0, its depth in camera 1 is below
+ * distance_thresh and its depth in camera 2 is in (0, distance_thresh); a non-null mask_inout is ANDed in and receives
+ * the chosen candidate's mask.  The first candidate with the largest count wins.  R9 (nprob x 9), t3 (nprob x 3: unit
+ * norm, or zero for the pure rotation), n3 (nprob x 3) and good4 (optional, nprob x 4: every candidate's count, so that a
+ * tie between two candidates shows) follow `mem` like the point arrays.  A singular H gives zeros.                 */
+int svo_homography_pose(svo_ctx *ctx, const double *H9, const float *p1, const float *p2, const int *offsets, int nprob,
+                        const double *K4, double distance_thresh, uint8_t *mask_inout, double *R9, double *t3, double *n3,
+                        int *good4, int mem);
+
 /* ---- descriptor matching: cv::BFMatcher(normType, false).knnMatch + the ratio test ----------------------------------
  * The block the reference runs wherever it pairs features outside the dense grid (src/triangulation.cpp:120-133, the
  * DENSE_FLAG == false branch of stereoTriangulate; src/StereoCV.cpp:77-88,136-147; src/bundleAdjust.cpp:269-271):

@@ -310,8 +310,16 @@ class StereoProcess {
     // in one svo_sift_extract_batch call, BFMatcher().knnMatch(desc1, desc2, 2) = svo_knn_match(SVO_MATCH_L2_F32, k 2), the
     // 0.8 ratio test = svo_ratio_pairs, then FmatThresholding and the same tail.  siftCapacity bounds the key points an
     // image may return (retainBest keeps ties, so it can exceed the budget); beyond it the call throws SVO_ERR_CAPACITY.
+    //
+    // HOMOGRAPHY_FLAG = true (opt-in): for a scene that is one plane (a road, a wall at a loop closure), where F and E are
+    // degenerate, or for a pure rotation -- after the F filter, svo_find_homography (homographyThreshold px, 0.995, 2000)
+    // in findEssentialMat's place and svo_homography_pose in recoverPose's; the plane's unit normal (first camera's frame)
+    // lands in planeNormal; a pure rotation gives monoT = 0.  The rest of the member is unchanged.
     double monoR[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, monoT[3] = {0, 0, 0};
     std::vector<Point2f> monoPts1, monoPts2;
+    bool HOMOGRAPHY_FLAG = false;
+    double homographyThreshold = 3.0;
+    double planeNormal[3] = {0, 0, 0};
     bool SIFT_FLAG = false;
     int siftFeaturesMono = 10000, siftCapacity = 40000;
     // detector->detect + compute of SIFT::create(nfeatures) on one image: KeyPoint fields as cv fills them, desc: 128
@@ -347,14 +355,25 @@ class StereoProcess {
         const int offsets[2] = {0, n};
         const double K4[4] = {focal_x, focal_y, cx, cy};
         std::vector<uint8_t> mask(n > 0 ? n : 1);
-        double E[90];
-        int nmodels = 0;
-        check(svo_find_essential(ctx(), fp(pt1), fp(pt2), offsets, 1, K4, 1.0, 0.99, 1000, slam_.ransacSeed + 4, mask.data(),
-                                 E, &nmodels, nullptr, nullptr, SVO_MEM_HOST));
-        if (nmodels < 1)
-            throw std::runtime_error("monocularTriangulate: no essential matrix");
-        int good = 0;
-        check(svo_recover_pose(ctx(), E, fp(pt1), fp(pt2), offsets, 1, K4, 50.0, nullptr, monoR, monoT, &good, SVO_MEM_HOST));
+        if (HOMOGRAPHY_FLAG) {
+            double H[9];
+            int count = 0;
+            check(svo_find_homography(ctx(), fp(pt1), fp(pt2), offsets, 1, homographyThreshold, 0.995, 2000, slam_.ransacSeed + 4,
+                                      mask.data(), H, &count, nullptr, SVO_MEM_HOST));
+            if (count < 4)
+                throw std::runtime_error("monocularTriangulate: no homography");
+            check(svo_homography_pose(ctx(), H, fp(pt1), fp(pt2), offsets, 1, K4, 50.0, nullptr, monoR, monoT, planeNormal, nullptr,
+                                      SVO_MEM_HOST));
+        } else {
+            double E[90];
+            int nmodels = 0;
+            check(svo_find_essential(ctx(), fp(pt1), fp(pt2), offsets, 1, K4, 1.0, 0.99, 1000, slam_.ransacSeed + 4, mask.data(),
+                                     E, &nmodels, nullptr, nullptr, SVO_MEM_HOST));
+            if (nmodels < 1)
+                throw std::runtime_error("monocularTriangulate: no essential matrix");
+            int good = 0;
+            check(svo_recover_pose(ctx(), E, fp(pt1), fp(pt2), offsets, 1, K4, 50.0, nullptr, monoR, monoT, &good, SVO_MEM_HOST));
+        }
         const double K[9] = {focal_x, 0, cx, 0, focal_y, cy, 0, 0, 1};
         double P1[12], P2[12];
         for (int r = 0; r < 3; r++)

@@ -1710,6 +1710,86 @@ def decompose_essential(E):
     return R1, R2, t
 
 
+# ---- planar two-view geometry: findHomography / decomposeHomographyMat and the pose they give ---------------------
+_NO_K = (1.0, 1.0, 0.0, 0.0)
+
+
+@_ctx_method
+def homography_4pt(self, x1, x2):
+    """``svo_homography_4pt``: the minimal solver on s 4-samples (s x 4 x 2 each, x2 ~ H x1) -> (H: s x 3 x 3 with h8 = 1,
+    zero where not ok; ok: s ints)."""
+    x1 = np.ascontiguousarray(x1, np.float64).reshape(-1, 4, 2)
+    x2 = np.ascontiguousarray(x2, np.float64).reshape(-1, 4, 2)
+    assert x1.shape == x2.shape
+    s = x1.shape[0]
+    H = np.zeros((s, 3, 3))
+    ok = np.zeros(s, np.int32)
+    _check(self.lib.svo_homography_4pt(self._h, _ptr(x1), _ptr(x2), s, _ptr(H), _ptr(ok), MEM_HOST))
+    return H, ok
+
+
+@_ctx_method
+def find_homography(self, p1, p2, threshold=3.0, confidence=0.995, max_iters=2000, seed=0):
+    """``svo_find_homography`` (cv::findHomography, RANSAC): one problem -- p1, p2 (n x 2 pixels) -- or lists of up to 16
+    problems.  numpy arrays, or device tensors whose masks come back as device tensors.  Per problem -> (H: 3 x 3 with
+    h8 = 1, zero without a model; mask: n uint8; inlier count; iterations run)."""
+    a, b, offsets, _, single, dev = _problem_set(p1, p2, _NO_K)
+    nprob, total = len(offsets) - 1, int(offsets[-1])
+    args = (C.c_double(threshold), C.c_double(confidence), int(max_iters), C.c_uint64(seed))
+    if dev:
+        import torch
+
+        mask = torch.empty(max(total, 1), dtype=torch.uint8, device=a.device)
+        H = torch.zeros((nprob, 9), dtype=torch.float64, device=a.device)
+        ints = torch.zeros((2, nprob), dtype=torch.int32, device=a.device)
+        torch.cuda.synchronize(a.device)
+        _check(self.lib.svo_find_homography(self._h, _ptr(a), _ptr(b), _ptr(offsets), nprob, *args, _ptr(mask), _ptr(H),
+                                            _ptr(ints[0]), _ptr(ints[1]), MEM_DEVICE))
+        _check(self.lib.svo_ctx_sync(self._h))
+        H, ints = H.cpu().numpy(), ints.cpu().numpy()
+    else:
+        mask = np.zeros(max(total, 1), np.uint8)
+        H = np.zeros((nprob, 9))
+        ints = np.zeros((2, nprob), np.int32)
+        _check(self.lib.svo_find_homography(self._h, _ptr(a), _ptr(b), _ptr(offsets), nprob, *args, _ptr(mask), _ptr(H),
+                                            _ptr(ints[0]), _ptr(ints[1]), MEM_HOST))
+    out = [(H[k].reshape(3, 3), mask[offsets[k]:offsets[k + 1]], int(ints[0, k]), int(ints[1, k])) for k in range(nprob)]
+    return out[0] if single else out
+
+
+@_ctx_method
+def homography_pose(self, H, p1, p2, K, distance_thresh=50.0, mask=None):
+    """``svo_homography_pose``: one problem -- H (3 x 3), p1, p2 (n x 2 pixels), K = (fx, fy, cx, cy), mask (n, optional:
+    ANDed in) -- or lists of up to 16.  Host arrays -> per problem (R, t (3,: unit norm, zero for a pure rotation), n (3,),
+    good4 (the four candidates' counts), the chosen candidate's mask)."""
+    a, b, offsets, K4, single, dev = _problem_set(p1, p2, K)
+    assert not dev, "homography_pose takes host arrays"
+    nprob, total = len(offsets) - 1, int(offsets[-1])
+    Hs = [H] if single else list(H)
+    assert len(Hs) == nprob
+    H9 = np.ascontiguousarray(np.concatenate([np.asarray(h, np.float64).reshape(9) for h in Hs]))
+    masks = [mask] if single else (list(mask) if mask is not None else [None] * nprob)
+    m = np.ones(max(total, 1), np.uint8)
+    for k, mk in enumerate(masks):
+        if mk is not None:
+            m[offsets[k]:offsets[k + 1]] = np.asarray(mk, np.uint8).reshape(-1)
+    R, t, n, good4 = np.zeros((nprob, 3, 3)), np.zeros((nprob, 3)), np.zeros((nprob, 3)), np.zeros((nprob, 4), np.int32)
+    _check(self.lib.svo_homography_pose(self._h, _ptr(H9), _ptr(a), _ptr(b), _ptr(offsets), nprob, _ptr(K4),
+                                        C.c_double(distance_thresh), _ptr(m), _ptr(R), _ptr(t), _ptr(n), _ptr(good4), MEM_HOST))
+    out = [(R[k], t[k], n[k], [int(g) for g in good4[k]], m[offsets[k]:offsets[k + 1]].copy()) for k in range(nprob)]
+    return out[0] if single else out
+
+
+def decompose_homography(H, K):
+    """``svo_decompose_homography`` (cv::decomposeHomographyMat, host) -> list of (R, t, n): none, one (a pure rotation)
+    or four, in the header's order."""
+    h = np.ascontiguousarray(H, np.float64).reshape(9)
+    K4 = np.ascontiguousarray(K, np.float64).reshape(4)
+    R, t, n, nsol = np.zeros((4, 3, 3)), np.zeros((4, 3)), np.zeros((4, 3)), C.c_int(0)
+    _check(load().svo_decompose_homography(_ptr(h), _ptr(K4), _ptr(R), _ptr(t), _ptr(n), C.byref(nsol)))
+    return [(R[k], t[k], n[k]) for k in range(nsol.value)]
+
+
 # ---- descriptor matching: BFMatcher::knnMatch + the ratio test (src/triangulation.cpp:120-133) ----------------------
 MATCH_L2_F32, MATCH_L2_U8, MATCH_HAMMING = 0, 1, 2
 

@@ -1,5 +1,5 @@
-// ransac_common.hip.h -- device helpers shared by the three RANSAC kernel files: fransac.hip (F matrix, 7-point samples),
-// pnp.hip (PnP, 5) and essential.hip (E matrix, 5): the counter-based generator, the draw of a sample, the iteration bound and
+// ransac_common.hip.h -- device helpers shared by the four RANSAC kernel files: fransac.hip (F matrix, 7-point samples),
+// pnp.hip (PnP, 5), essential.hip (E matrix, 5) and homography.hip (H, 4): the counter-based generator, the draw of a sample, the iteration bound and
 // the replay of the sequential loop.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -197,6 +197,7 @@ struct svo_ctx {
     // registration call
     DevBuf icp_work;
     // essential.hip: normalised points, the RANSAC's per-iteration models / counts / state, recoverPose's candidate masks
+    // (homography.hip's calls lay out the same buffer anew for their own models / counts / state / candidate masks)
     DevBuf ess;
     // sift.hip, brief.hip, surf.hip (feature_batch.hip.h, integral_scan.hip.h): the staged host images of a call (or surf.hip's
     // gathered grey device images), and the integral images of a batch with surf.hip's grey planes behind them.  One of each for
