@@ -5,7 +5,8 @@
 // (PyrLKtrackFrame2Frame, method 8 == FM_RANSAC, 1 px).  Only the mask is consumed there.
 //
 // Structure (all on the context's stream, no host round trip): ONE kernel per phase,
-//   one WAVEFRONT per RANSAC iteration (a wave of the second phase takes every 64th):
+//   one WORKGROUP per RANSAC iteration (a workgroup of the second phase takes every 64th); a single wave in the lock-step
+//   build's second phase, TWO waves in its first, four for a lone problem -- wave 0 solves, all share the scoring pass:
 //     solve   lane 0: counter-based 7-sample (collinear samples re-drawn), 7x9 Gauss-Jordan in
 //             LDS, cubic det(l*F1 + (1-l)*F2) = 0, up to three unit-norm models (LDS + HBM);
 //     score   all lanes, model after model: the N correspondences strided over the 64 lanes,
@@ -17,15 +18,22 @@
 //             algorithm's, and -- once the loop has ended -- writes the model and the counts;
 //     finish  the mask of the winning model and the order-preserving compaction of the payload
 //             arrays by it.
-// Two phases (iterations [0,64) and [64,max)), a launch each.  Who finishes:
+// Two phases, a launch each: iterations [0,A) and [A,max), A = 64 for a lone problem and 32 for the lock-step build.  Either
+// first launch has 64 waves per problem; the lock-step one spends them on half the iterations, two waves each: at VO inlier
+// ratios the sequential loop ends after 4 .. 16 iterations, so most of the 64 scoring passes were never looked at, and the
+// launch lasts as long as its longest wave (solve + up to three scoring passes).  The second phase neither solves nor scores
+// an iteration at or above the bound the first phase's replay left (the bound only falls).  The replay is the sequential
+// loop, so no answer depends on A or on the dealing of the pairs to waves; SVO_FR_LEAN_WAVES=1 (read once) selects the
+// single-wave first launch of 64 iterations, for A/B and tests.  (Four waves and 16 iterations lost what two and 32 gained:
+// DESIGN.md 6.2.)  Who finishes:
 //   * the loop ended in the first phase (the common case at VO inlier ratios: 0.99 confidence, 85%
-//     inliers -> 12 iterations) and a launch follows: the first phase's last workgroup marks the
+//     inliers -> 12 iterations; below about 75% it runs past 32) and a launch follows: the first phase's last workgroup marks the
 //     state "finish pending" (RansacState::pad) and leaves; ALL workgroups of the second launch
 //     -- which had nothing to do in this case -- share the finish (fr_wide_finish): blocks of 64
 //     consecutive pairs, a pair per lane, `kept` and the number of kept pairs before it read from
 //     the winner's bit plane alone.  No error is evaluated again, no ticket is taken and no
 //     workgroup waits for another;
-//   * everything else -- the loop runs on into the second phase, a call of at most 64 iterations
+//   * everything else -- the loop runs on into the second phase, a call of no more iterations than the first phase
 //     (one launch), fewer than 15 pairs (fr_small_case), a launch in which a workgroup found the
 //     gate closed -- the workgroup with the last ticket finishes alone, evaluating the winner's
 //     errors again (the tail of fr_ransac_kernel).
@@ -41,8 +49,12 @@ using namespace svo;
 namespace {
 
 constexpr int M = 7;
-constexpr int PHASE_A = 64;
-constexpr int PHASE_WAVES = 64;  // waves per problem and phase; a wave takes every PHASE_WAVES-th iteration
+constexpr int PHASE_WAVES = 64;  // waves per problem and phase; a workgroup of the second phase takes every PHASE_WAVES-th iteration
+constexpr int PHASE_A = 64;  // iterations of a lone problem's first phase (four waves each: the chip to itself)
+// The lock-step build's first launch keeps PHASE_WAVES waves per problem whatever their grouping: its first phase is
+// PHASE_WAVES / (waves per workgroup) iterations long.
+constexpr int NW_LEAN = 2;  // waves that share an iteration of the lock-step build's first phase (SVO_FR_LEAN_WAVES=1: one)
+constexpr int phase_a_lean(int nw) { return PHASE_WAVES / nw; }
 
 // One F-matrix RANSAC problem as the kernels see it; a launch may carry several (blockIdx.y picks
 // the job) -- the chunks of a context that run in lock step (svo_vo_run_chunks).
@@ -592,19 +604,21 @@ template <int NW> __device__ void fr_wide_finish(const FrJob &job, const RansacS
 
 // One phase of the RANSAC loop: iterations [it0, min(it1_cap, max_iters)), one wave per iteration (see the
 // file header).  `final_phase`: no launch follows, so the last wave finishes the problem whatever the state.
-// LEAN: the lock-step groups -- single-wave workgroups capped at 96 VGPRs (with spills), so that a wave starts beside
-// four tracking waves of another context on its SIMD.  !LEAN: a lone problem has the chip to itself, its 64
+// LEAN: the lock-step groups -- workgroups of NWL waves (at most one per SIMD) capped at 96 VGPRs (with spills), so that a
+// workgroup starts beside four tracking waves of another context on every SIMD (five waves per SIMD in all, hence the
+// second launch bound).  !LEAN: a lone problem has the chip to itself, its 64
 // iterations would leave 15 of 16 SIMDs idle: FOUR waves per iteration (wave 0 solves, all four share the scoring
 // pass, and the finishing workgroup's four waves share the mask / compaction pass), 128-VGPR build.
 // TAIL: the instantiation the LAST launch of a call uses.  It also carries cv::findFundamentalMat's behaviour below 15
 // pairs (fr_small_case), so that the kernel of the first 64 iterations -- the one on every frame's path -- stays as it was,
 // and the wide finish of a problem whose loop ended in the first phase (fr_wide_finish: every wave of the launch, in both
 // builds -- the bit plane's layout does not depend on the number of waves that scored).
-template <bool LEAN, bool TAIL>
-__global__ __launch_bounds__(LEAN ? 64 : 256, LEAN ? 5 : 4) void fr_ransac_kernel(FrBatchN<LEAN ? SVO_LK_MAX_JOBS : 1> batch, int it0, int it1_cap,
-                                                                                   int final_phase)
+template <bool LEAN, bool TAIL, int NWL = 1>
+__global__ __launch_bounds__(LEAN ? 64 * NWL : 256, LEAN ? 5 : 4) void fr_ransac_kernel(FrBatchN<LEAN ? SVO_LK_MAX_JOBS : 1> batch, int it0,
+                                                                                         int it1_cap, int final_phase)
 {
-    constexpr int NW = LEAN ? 1 : 4;  // waves per workgroup
+    constexpr int NW = LEAN ? NWL : 4;  // waves per workgroup
+    static_assert(NW == 1 || NW == 2 || NW == 4, "at most one wave per SIMD");
     svo_chain_priority();
     const FrJob &job = batch.j[blockIdx.y];
     // The gate (VoChain::kf / ::run) may be cleared on ANOTHER stream while this launch is being dispatched (the pipelined
@@ -623,7 +637,8 @@ __global__ __launch_bounds__(LEAN ? 64 : 256, LEAN ? 5 : 4) void fr_ransac_kerne
     const int n_host = job.n_host;
     const int *__restrict__ d_n = job.d_n;
     const int max_iters = job.max_iters;
-    const int it1 = it1_cap < max_iters ? it1_cap : max_iters;
+    const int it_end = it1_cap < max_iters ? it1_cap : max_iters;
+    int it1 = it_end;  // the iterations this launch solves and scores end here, the replay at it_end
     RansacState *st = job.st;
     double *__restrict__ Fm = job.Fm;
     int *__restrict__ nmodels = job.nmodels;
@@ -646,6 +661,10 @@ __global__ __launch_bounds__(LEAN ? 64 : 256, LEAN ? 5 : 4) void fr_ransac_kerne
             fr_wide_finish<NW>(job, *st, n);
         return;
     }
+    // The bound only ever falls, so the replay never looks at an iteration at or above the bound the earlier phase left:
+    // those are neither solved nor scored (the same value in every workgroup: the state is the previous launch's).
+    if (TAIL && it0 > 0 && st->niters < it1)
+        it1 = st->niters;
     // a first phase with a successor keeps the ballots of its scoring pass: should the loop end here, the successor's waves
     // finish from the winner's
     const bool keep_planes = !TAIL && it0 == 0 && !final_phase;
@@ -755,7 +774,7 @@ __global__ __launch_bounds__(LEAN ? 64 : 256, LEAN ? 5 : 4) void fr_ransac_kerne
     }
     if (threadIdx.x == 0) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // other waves' counts, not this CU's stale lines
-        RansacState r = ransac_replay<3>(st, it0 == 0 ? 1 : 0, it1, max_iters, n, job.confidence, nmodels, counts, M);
+        RansacState r = ransac_replay<3>(st, it0 == 0 ? 1 : 0, it_end, max_iters, n, job.confidence, nmodels, counts, M);
         r.pad = keep_planes && r.done ? FINISH_PENDING : 0;  // every workgroup was due: the winner's plane is whole
         *st = r;
         s_state = r;
@@ -851,18 +870,24 @@ int svo_launch_fransac_batch(svo_ctx *ctx, int n_jobs, const svo_fransac_job *jo
         svo_set_error("fransac: at most %d jobs per launch", SVO_LK_MAX_JOBS);
         return SVO_ERR_ARG;
     }
-    int it_max = 1, cap_max = 0;
+    int it_max = 1, cap_max = 0, n_live = 0;
     for (int k = 0; k < n_jobs; k++) {
         const int mi = jobs[k].max_iters < 1 ? 1 : jobs[k].max_iters;
         it_max = mi > it_max ? mi : it_max;
         cap_max = jobs[k].cap > cap_max ? jobs[k].cap : cap_max;
+        n_live += jobs[k].cap > 0 ? 1 : 0;
     }
+    // waves per workgroup of the lock-step build's first launch; SVO_FR_LEAN_WAVES=1 is the single-wave form of 64 iterations
+    // (for A/B and tests: the answer does not depend on it).  Read once; the kernels are separate instantiations.
+    static const int nw_env = getenv("SVO_FR_LEAN_WAVES") ? atoi(getenv("SVO_FR_LEAN_WAVES")) : NW_LEAN;
+    const int nw_lean = nw_env == 1 ? 1 : NW_LEAN;
+    const int phase_a = n_live > 1 ? phase_a_lean(nw_lean) : PHASE_A;
     const int it_ws = it_max < 304 ? 304 : it_max;  // the least-median branch runs 300 iterations whatever max_iters says
     const size_t f_stride = (size_t)it_ws * 30, i_stride = ((size_t)it_ws * 4 + 32 + 15) / 16 * 16;
     // the first phase's bit planes (FrJob::planes), behind the models in w_a: they live from the first launch to the second,
     // as Fm does; a call of one launch keeps none
-    const int plane_words = it_max > PHASE_A ? (cap_max + 255) / 256 * 4 : 0;
-    const size_t p_stride = (size_t)PHASE_A * 3 * plane_words;
+    const int plane_words = it_max > phase_a ? (cap_max + 255) / 256 * 4 : 0;
+    const size_t p_stride = (size_t)phase_a * 3 * plane_words;
     int rc;
     if ((rc = ctx->w_a.ensure((f_stride * sizeof(double) + p_stride * sizeof(unsigned long long)) * n_jobs)) ||
         (rc = ctx->w_b.ensure(i_stride * sizeof(int) * n_jobs)))
@@ -914,7 +939,7 @@ int svo_launch_fransac_batch(svo_ctx *ctx, int n_jobs, const svo_fransac_job *jo
     for (int k = nb; k < SVO_LK_MAX_JOBS; k++)
         batch.j[k] = batch.j[0];
     ScopedKernelTime tm(ctx, SVO_K_FRANSAC);
-    const int bounds[3] = {0, it_max < PHASE_A ? it_max : PHASE_A, it_max};
+    const int bounds[3] = {0, it_max < phase_a ? it_max : phase_a, it_max};
     bool any_small = false;
     for (int k = 0; k < nb; k++)
         any_small |= batch.j[k].cv_small != 0;
@@ -925,6 +950,8 @@ int svo_launch_fransac_batch(svo_ctx *ctx, int n_jobs, const svo_fransac_job *jo
         if (nb > 1) {
             if (tail)
                 hipLaunchKernelGGL((fr_ransac_kernel<true, true>), dim3(waves, nb), dim3(64), 0, ctx->stream, batch, it0, it1, fin);
+            else if (nw_lean == NW_LEAN)
+                hipLaunchKernelGGL((fr_ransac_kernel<true, false, NW_LEAN>), dim3(waves, nb), dim3(64 * NW_LEAN), 0, ctx->stream, batch, it0, it1, fin);
             else
                 hipLaunchKernelGGL((fr_ransac_kernel<true, false>), dim3(waves, nb), dim3(64), 0, ctx->stream, batch, it0, it1, fin);
         } else {
@@ -934,8 +961,8 @@ int svo_launch_fransac_batch(svo_ctx *ctx, int n_jobs, const svo_fransac_job *jo
                 hipLaunchKernelGGL((fr_ransac_kernel<false, false>), dim3(waves, nb), dim3(256), 0, ctx->stream, one, it0, it1, fin);
         }
     };
-    // two phases (iterations 0..63, 64..max); the LAST launch of the call is the TAIL instantiation, which also carries the
-    // small-sample branch.  A call of at most 64 iterations whose jobs want that branch gets an (empty) tail launch for it.
+    // two phases (iterations below phase_a, phase_a..max); the LAST launch of the call is the TAIL instantiation, which also carries the
+    // small-sample branch.  A call of at most phase_a iterations whose jobs want that branch gets an (empty) tail launch for it.
     const bool two = bounds[2] > bounds[1];
     launch(bounds[0], bounds[1], bounds[1] - bounds[0] < PHASE_WAVES ? bounds[1] - bounds[0] : PHASE_WAVES, !two && !any_small);
     if (two)
@@ -980,6 +1007,7 @@ extern "C" int svo_selftest_fransac_gate(svo_ctx *ctx, const float *d_p1, const 
     int rc;
     if ((rc = ctx->s_g.ensure(sizeof(int) * PHASE_WAVES)))
         return rc;
+    static_assert(phase_a_lean(NW_LEAN) <= PHASE_WAVES && PHASE_A <= PHASE_WAVES, "a gate slot for every workgroup of either launch");
     int h_gate[PHASE_WAVES];
     for (int b = 0; b < PHASE_WAVES; b++)
         h_gate[b] = (b & 1) ? 0 : 1;
