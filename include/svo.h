@@ -979,6 +979,41 @@ int svo_fast_detect_batch(svo_ctx *ctx, const uint8_t *const *images, int n_imag
 int svo_fast_anms_batch(svo_ctx *ctx, const uint8_t *const *images, int n_images, int w, int h, int c,
                         const svo_fast_params *prm, int num_to_keep, int cap, float *xy, float *response, int *n, int mem);
 
+/* ---- goodFeaturesToTrack: cv::goodFeaturesToTrack / GFTTDetector (Shi-Tomasi min-eigenvalue or Harris corners) ----------------
+ * The algorithm is the one tests/gftt_numpy.py states, points G1 ... G13.  Grey is the image itself (c = 1)
+ * or cvtColor's integer weights on B, G, R (c = 3).  The corner measure is cornerMinEigenVal / cornerHarris with a 3 x 3 Sobel and a
+ * block_size x block_size window, float arithmetic, nothing fused; corners are the 3 x 3 local maxima (plateaus whole) above
+ * quality_level times the largest measure of the image -- of the pixels with a non-zero mask byte when a mask is given --, one
+ * pixel inside the border, ordered by measure descending and row-major index descending among equals; min_distance >= 1 keeps, in
+ * that order, the corners with no kept corner closer than min_distance (exactly the sequential greedy selection); max_corners > 0
+ * keeps the first max_corners of them.
+ *
+ * svo_gftt_detect_batch: n_images (1 ... 16) images of one size, w x h x c bytes each; images: a host array of host or device
+ * pointers according to mem; masks: NULL, or a host array of n_images pointers, each NULL or w x h bytes following mem; xy /
+ * response hold n_images x cap entries, image i's at i * cap (response may be NULL), in acceptance order; response: the measure;
+ * n: HOST ints in both modes.  w < 3 or h < 3 is legal and yields no corners.  SVO_ERR_ARG (nothing is written): null ctx / images /
+ * an image / prm / xy / n, xy, response or n not 4-byte aligned, c not 1 or 3, n_images outside 1 ... 16, cap < 1, w or h below 1 or
+ * above 16384, more than 2^24 interior pixels, (w - 2)(h - 2), in the images of one call (the candidate lists and the sort are
+ * sized to that bound), block_size not odd in 3 ... 31, quality_level not in (0, 1] or NaN, negative or NaN min_distance, with
+ * use_harris a k that is not finite as a float, mem neither SVO_MEM_HOST nor SVO_MEM_DEVICE.  SVO_ERR_CAPACITY: an image has more
+ * than cap corners -- every n[i] holds the true count and the first min(n[i], cap) corners of each image are valid; nothing is
+ * written past cap.
+ *
+ * svo_gftt_response: the measure of every pixel before thresholding, w x h floats following mem (any w, h >= 1).            */
+typedef struct svo_gftt_params {
+    int max_corners;      /* 1000; <= 0 = all */
+    int block_size;       /* 3 */
+    int use_harris;       /* 0 */
+    int pad;              /* 0 */
+    double quality_level; /* 0.01 */
+    double min_distance;  /* 1.0 */
+    double k;             /* 0.04 */
+} svo_gftt_params;
+void svo_gftt_default_params(svo_gftt_params *p);
+int svo_gftt_detect_batch(svo_ctx *ctx, const uint8_t *const *images, const uint8_t *const *masks, int n_images, int w, int h, int c,
+                          const svo_gftt_params *prm, int cap, float *xy, float *response, int *n, int mem);
+int svo_gftt_response(svo_ctx *ctx, const uint8_t *image, int w, int h, int c, const svo_gftt_params *prm, float *eig, int mem);
+
 /* ---- Star (CenSurE): xfeatures2d::StarDetector::create()->detect, the detector of the commented pair above
  * visualSLAM::stereoTriangulate (src/triangulation.cpp:79-80), with BriefDescriptorExtractor as its descriptor --------------------
  * The algorithm is the one tests/star_numpy.py states.  Grey is the image itself (c = 1) or cvtColor's

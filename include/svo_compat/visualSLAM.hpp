@@ -57,6 +57,13 @@ class visualSLAM {
     bool FAST_FLAG = false;
     int fastThreshold = 1;
     int fastKeep = 0;
+    // with DENSE_FLAG == true and FAST_FLAG == false: true = the reference points of stereoTriangulate come from
+    // gfttKeypointExtractor (cv::goodFeaturesToTrack: Shi-Tomasi corners, the measure LK's own minEigThreshold test uses) instead
+    // of the grid.  Off: every method issues the calls it always issued.
+    bool GFTT_FLAG = false;
+    int gfttMaxCorners = 1000;
+    double gfttQuality = 0.01;
+    double gfttMinDistance = 10;
     // with DENSE_FLAG == false and SURF_FLAG == false: true = the sparse branch with the commented detector / descriptor pair of
     // src/triangulation.cpp:79-80, StarDetector::create() (starMaxSize, starResponseThreshold; the other arguments at their
     // defaults) + BriefDescriptorExtractor::create(), in ORB's place.  Off: every method issues the calls it always issued.
@@ -161,6 +168,41 @@ class visualSLAM {
         return out;
     }
 
+    // ---- cv::goodFeaturesToTrack(img, corners, gfttMaxCorners, gfttQuality, gfttMinDistance) as GFTTDetector::detect returns it ----
+    // Key points in acceptance order (measure descending among the accepted) with size = the block size, angle -1 and the
+    // measure as response.
+    std::vector<KeyPoint> gfttKeypointExtractor(Mat img)
+    {
+        std::vector<KeyPoint> out;
+        if (mat_data(img) == nullptr)
+            return out;
+        svo_gftt_params prm;
+        svo_gftt_default_params(&prm);
+        prm.max_corners = gfttMaxCorners;
+        prm.quality_level = gfttQuality;
+        prm.min_distance = gfttMinDistance;
+        const uint8_t *imgs[1] = {mat_data(img)};
+        const int w = mat_cols(img), h = mat_rows(img), c = mat_channels(img);
+        int cap = gfttMaxCorners > 0 ? gfttMaxCorners : 4096, n = 0;
+        std::vector<float> xy, resp;
+        for (;;) {
+            xy.resize((size_t)cap * 2);
+            resp.resize((size_t)cap);
+            const int rc = svo_gftt_detect_batch(ctx_, imgs, nullptr, 1, w, h, c, &prm, cap, xy.data(), resp.data(), &n, SVO_MEM_HOST);
+            if (rc != SVO_ERR_CAPACITY)
+                check(rc);
+            if (rc == SVO_OK)
+                break;
+            cap = n;  // the needed count
+        }
+        out.reserve((size_t)n);
+        for (int i = 0; i < n; i++) {
+            out.emplace_back(xy[2 * (size_t)i], xy[2 * (size_t)i + 1], (float)prm.block_size);
+            out.back().response = resp[(size_t)i];
+        }
+        return out;
+    }
+
     // ---- src/triangulation.cpp:79: StarDetector::create(starMaxSize, starResponseThreshold)->detect(img, kps) ----
     // Key points carry their size (the outer size of the winning pattern) and response (negative for dark blobs), angle -1 and
     // octave 0 as the detector leaves them; a tile's maximum before its minimum, tiles in row-major order.
@@ -204,7 +246,7 @@ class visualSLAM {
         compact2(mask, refPts, trkPts);
     }
 
-    // ---- src/triangulation.cpp:73-166 (both branches of DENSE_FLAG; FAST_FLAG swaps the dense branch's key-point source) ----
+    // ---- src/triangulation.cpp:73-166 (both branches of DENSE_FLAG; FAST_FLAG, else GFTT_FLAG: the dense branch's key-point source) ----
     void stereoTriangulate(const Mat &im1, const Mat &im2, std::vector<Point3f> &ref3dPts,
                            std::vector<Point2f> &ref2dPts)
     {
@@ -214,7 +256,9 @@ class visualSLAM {
         }
         std::vector<Point2f> refPts, trkPts;
         if (DENSE_FLAG) {
-            std::vector<KeyPoint> dkps = FAST_FLAG ? fastKeypointExtractor(im1) : denseKeypointExtractor(im1, gridStep);
+            std::vector<KeyPoint> dkps = FAST_FLAG   ? fastKeypointExtractor(im1)
+                                         : GFTT_FLAG ? gfttKeypointExtractor(im1)
+                                                     : denseKeypointExtractor(im1, gridStep);
             for (const KeyPoint &k : dkps)
                 refPts.emplace_back(k.pt);
             denseLKtracking(im1, im2, refPts, trkPts);

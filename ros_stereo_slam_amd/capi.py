@@ -1110,6 +1110,69 @@ def fast_anms(self, images, num_to_keep, threshold=10, nonmax=True, max_keypoint
     return _fast_call(self, images, prm, cap, int(num_to_keep), False)
 
 
+class GfttParams(C.Structure):
+    """``svo_gftt_params``: goodFeaturesToTrack's arguments (max_corners <= 0 = all)."""
+    _fields_ = [("max_corners", C.c_int), ("block_size", C.c_int), ("use_harris", C.c_int), ("pad", C.c_int),
+                ("quality_level", C.c_double), ("min_distance", C.c_double), ("k", C.c_double)]
+
+
+def gftt_params(**overrides) -> GfttParams:
+    return _make_params(GfttParams, "svo_gftt_default_params", overrides)
+
+
+_GFTT_COLUMNS = [("xy", np.float32, 2), ("response", np.float32, 1)]
+
+
+@_ctx_method
+def gftt_detect(self, images, masks=None, params=None, cap=None, **overrides):
+    """``svo_gftt_detect_batch``: cv::goodFeaturesToTrack on 1 ... 16 images of one size (host arrays or device tensors) in one set
+    of launches -> per image (xy [n, 2], response [n]) float32 host arrays in acceptance order.  ``masks``: None, or one entry per
+    image, each None or an [h, w] uint8 array / tensor where the images live.  ``params``: a GfttParams or a dict; keyword
+    arguments override its fields.  More than ``cap`` corners in an image: SvoError(SVO_ERR_CAPACITY) whose ``needed`` lists the
+    counts."""
+    prm = _as_params(GfttParams, gftt_params, params)
+    for k, v in overrides.items():
+        assert hasattr(prm, k), k
+        setattr(prm, k, v)
+    w, h, c = _image_shape(images[0])
+    if cap is None:
+        cap = max((w - 2) * (h - 2), 1)          # no image has more corners than interior pixels
+    mptrs = None
+    if masks is not None:
+        assert len(masks) == len(images)
+        dev = _is_device(images[0])
+        masks = [None if m is None else m.contiguous() if dev else np.ascontiguousarray(m, np.uint8) for m in masks]
+        mptrs = (C.c_void_p * max(len(masks), 1))(*[_ptr(m).value for m in masks])
+    fn = lambda ctx, ptrs, *rest: self.lib.svo_gftt_detect_batch(ctx, ptrs, mptrs, *rest)   # the masks follow the images
+    col, n, _ = _batch_call(self, fn, images, _GFTT_COLUMNS, cap, (C.byref(prm), cap))
+    return _cut(col.values(), n)
+
+
+@_ctx_method
+def gftt_response(self, image, params=None, **overrides) -> np.ndarray:
+    """``svo_gftt_response`` -> the corner measure of every pixel before thresholding, [h, w] float32 (host array or device
+    tensor in, host array out)."""
+    prm = _as_params(GfttParams, gftt_params, params)
+    for k, v in overrides.items():
+        assert hasattr(prm, k), k
+        setattr(prm, k, v)
+    w, h, c = _image_shape(image)
+    dev = _is_device(image)
+    if dev:
+        import torch
+
+        image = image.contiguous()
+        eig = torch.zeros((h, w), dtype=torch.float32, device=image.device)
+        torch.cuda.synchronize(image.device)
+    else:
+        image, eig = np.ascontiguousarray(image, np.uint8), np.zeros((h, w), np.float32)
+    _check(self.lib.svo_gftt_response(self._h, _ptr(image), w, h, c, C.byref(prm), _ptr(eig), _mem_of(dev)))
+    if dev:
+        _check(self.lib.svo_ctx_sync(self._h))
+        eig = eig.cpu().numpy()
+    return eig
+
+
 class StarParams(C.Structure):
     """``svo_star_params``: xfeatures2d::StarDetector::create's arguments."""
     _fields_ = [("max_size", C.c_int), ("response_threshold", C.c_int), ("line_threshold_projected", C.c_int),

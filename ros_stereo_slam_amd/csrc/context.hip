@@ -215,7 +215,7 @@ int svo_ctx_destroy(svo_ctx *ctx)
                       &ctx->feat_img, &ctx->feat_sum, &ctx->sift_pyr, &ctx->sift_work, &ctx->sift_out,
                       &ctx->brief_work, &ctx->brief_pat, &ctx->surf_planes, &ctx->surf_work,
                       &ctx->wls_work, &ctx->wls_maps, &ctx->wls_lut, &ctx->fast_work,
-                      &ctx->voxel_work, &ctx->voxel_stage, &ctx->rect_stage, &ctx->bm_work};
+                      &ctx->voxel_work, &ctx->voxel_stage, &ctx->rect_stage, &ctx->bm_work, &ctx->gftt_work};
     for (DevBuf *b : bufs)
         b->release();
     ctx->up_ring.release();

@@ -224,6 +224,9 @@ struct svo_ctx {
     // fast.hip: the grey, fired and score planes of a batch, the per-wavefront counts and offsets of the ordered compaction, the
     // key-point lists of host calls and of the chained ANMS (layout: fast_plan.hip.h)
     DevBuf fast_work;
+    // gftt.hip: the measure planes of a batch, the candidate keys and the sort's ping-pong arrays, the cell lists and states of the
+    // selection, the staged masks and the corner lists of host calls (layout: gftt_plan.hip.h)
+    DevBuf gftt_work;
     // voxel.hip: the keys, the sort's ping-pong arrays and histograms, the rows gathered in voxel order and the segment
     // starts (layout: voxel_plan.hip.h); voxel_stage: the inputs and outputs of a host call
     DevBuf voxel_work, voxel_stage;
